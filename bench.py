@@ -15,6 +15,14 @@ back-to-back steps issued through model.forward_async (the latency-bound LSTM ta
 i+1 on a second HIP stream; every step is a complete forward, all K complete inside the timed region);
 `value_sequential` / `p50_forward_ms` are the same K steps as plain model(x) calls (no overlap).
 
+A plain run does only what the headline needs: it sets up, warms up, times the K steps of the headline leg and prints the line
+(`metric`, `value`, `unit`, `ms_per_step`, `higher_is_better`, `dtype` and the workload's config; the figures of the other legs are
+null).  `--full` adds every other leg described below -- the sequential and one-chain timings, p50 latency, the exact-fp32 leg, the
+weak leg beside a strong headline, the strong-scaling proxy, `allgather_us`, the rooflines, `cpu_baseline` and `parity`.
+`--dump-outputs DIR` writes the logits of the headline leg's last timed step as DIR/logits.npy (float32; above 64 MB a seeded
+sample of whole utterances, their indices in DIR/logits_rows.npy): the inputs and weights are keyed, so two builds run with the
+same arguments can be compared output for output.
+
 `value` is FP32-EMULATED arithmetic on the 16-bit matrix cores for the GEMM-shaped 82 % of the FLOPs (config.dense_scheme /
 config.linear_scheme say how: two fp16 terms per fp32 operand, three MFMAs per product, fp32 accumulate -- error vs fp64 at
 the level of an exact fp32 evaluation, tests/); `value_strict_f32` / `ms_per_step_strict_f32` are the same K steps in the
@@ -25,7 +33,7 @@ per GPU).  With N = 1 `strong_proxy` times the same steps at 64 / 8 = 8 utteranc
 `projected_x8` = 8 x its rate / `value` (north_star: >= 6 x).  `--force-collective` runs the RCCL all-gather with one rank too
 (`allgather_us`).
 
-One JSON line on stdout (rank 0).  Besides the driver's contract fields it carries
+One JSON line on stdout (rank 0).  Besides the driver's contract fields it carries, with --full,
   roofline      the node op of the search space -- since round 3 a whole cell of three grouped Conv1d per launch (grouped_cell_kernel),
                 the graded kernel of SURVEY.md 8(d).  Round 4: every launch priced under its OWN roofline -- x0 in, y out, weights
                 against 8 TB/s; the three convolutions' flops against the pipe the launch ran on (fp32 vector rate, or the bf16 MFMA
@@ -106,8 +114,17 @@ def main():
                          'control flow on a box with fewer GPUs than ranks -- ranks then share devices (local rank modulo the device count)')
     ap.add_argument('--force-collective', action='store_true',
                     help='take the RCCL path with one rank too: a 1-rank nccl group on this GPU, every step ends with the all-gather of '
-                         'the logits (parallel.ShardedForward(force_collective=True)); reports allgather_us')
+                         'the logits (parallel.ShardedForward(force_collective=True)); reports allgather_us with --full')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline leg, run every other leg of the line (sequential and one-chain timings, p50 latency, '
+                         'exact-fp32 leg, weak leg, strong-scaling proxy, allgather_us, rooflines, cpu_baseline, parity); '
+                         'off: set up, warm up, time the K steps, print')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the logits of the last timed step as DIR/logits.npy (float32, at most 64 MB: '
+                         'a seeded sample of whole utterances above that, their indices in DIR/logits_rows.npy)')
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit('--steps must be at least 1')
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
     rank = int(os.environ.get('RANK', '0'))
@@ -145,6 +162,15 @@ def main():
         args.no_strict = True
 
     cur = {'x': x}
+    # with N > 1 the headline is the strong-scaling leg: the SAME --batch utterances split over the ranks (a plain run times that leg only)
+    headline_strong = world > 1 and args.scaling == 'weak' and not args.no_strong and args.batch % world == 0
+    if headline_strong:
+        from nb_asr_amd.parallel import shard_bounds
+        lo, hi = shard_bounds(args.batch, world, rank)
+        x_strong = keyed_input(args.batch, args.frames, seed=0).to(device)[lo:hi].contiguous().to(x.dtype)
+        if not args.full:
+            cur['x'] = x_strong
+    frames_out = ((args.frames + 1) // 2 + 1) // 2
 
     def step():
         with torch.no_grad():
@@ -167,14 +193,15 @@ def main():
 
     tail_group = args.tail_group if args.tail_group == 'auto' else int(args.tail_group)
 
-    def pipelined(ways=None):
+    def pipelined(ways=None, steps=None):
         # back-to-back batches: the LSTM + head of step i run on a side stream while the main stream already runs the
         # encoder of step i+1 (model.forward_async); every step is a complete forward and all K finish before the
         # closing synchronize
         ways = args.in_flight if ways is None else ways
+        steps = args.steps if steps is None else steps
         if ways <= 1:
             with torch.no_grad():
-                handles = [model.forward_async(cur['x']) for _ in range(args.steps)]
+                handles = [model.forward_async(cur['x']) for _ in range(steps)]
                 out = None
                 for h in handles:
                     out = runner.gather_logits(h.result())
@@ -186,7 +213,7 @@ def main():
         if os.environ.get('NBASR_BENCH_FAIL_CHAINS') == '1':          # test hook: the one-GPU fall-back to one chain (in_flight_error)
             raise RuntimeError('NBASR_BENCH_FAIL_CHAINS=1')
         out = None
-        for o in model.forward_many([cur['x']] * args.steps, in_flight=ways, tail_group=tail_group):
+        for o in model.forward_many([cur['x']] * steps, in_flight=ways, tail_group=tail_group):
             out = runner.gather_logits(o)
         return out
 
@@ -194,56 +221,78 @@ def main():
         out = step()
     with torch.no_grad():
         for _ in range(2):
-            model.forward_async(x).result()
+            model.forward_async(cur['x']).result()
     in_flight_error = []
+
+    def warm_steps():
+        """Steps of one warm pass of the chains: K, or -- for a long timed pass -- fewer (at least 16) that hand every chain the same
+        tail-group keys as the K timed steps (the same group size, the same remainder, the same parity of the number of groups: a group's
+        key names the tail slot it alternates through), so that the untimed passes do not grow with K."""
+        n = max(1, 64 // max(int(cur['x'].shape[0]), 1)) if tail_group == 'auto' else max(1, tail_group)
+        period = 2 * max(args.in_flight, 1) * n
+        return min(args.steps, period * max(2, -(-16 // period)) + args.steps % period)
 
     def warm_chains():
         if args.in_flight > 1 and not args.no_pipeline:
+            warm = warm_steps()
             if world == 1 and not runner.collective and not in_flight_error:
                 # one GPU, no collective in the step: if the chains cannot run on this box (a stream that cannot be created, a capture the
                 # runtime refuses) the line says so and carries the one-chain number, instead of no line at all.  With N > 1 a rank must
                 # not change its sequence of collectives on its own: there the failure stays a failure.
                 try:
-                    pipelined()
+                    pipelined(steps=warm)
                 except Exception as e:          # noqa: BLE001
                     in_flight_error.append(f'{type(e).__name__}: {e}'[:400])
                     args.in_flight = 1
                     model._plans.clear()
                     return
             for _ in range(3):                            # every chain's plan, launch tapes (recorded at a key's second sight) and recurrence
-                pipelined()                               # graphs (captured at the third) exist before a timed region: with tail groups a
-                                                          # (member, slot) key comes up only once or twice in a pass of K steps
+                pipelined(steps=warm)                     # graphs (captured at the third) exist before a timed region: with tail groups a
+                                                          # (member, slot) key comes up only once or twice in a pass
+
+    def check_logits(o, rows):
+        assert o.shape == (rows, frames_out, 49) and bool(torch.isfinite(o.float()).all())
 
     warm_chains()
-    elapsed_seq, out = timed(sequential)
-    assert out.shape == (args.batch * world, (((args.frames + 1) // 2) + 1) // 2, 49) and bool(torch.isfinite(out.float()).all())
+    # the headline leg's rows: the global batch (strong) or --batch per rank, all-gathered (weak)
+    rows = args.batch if headline_strong and not args.full else args.batch * world
+    elapsed_seq = elapsed_one = p50 = None
+    if args.full or args.no_pipeline:
+        elapsed_seq, out = timed(sequential)
+        check_logits(out, rows)
+        head_out = out
     if args.no_pipeline:
         elapsed = elapsed_one = elapsed_seq
     else:
-        elapsed, out2 = timed(pipelined)
-        assert torch.equal(out2, out)
-        elapsed_one = elapsed
-        if args.in_flight > 1:
-            elapsed_one, out3 = timed(lambda: pipelined(1))          # the same K steps as ONE chain, beside the headline
-            assert torch.equal(out3, out)
+        elapsed, head_out = timed(pipelined)
+        if args.full:
+            assert torch.equal(head_out, out)
+            elapsed_one = elapsed
+            if args.in_flight > 1:
+                elapsed_one, out3 = timed(lambda: pipelined(1))          # the same K steps as ONE chain, beside the headline
+                assert torch.equal(out3, out)
+        else:
+            check_logits(head_out, rows)
+            out = head_out
 
-    # p50 forward latency: each forward bracketed by HIP events on the launch stream
-    lat = []
-    for _ in range(max(args.steps, 5)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        step()
-        e1.record()
-        e1.synchronize()
-        lat.append(e0.elapsed_time(e1))
-    p50 = statistics.median(lat)
+    if args.full:
+        # p50 forward latency: each forward bracketed by HIP events on the launch stream
+        lat = []
+        for _ in range(max(args.steps, 5)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            step()
+            e1.record()
+            e1.synchronize()
+            lat.append(e0.elapsed_time(e1))
+        p50 = statistics.median(lat)
 
     plan = model._plans.values()[-1]
     dense_schemes = dict(plan.dense_schemes)
 
     # the same K steps with every GEMM on the exact-fp32 MFMA (no operand splitting): the strict-fp32 number
     strict = None
-    if not args.no_strict and plan.dense_mode != 'f32':
+    if args.full and not args.no_strict and plan.dense_mode != 'f32':
         saved = {k: os.environ.get(k) for k in ('NBASR_DENSE_MODE', 'NBASR_LINEAR_MODE')}
         os.environ['NBASR_DENSE_MODE'] = os.environ['NBASR_LINEAR_MODE'] = 'f32'
         try:
@@ -275,10 +324,12 @@ def main():
 
     # strong scaling (N > 1): the SAME global batch of --batch utterances split over the ranks
     strong = None
-    if world > 1 and args.scaling == 'weak' and not args.no_strong and args.batch % world == 0:
-        from nb_asr_amd.parallel import shard_bounds
-        lo, hi = shard_bounds(args.batch, world, rank)
-        cur['x'] = keyed_input(args.batch, args.frames, seed=0).to(device)[lo:hi].contiguous().to(x.dtype)
+    if headline_strong and not args.full:
+        # a plain run: the leg timed above WAS the strong one
+        strong = {'value': args.batch * args.steps / elapsed, 'ms_per_step': 1e3 * elapsed / args.steps,
+                  'value_one_in_flight': None, 'ms_per_step_one_in_flight': None, 'per_gpu_batch': hi - lo, 'global_batch': args.batch}
+    elif headline_strong:
+        cur['x'] = x_strong
         for _ in range(3):
             step()
         with torch.no_grad():
@@ -286,6 +337,7 @@ def main():
         warm_chains()
         elapsed_strong, out_g = timed(sequential if args.no_pipeline else pipelined)
         assert out_g.shape[0] == args.batch
+        head_out = out_g
         elapsed_strong1 = elapsed_strong
         if args.in_flight > 1 and not args.no_pipeline:
             elapsed_strong1, out_g1 = timed(lambda: pipelined(1))
@@ -299,7 +351,7 @@ def main():
     # strong-scaled run of this batch computes per step (same model, same data: the first eighth of the batch).  8 x its rate over
     # this GPU's rate at the full batch is the speed-up 8 GPUs would reach if the all-gather were free (north star: >= 6 x)
     proxy = None
-    if world == 1 and args.scaling == 'weak' and not args.no_strong_proxy and args.batch >= 8 and args.batch % 8 == 0:
+    if args.full and world == 1 and args.scaling == 'weak' and not args.no_strong_proxy and args.batch >= 8 and args.batch % 8 == 0:
         b8 = args.batch // 8
         cur['x'] = x[:b8].contiguous()
         for _ in range(3):
@@ -327,7 +379,7 @@ def main():
 
     # the one collective of the path, on its own: HIP events around the all-gather of this rank's logits shard (RCCL when the group is nccl)
     allgather_us = None
-    if runner.collective:
+    if args.full and runner.collective:
         shard = out[: args.batch].contiguous() if out.shape[0] != args.batch else out
         for _ in range(5):
             runner.gather_logits(shard)
@@ -340,10 +392,18 @@ def main():
         allgather_us = runner.max_over_ranks(1e3 * e0.elapsed_time(e1) / 20)
 
     from nb_asr_amd import hip as nb_hip
-    weak_value, weak_ms = args.batch * world * args.steps / elapsed, 1e3 * elapsed / args.steps
+    weak_value = weak_ms = None                           # (a plain run with a strong headline times no weak leg)
+    if args.full or not headline_strong:
+        weak_value, weak_ms = args.batch * world * args.steps / elapsed, 1e3 * elapsed / args.steps
     # BASELINE's metric is quoted on the GLOBAL batch (B=64, T=1000) at 1/2/4/8 GPUs: with N > 1 the headline `value` is the
     # strong-scaling rate (the same --batch utterances split over the ranks) and the weak one (--batch per GPU) sits beside it
-    headline_strong = strong is not None
+    assert headline_strong == (strong is not None)
+
+    def per_step(seconds, utterances):
+        return (None, None) if seconds is None else (utterances * args.steps / seconds, 1e3 * seconds / args.steps)
+
+    value_one, ms_one = per_step(elapsed_one, args.batch * world)
+    value_seq, ms_seq = per_step(elapsed_seq, args.batch * world)
     result = {
         'metric': 'utterances_per_sec',
         'value': strong['value'] if headline_strong else weak_value,
@@ -357,15 +417,16 @@ def main():
         'in_flight': max(args.in_flight, 1) if not args.no_pipeline else 1,
         'in_flight_error': in_flight_error[0] if in_flight_error else None,
         'tail_group': (args.tail_group if args.in_flight > 1 and not args.no_pipeline else 1),
-        'value_one_in_flight': args.batch * world * args.steps / elapsed_one,
-        'ms_per_step_one_in_flight': 1e3 * elapsed_one / args.steps,
+        'value_one_in_flight': value_one,
+        'ms_per_step_one_in_flight': ms_one,
         'strong_proxy': proxy,
         'allgather_us': allgather_us,
         'p50_forward_ms': p50,
-        'value_b_over_p50': args.batch * world / (1e-3 * p50),          # SURVEY 8(d)'s definition: B / p50 of a single forward
-        'value_sequential': args.batch * world * args.steps / elapsed_seq,
-        'ms_per_step_sequential': 1e3 * elapsed_seq / args.steps,
+        'value_b_over_p50': args.batch * world / (1e-3 * p50) if p50 else None,          # SURVEY 8(d)'s definition: B / p50 of a single forward
+        'value_sequential': value_seq,
+        'ms_per_step_sequential': ms_seq,
         'higher_is_better': True,
+        'full': bool(args.full),
         'scaling': 'strong' if headline_strong else args.scaling,
         'vs_baseline': None,
         'dtype': args.dtype,
@@ -383,7 +444,7 @@ def main():
                                + (' -- bf16 storage (activations, GEMM operands), fp32 accumulation' if args.dtype == 'bf16' else ' -- fp32'),
                    'per_gpu_batch': strong['per_gpu_batch'] if headline_strong else args.batch,
                    'global_batch': strong['global_batch'] if headline_strong else args.batch * world,
-                   'weak_leg': {'per_gpu_batch': args.batch, 'global_batch': args.batch * world} if headline_strong else None,
+                   'weak_leg': {'per_gpu_batch': args.batch, 'global_batch': args.batch * world} if headline_strong and args.full else None,
                    'frames': args.frames, 'features': FEATURES,
                    'parallelism': (f'batch-sharded x{world}, one RCCL all-gather of logits' if world > 1 else
                                    'single GPU, 1-rank RCCL group: every step ends with the all-gather' if runner.collective else 'single GPU'),
@@ -401,14 +462,16 @@ def main():
                    'nbasr_env': {k: v for k, v in sorted(os.environ.items()) if k.startswith('NBASR_')}},
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         result.update(roofline_leg(model, x, args))
     parity_failed = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # `out` = the logits of the timed steps (the pipelined leg's are asserted bit-equal to them above)
         result['cpu_baseline'], result['parity'], result['parity_strict_f32'] = cpu_baseline_leg(
             model, args, x.detach().float().cpu(), out, strict['logits'] if strict else None)
         parity_failed = not result['parity']['ok'] or not (result['parity_strict_f32'] or {'ok': True})['ok']
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head_out)
     runner.barrier()
     runner.close()
     # RCCL writes its version banner to the C-level stdout buffer, which would otherwise be flushed at exit, AFTER the result:
@@ -422,6 +485,28 @@ def main():
         print(json.dumps(result), flush=True)
         if parity_failed:
             sys.exit('bench.py: the timed workload violates the parity rule (see "parity" in the line above)')
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, logits):
+    """The logits of the headline leg's last timed step -> DIR/logits.npy (float32).  Above DUMP_LIMIT_BYTES a fixed sample of whole
+    utterances (seeded, in batch order) is written instead, and their batch indices as DIR/logits_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    a = logits.detach().float().cpu().numpy()
+    rows_path = os.path.join(dirname, 'logits_rows.npy')
+    if os.path.exists(rows_path):
+        os.remove(rows_path)                              # (left by an earlier, larger run)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = (DUMP_LIMIT_BYTES - (1 << 20)) // (a.nbytes // a.shape[0])       # 1 MB for the row indices and the headers
+        if keep < 1:
+            sys.exit(f'bench.py: one utterance of logits is larger than {DUMP_LIMIT_BYTES >> 20} MB; cannot dump a sample of whole utterances')
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        np.save(rows_path, rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(dirname, 'logits.npy'), np.ascontiguousarray(a))
 
 
 def kernel_source_hash():

@@ -1,14 +1,14 @@
 """The benchmarking-dataset emitter (BASELINE config 5): format round trip, loader checks, work sharding (no GPU)."""
+import json
 import pathlib
 import pickle
-import sys
 
 import pytest
 
 from nb_asr_amd import bench_dataset, search_space
 
 ARCH = [[1, 0], [1, 0, 0], [1, 0, 0, 0]]
-REF = pathlib.Path('/root/reference')
+REF_ANSWERS = pathlib.Path(__file__).resolve().parent / 'golden' / 'reference_answers.json'
 
 
 def _rows():
@@ -95,37 +95,51 @@ def test_work_list_shards_cover_every_unique_architecture():
     assert max(len(p) for p in parts) - min(len(p) for p in parts) <= 1
 
 
-@pytest.mark.skipif(not REF.exists(), reason='reference checkout only exists in the build container')
+def _json(obj):
+    return json.loads(json.dumps(obj))
+
+
+def _pickles(path):
+    with open(path, 'rb') as f:                              # exactly two pickles: header, then rows
+        header, data = pickle.load(f), pickle.load(f)
+        assert f.read() == b''
+    return {'header': header, 'rows': data}
+
+
 def test_reference_loader_reads_the_file(tmp_path):
-    """Where the reference is available, its own BenchmarkingDataset / from_folder must load what we emit."""
+    """The reference's own BenchmarkingDataset loaded what this emitter writes: its answers are recorded in
+    tests/golden/reference_answers.json (tests/golden/make_reference_answers.py ran the loader on this emitter's files).  The emitter
+    must still write exactly the content that loader read, and the package's reader must answer as the loader did."""
+    want = json.loads(REF_ANSWERS.read_text())['bench_dataset']
+    assert want['arch'] == ARCH and _json(_rows()) == want['rows']
     path = tmp_path / bench_dataset.file_name('mi355x-fp32')
     bench_dataset.write_benchmarking_dataset(path, 'mi355x-fp32', _rows())
-    sys.path.insert(0, str(REF))
-    try:
-        from nasbench_asr import dataset as ref_dataset
-        ds = ref_dataset.BenchmarkingDataset([str(path)])
-        assert ds.devices == ['mi355x-fp32'] and ds.columns[:2] == ['model_hash', 'latency']
-        assert ds.latency(ARCH) == [[0.01]]
-        assert ds.latency(ARCH, return_dict=True) == {'mi355x-fp32': {'latency': 0.01}}
-        assert ds.latency([[5, 0], [5, 0, 0], [5, 0, 0, 0]]) is None
-        assert ARCH in ds
-        # two sweeps (1 GPU, 8 GPUs) load TOGETHER, and from_folder finds both and ignores the side-car files (ADVICE r1)
-        path8 = tmp_path / bench_dataset.file_name('mi355x-fp32-x8')
-        bench_dataset.write_benchmarking_dataset(path8, 'mi355x-fp32-x8', [[h, 2 * v] for h, v in _rows()], meta={'n_gpus': 8})
-        bench_dataset.write_benchmarking_dataset(path, 'mi355x-fp32', _rows(), meta={'n_gpus': 1})
-        both = ref_dataset.BenchmarkingDataset([str(path), str(path8)])
-        assert both.devices == ['mi355x-fp32', 'mi355x-fp32-x8']
-        assert both.latency(ARCH, return_dict=True) == {'mi355x-fp32': {'latency': 0.01}, 'mi355x-fp32-x8': {'latency': 0.02}}
-        # from_folder's file-name pattern (dataset.py:537,544; it also insists on a training file, which a latency sweep
-        # does not produce) picks up both pickles and neither side-car
-        import re
-        pattern = re.compile('nb-asr-bench-[a-zA-Z0-9-]+.pickle')
-        assert sorted(f.name for f in tmp_path.iterdir() if pattern.fullmatch(f.name)) == sorted([path.name, path8.name])
-        assert sum(f.name.endswith('.meta.json') for f in tmp_path.iterdir()) == 2
-    finally:
-        sys.path.remove(str(REF))
-        for name in [m for m in sys.modules if m.startswith('nasbench_asr')]:
-            del sys.modules[name]
+    one = want['one_device']
+    assert _json(_pickles(path)) == one['file']
+    assert one['devices'] == ['mi355x-fp32'] and one['columns'] == ['model_hash', 'latency']
+    assert one['latency_arch'] == [[0.01]]
+    assert one['latency_arch_dict'] == {'mi355x-fp32': {'latency': 0.01}}
+    assert one['latency_absent'] is None
+    assert one['arch_in'] is True
+    _, device, db = bench_dataset.read_benchmarking_dataset(path)
+    assert [device] == one['devices'] and [db[search_space.get_model_hash(ARCH)]] == one['latency_arch']
+    assert search_space.get_model_hash([[5, 0], [5, 0, 0], [5, 0, 0, 0]]) not in db
+    # two sweeps (1 GPU, 8 GPUs) load TOGETHER, and from_folder finds both and ignores the side-car files (ADVICE r1)
+    path8 = tmp_path / bench_dataset.file_name('mi355x-fp32-x8')
+    bench_dataset.write_benchmarking_dataset(path8, 'mi355x-fp32-x8', [[h, 2 * v] for h, v in _rows()], meta={'n_gpus': 8})
+    bench_dataset.write_benchmarking_dataset(path, 'mi355x-fp32', _rows(), meta={'n_gpus': 1})
+    two = want['two_devices']
+    assert _json(_pickles(path8)) == two['file_x8'] and _json(_pickles(path)) == one['file']
+    assert two['devices'] == ['mi355x-fp32', 'mi355x-fp32-x8']
+    assert two['latency_arch_dict'] == {'mi355x-fp32': {'latency': 0.01}, 'mi355x-fp32-x8': {'latency': 0.02}}
+    assert {bench_dataset.read_benchmarking_dataset(p)[1]: bench_dataset.read_benchmarking_dataset(p)[2][search_space.get_model_hash(ARCH)][0]
+            for p in (path, path8)} == {d: v['latency'] for d, v in two['latency_arch_dict'].items()}
+    # from_folder's file-name pattern (it also insists on a training file, which a latency sweep does not produce) picks up both
+    # pickles and neither side-car
+    import re
+    pattern = re.compile('nb-asr-bench-[a-zA-Z0-9-]+.pickle')
+    assert sorted(f.name for f in tmp_path.iterdir() if pattern.fullmatch(f.name)) == sorted([path.name, path8.name])
+    assert sum(f.name.endswith('.meta.json') for f in tmp_path.iterdir()) == 2
 
 
 def test_committed_full_sweep_covers_the_search_space():

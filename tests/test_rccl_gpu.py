@@ -91,7 +91,7 @@ def test_bench_force_collective_reports_the_allgather(tmp_path):
     repo = pathlib.Path(__file__).resolve().parent.parent
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, str(repo / 'bench.py'), '--batch', '8', '--frames', '200', '--steps', '3', '--warmup', '1',
-                          '--force-collective', '--no-cpu-baseline', '--no-strict', '--no-roofline'],
+                          '--full', '--force-collective', '--no-cpu-baseline', '--no-strict', '--no-roofline'],
                          capture_output=True, text=True, timeout=900, env=env, cwd=str(repo))
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

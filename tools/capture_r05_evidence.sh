@@ -8,7 +8,7 @@ bash tools/capture_profiles.sh r05 > $OUT/capture.log 2>&1
 cp -r $REPO/gpurun_out/profiles_r05/* $OUT/ 2>/dev/null
 cd $REPO
 for B in 8 16 32; do
-  python3 bench.py --batch $B --no-cpu-baseline --no-strict > $OUT/r05_bench_b$B.json 2> /dev/null
+  python3 bench.py --full --batch $B --no-cpu-baseline --no-strict > $OUT/r05_bench_b$B.json 2> /dev/null
   python3 -c "
 import json; d=json.loads(open('$OUT/r05_bench_b$B.json').read().strip().splitlines()[-1]); print($B, round(d['value']), d['ms_per_step'], d.get('p50_forward_ms'))"
 done
