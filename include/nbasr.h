@@ -240,6 +240,18 @@ int nbasr_lstm_recurrence_xcd(const float* gates_ws, const void* packed_whh16, f
  * read); the chain of `frames` launches is replayed as one cached graph where the call recurs, like nbasr_lstm_recurrence_packed. */
 int nbasr_lstm_recurrence_frames16(const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
                                    int batch, int frames, int hidden, nbasr_stream_t stream);
+/* The per-frame form with CARRIED STATE (streaming inference, nb_asr_amd/streaming.py): the arguments of
+ * nbasr_lstm_recurrence_frames16, plus
+ *   h0(batch, hidden): h of the frame before this call's first (the previous call's h_out[:, frames-1]); NULL = zeros;
+ *   flags: 0, or NBASR_LSTM_CONTINUE -- frame 0 then starts from c = cell_ws (the previous call's final cell state) and h = h0
+ *          instead of zeros.  h0 must be NULL without NBASR_LSTM_CONTINUE.
+ * h0 enters frame 0's w_hh . h product on the same fp16-pair path as every later frame, split with THIS call's per-utterance
+ * scale (from this call's gates).  h_n = h_out[:, frames-1] and c_n = cell_ws after the call.  flags = 0, h0 = NULL: bit-identical
+ * to nbasr_lstm_recurrence_frames16.  A chain of calls agrees with one call over all frames to fp32 round-off (the scale of a
+ * call depends on its own gates). */
+#define NBASR_LSTM_CONTINUE 2
+int nbasr_lstm_recurrence_frames16_state(const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
+                                         const float* h0, int batch, int frames, int hidden, int flags, nbasr_stream_t stream);
 
 /* CTC head nn.Linear(features -> classes) (reference model.py:101 / 122-124):
  * logits(rows, classes) = h(rows, features) . w(classes, features)^T + bias. */
@@ -345,6 +357,13 @@ int nbasr_skip_sum(const void* skip0, const void* skip1, const void* skip2, void
  *   nbasr_ctc_beam_search below. */
 int nbasr_ctc_postprocess(const float* logits, const int* lengths, float* log_probs, int* tokens, int* token_counts,
                           int batch, int frames, int classes, int blank, nbasr_stream_t stream);
+/* Greedy CTC decoding of ONE CHUNK of a stream of logits (nbasr_ctc_postprocess's greedy part, streaming inference):
+ *   logits(batch, frames, classes) = the chunk; prev(batch) int32, in/out: the argmax of the frame before the chunk (-1 at the start
+ *   of an utterance), replaced by the chunk's last argmax (unchanged for frames = 0).  tokens(batch, frames) int32 padded with -1,
+ *   token_counts(batch).  Repeats are collapsed across the chunk boundary, so the concatenated tokens of a chain of calls are those
+ *   of nbasr_ctc_postprocess over the concatenated logits. */
+int nbasr_ctc_greedy_stream(const float* logits, int* prev, int* tokens, int* token_counts,
+                            int batch, int frames, int classes, int blank, nbasr_stream_t stream);
 
 /* ---- validation decode (replaces reference training/torch/trainer.py:229-247 Trainer.decode) ----------
  * nbasr_ctc_beam_search: CTC prefix beam search without a language model, the algorithm of the reference's decoder
@@ -522,6 +541,17 @@ int nbasr_conv_fold(const float* cols, float* dx, int batch, int c_in, int frame
 int nbasr_lstm_gate_scan(float* pre, float* cells, int hidden, int frames, int batch, int ldb, nbasr_stream_t stream);
 int nbasr_lstm_backward_step(const float* dh_out, const float* w_hh_t, float* dc, const float* acts, const float* cells, float* dpre,
                              int hidden, int frames, int batch, int ldb, int t, nbasr_stream_t stream);
+
+/* ---- streaming windows (streaming inference, nb_asr_amd/streaming.py) ------------------------------------------------------
+ * nbasr_stream_window: rebuild one stage's input window.  Per row r < batch * channels (utterance r / channels):
+ *   dst[r][0 .. n_hist)              = hist[r][hist_off ..]   (the retained frames of the stage's previous window; hist != dst)
+ *   dst[r][n_hist .. n_hist + n_new) = src[r][src_off ..]     (frames the producing stage has just made final)
+ *   dst[r][n_hist + n_new .. dst_ld) = 0                      (the pitch columns: stale frames of an earlier, longer window)
+ * hist rows have pitch hist_ld, src rows src_ld, dst rows dst_ld (>= n_hist + n_new; no alignment required).  absmax(batch) or
+ * NULL: also max finite |dst[b]| per utterance (zeroed by the call first) -- the bound the f16x2 dense convolution takes for
+ * the whole window. */
+int nbasr_stream_window(const float* hist, int hist_ld, int hist_off, int n_hist, const float* src, int src_ld, int src_off, int n_new,
+                        float* dst, int dst_ld, int batch, int channels, float* absmax, nbasr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -65,10 +65,10 @@ __device__ __forceinline__ float finite_abs(float v) { const float a = fabsf(v);
 // every time and never replay); caches are per device; an entry is launched under the lock and destroyed only after the event behind
 // its last launch has completed; a stream that is being captured by the caller takes the plain launches.
 struct ChainKey {
-    const void* ptr[5];
-    int val[5];
+    const void* ptr[6];
+    int val[6];                                   // (an entry point that names fewer leaves the rest zero)
     bool operator==(const ChainKey& o) const {
-        for (int i = 0; i < 5; ++i) if (ptr[i] != o.ptr[i] || val[i] != o.val[i]) return false;
+        for (int i = 0; i < 6; ++i) if (ptr[i] != o.ptr[i] || val[i] != o.val[i]) return false;
         return true;
     }
 };

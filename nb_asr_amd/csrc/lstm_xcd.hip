@@ -280,7 +280,7 @@ __device__ __forceinline__ int lx_publish_offset(int slice, int wave, int n16)
 template <int WPB>
 __global__ __launch_bounds__(64 * WPB) void lstm_step16_kernel(
     const float* __restrict__ gates_in, const unsigned char* __restrict__ wp, float* __restrict__ cell, float* __restrict__ h_out,
-    unsigned char* tiles, int batch, int frames, int hidden, int t, int prio, int tiles_per_block)
+    unsigned char* tiles, int batch, int frames, int hidden, int t, int prio, int tiles_per_block, int cont)
 {
     constexpr int MAX_TPB = 4;                             // utterance tiles a workgroup walks with ONE fetch of its weights
     __shared__ xuint4 htile[LX_KSTEPS][2][64];
@@ -306,7 +306,7 @@ __global__ __launch_bounds__(64 * WPB) void lstm_step16_kernel(
         const size_t gate_off = static_cast<size_t>(min(eb, batch - 1)) * (4 * hidden) + min(eu, hidden - 1);
 #pragma unroll
         for (int g = 0; g < 4; ++g) pre[k][g] = live ? gates_in[static_cast<size_t>(t) * batch * (4 * hidden) + gate_off + g * hidden] : 0.f;
-        c_prev[k] = (live && t > 0 && eu < hidden && eb < batch) ? cell[static_cast<size_t>(eb) * hidden + eu] : 0.f;
+        c_prev[k] = (live && (t > 0 || cont) && eu < hidden && eb < batch) ? cell[static_cast<size_t>(eb) * hidden + eu] : 0.f;
     }
     xuint4 wfrag[LX_KSTEPS][2];
 #ifdef NBASR_LX_TAIL_EXPERIMENT
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(64 * WPB) void lstm_step16_kernel(
         for (int ks = 0; ks < LX_KSTEPS; ++ks) { wfrag[ks][0] = xuint4{0, 0, 0, 0}; wfrag[ks][1] = xuint4{0, 0, 0, 0}; }
     } else
 #endif
-    if (t > 0) {
+    if (t > 0 || cont) {
         // (a row tile beyond the layer -- the grid is rounded up to whole workgroups -- reads the zero rows the packer wrote up to the slice's end,
         // or, past the last slice, the last slice's: its sums are never stored)
         const int wslice = min(slice, (hidden + LX_UNITS - 1) / LX_UNITS - 1);
@@ -334,7 +334,7 @@ __global__ __launch_bounds__(64 * WPB) void lstm_step16_kernel(
         float hs, hs_inv;
         lx_h_scale(range[min(eb, batch - 1)], hs, hs_inv);
         xfloat4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        if (t > 0) {
+        if (t > 0 || cont) {
             const unsigned char* img = tile_ws + ((t - 1) & 1) * LX_IMAGE_BYTES;
             if (k > 0) __syncthreads();                    // every wave has read the previous tile's image
             // (columns of utterances beyond the batch are not fetched: nothing reads their sums, and a part-filled tile -- 8 utterances, one
@@ -360,6 +360,24 @@ __global__ __launch_bounds__(64 * WPB) void lstm_step16_kernel(
             cell[static_cast<size_t>(eb) * hidden + eu] = c_state;
         }
     }
+}
+
+// ---- carried state (streaming: nbasr_lstm_recurrence_frames16_state) ----------------------------------------------------------
+// h_(-1) = h0 enters frame 0's product through the image frame 0 reads (step parity 1), split exactly as lx_publish would have written
+// it -- hi + lo' 2^-11 of h0 x THIS call's per-utterance scale (the range words of this call's gates: written by lx_gate_range_kernel
+// just before).  One thread per (hidden unit, utterance); the rows of k beyond `hidden` and the columns beyond `batch` stay zero.
+__global__ __launch_bounds__(256) void lx_seed_h_kernel(const float* __restrict__ h0, unsigned char* __restrict__ tiles, int batch, int hidden)
+{
+    const int u = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (u >= hidden || b >= batch) return;
+    const unsigned* const range = reinterpret_cast<const unsigned*>(tiles) - (LX_HEADER_WORDS - LX_W_RANGE);
+    float hs, hs_inv;
+    lx_h_scale(range[b], hs, hs_inv);
+    const unsigned dw = lx_split_h(h0[static_cast<size_t>(b) * hidden + u], hs);
+    const int row_tile = u >> 2, slice = row_tile >> 2, wave = row_tile & 3;
+    unsigned char* const dst = tiles + static_cast<size_t>(b >> 4) * LX_TILE_BYTES + LX_IMAGE_BYTES + lx_publish_offset(slice, wave, b & 15) + 2 * (u & 3);
+    *reinterpret_cast<unsigned short*>(dst) = static_cast<unsigned short>(dw >> 16);
+    *reinterpret_cast<unsigned short*>(dst + 1024) = static_cast<unsigned short>(dw & 0xffffu);
 }
 
 // ---- the recurrence in ONE launch ------------------------------------------------------------------------------------------------
@@ -608,24 +626,23 @@ static int lx_grid(int hidden)
     return cached[device] >= lx_slices(hidden) ? cached[device] : 0;
 }
 
-extern "C" int nbasr_lstm_recurrence_frames16(const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
-                                              int batch, int frames, int hidden, nbasr_stream_t stream)
+static int lx_frames16(const char* what, const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
+                       const float* h0, int cont, int batch, int frames, int hidden, nbasr_stream_t stream)
 {
-    clear_error();
-    NBASR_REQUIRE(batch >= 0 && frames >= 0 && hidden > 0, NBASR_EINVAL, "nbasr_lstm_recurrence_frames16: bad sizes");
-    NBASR_REQUIRE(hidden % 4 == 0, NBASR_EALIGN, "nbasr_lstm_recurrence_frames16: hidden=%d must be a multiple of 4", hidden);
+    NBASR_REQUIRE(batch >= 0 && frames >= 0 && hidden > 0, NBASR_EINVAL, "%s: bad sizes", what);
+    NBASR_REQUIRE(hidden % 4 == 0, NBASR_EALIGN, "%s: hidden=%d must be a multiple of 4", what, hidden);
     if (batch == 0 || frames == 0) return NBASR_OK;
-    NBASR_REQUIRE(gates_ws && packed_whh16 && cell_ws && h_out && xcd_ws, NBASR_ENULL, "nbasr_lstm_recurrence_frames16: NULL pointer");
-    NBASR_REQUIRE(aligned16(packed_whh16) && aligned16(xcd_ws), NBASR_EALIGN, "nbasr_lstm_recurrence_frames16: packed_whh16, xcd_ws must be 16-byte aligned");
-    NBASR_REQUIRE(nbasr_lstm_xcd_workspace_bytes(batch, hidden) != 0, NBASR_EINVAL, "nbasr_lstm_recurrence_frames16: batch=%d hidden=%d does not fit the form "
-                  "(hidden <= %d, batch <= %d); use nbasr_lstm_recurrence_packed", batch, hidden, LX_KSTEPS * 32, LX_MAX_TILES * 16);
+    NBASR_REQUIRE(gates_ws && packed_whh16 && cell_ws && h_out && xcd_ws, NBASR_ENULL, "%s: NULL pointer", what);
+    NBASR_REQUIRE(aligned16(packed_whh16) && aligned16(xcd_ws), NBASR_EALIGN, "%s: packed_whh16, xcd_ws must be 16-byte aligned", what);
+    NBASR_REQUIRE(nbasr_lstm_xcd_workspace_bytes(batch, hidden) != 0, NBASR_EINVAL, "%s: batch=%d hidden=%d does not fit the form "
+                  "(hidden <= %d, batch <= %d); use nbasr_lstm_recurrence_packed", what, batch, hidden, LX_KSTEPS * 32, LX_MAX_TILES * 16);
     // the images are zeroed by every call (a node of the cached graph): the rows of k beyond `hidden` and the columns beyond `batch` are
     // never written, and a NaN pattern left there by an earlier owner of the memory would turn 0 x NaN into NaN sums
     const size_t tiles_n = (batch + 15) / 16;
-    struct Ctx { hipStream_t s; const float* gates; const unsigned char* w; float* cell; float* h; unsigned char* tiles; size_t tiles_bytes; int batch, frames, hidden, prio, wpb, tpb; };
+    struct Ctx { hipStream_t s; const float* gates; const unsigned char* w; float* cell; float* h; unsigned char* tiles; size_t tiles_bytes; const float* h0; int batch, frames, hidden, prio, wpb, tpb, cont; };
     Ctx ctx{as_stream(stream), gates_ws, static_cast<const unsigned char*>(packed_whh16), cell_ws, h_out,
-            static_cast<unsigned char*>(xcd_ws) + LX_HEADER_WORDS * sizeof(unsigned), tiles_n * LX_TILE_BYTES, batch, frames, hidden, 1,
-            batch <= 32 ? 2 : 4, 1};
+            static_cast<unsigned char*>(xcd_ws) + LX_HEADER_WORDS * sizeof(unsigned), tiles_n * LX_TILE_BYTES, h0, batch, frames, hidden, 1,
+            batch <= 32 ? 2 : 4, 1, cont};
     // (tiles per workgroup, NBASR_LX_TPB: walking 2 / 4 utterance tiles with one fetch of the weights halves / quarters the bytes a frame
     // moves, but a launch then lasts 2-4 x as long and the CHAIN becomes the critical path: 10 630 -> 10 150 -> 8 690 utterances/s at 64)
     // (same-box A/B of the shapes, pipelined utterances/s: 8 utterances 5 349 / 5 381 / - with 1 / 2 / 4 waves per workgroup, 16: 7 613 / 7 685 / 6 968,
@@ -634,21 +651,42 @@ extern "C" int nbasr_lstm_recurrence_frames16(const float* gates_ws, const void*
     if (const char* force = getenv("NBASR_LX_WPB")) ctx.wpb = (force[0] == '1') ? 1 : (force[0] == '2') ? 2 : 4;      // (A/B hook; every form gives the same bits)
     if (const char* force = getenv("NBASR_LX_PRIO")) ctx.prio = atoi(force);
     if (const char* force = getenv("NBASR_LX_TPB")) ctx.tpb = std::min(std::max(atoi(force), 1), 4);
-    const ChainKey key{{gates_ws, packed_whh16, cell_ws, h_out, xcd_ws}, {batch, frames, hidden, 16, ctx.wpb * 8 + ctx.tpb}};
-    return replay_chain(ctx.s, key, "nbasr_lstm_recurrence_frames16", [](void* p) {
+    // (h0 and the continue flag are part of the key: a graph bakes in the h0 pointer and whether frame 0 reads it)
+    const ChainKey key{{gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, h0}, {batch, frames, hidden, 16, ctx.wpb * 8 + ctx.tpb, cont}};
+    return replay_chain(ctx.s, key, what, [](void* p) {
         const Ctx& c = *static_cast<const Ctx*>(p);
         unsigned* const range = reinterpret_cast<unsigned*>(c.tiles) - (LX_HEADER_WORDS - LX_W_RANGE);
         zero_async(range, (LX_HEADER_WORDS - LX_W_RANGE) * sizeof(unsigned) + c.tiles_bytes, c.s);                     // the range words + the images
         hipLaunchKernelGGL(lx_gate_range_kernel, dim3((c.frames + 7) / 8, c.batch), dim3(256), 0, c.s, c.gates, range, c.batch, c.frames, 4 * c.hidden);
+        if (c.cont && c.h0)
+            hipLaunchKernelGGL(lx_seed_h_kernel, dim3((c.hidden + 255) / 256, c.batch), dim3(256), 0, c.s, c.h0, c.tiles, c.batch, c.hidden);
         const int row_tiles = (c.hidden + 3) / 4;
         const int n_tiles = (c.batch + 15) / 16;
         const dim3 grid((row_tiles + c.wpb - 1) / c.wpb, (n_tiles + c.tpb - 1) / c.tpb);
         for (int t = 0; t < c.frames; ++t) {
-            if (c.wpb == 1) hipLaunchKernelGGL(lstm_step16_kernel<1>, grid, dim3(64), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb);
-            else if (c.wpb == 2) hipLaunchKernelGGL(lstm_step16_kernel<2>, grid, dim3(128), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb);
-            else hipLaunchKernelGGL(lstm_step16_kernel<4>, grid, dim3(256), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb);
+            if (c.wpb == 1) hipLaunchKernelGGL(lstm_step16_kernel<1>, grid, dim3(64), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb, c.cont && t == 0);
+            else if (c.wpb == 2) hipLaunchKernelGGL(lstm_step16_kernel<2>, grid, dim3(128), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb, c.cont && t == 0);
+            else hipLaunchKernelGGL(lstm_step16_kernel<4>, grid, dim3(256), 0, c.s, c.gates, c.w, c.cell, c.h, c.tiles, c.batch, c.frames, c.hidden, t, c.prio, c.tpb, c.cont && t == 0);
         }
     }, &ctx);
+}
+
+extern "C" int nbasr_lstm_recurrence_frames16(const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
+                                              int batch, int frames, int hidden, nbasr_stream_t stream)
+{
+    clear_error();
+    return lx_frames16("nbasr_lstm_recurrence_frames16", gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, nullptr, 0, batch, frames, hidden, stream);
+}
+
+extern "C" int nbasr_lstm_recurrence_frames16_state(const float* gates_ws, const void* packed_whh16, float* cell_ws, float* h_out, void* xcd_ws,
+                                                    const float* h0, int batch, int frames, int hidden, int flags, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE((flags & ~NBASR_LSTM_CONTINUE) == 0, NBASR_EINVAL, "nbasr_lstm_recurrence_frames16_state: unknown flags 0x%x", flags);
+    NBASR_REQUIRE(h0 == nullptr || (flags & NBASR_LSTM_CONTINUE), NBASR_EINVAL,
+                  "nbasr_lstm_recurrence_frames16_state: h0 is read only with NBASR_LSTM_CONTINUE");
+    return lx_frames16("nbasr_lstm_recurrence_frames16_state", gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, h0,
+                       (flags & NBASR_LSTM_CONTINUE) ? 1 : 0, batch, frames, hidden, stream);
 }
 
 extern "C" size_t nbasr_lstm_xcd_workspace_bytes(int batch, int hidden)

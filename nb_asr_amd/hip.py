@@ -91,10 +91,12 @@ SIGNATURES = {
     'nbasr_lstm_xcd_workspace_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_lstm_recurrence_xcd': (_c_int, [_c_float_p] * 5 + [_c_int] * 4 + [_c_stream]),
     'nbasr_lstm_recurrence_frames16': (_c_int, [_c_float_p] * 5 + [_c_int] * 3 + [_c_stream]),
+    'nbasr_lstm_recurrence_frames16_state': (_c_int, [_c_float_p] * 6 + [_c_int] * 4 + [_c_stream]),
     'nbasr_linear_head': (_c_int, [_c_float_p] * 4 + [_c_int] * 3 + [_c_stream]),
     'nbasr_linear_head_bct': (_c_int, [_c_float_p] * 4 + [_c_int] * 5 + [_c_ln_p, _c_stream]),
     # post-logits step
     'nbasr_ctc_postprocess': (_c_int, [_c_float_p] * 5 + [_c_int] * 4 + [_c_stream]),
+    'nbasr_ctc_greedy_stream': (_c_int, [_c_float_p] * 4 + [_c_int] * 4 + [_c_stream]),
     'nbasr_ctc_loss': (_c_int, [_c_float_p] * 5 + [_c_int] * 6 + [_c_stream]),
     'nbasr_ctc_grad_workspace_bytes': (ctypes.c_size_t, [_c_int] * 3),
     'nbasr_ctc_loss_grad': (_c_int, [_c_float_p] * 7 + [_c_int] * 5 + [_c_stream]),
@@ -102,6 +104,8 @@ SIGNATURES = {
     'nbasr_ctc_beam_search': (_c_int, [_c_float_p] * 6 + [_c_int] * 6 + [_c_stream]),
     'nbasr_token_error_counts': (_c_int, [_c_float_p, _c_float_p, _c_int, _c_float_p, _c_float_p, _c_int, _c_float_p, _c_int, _c_int,
                                           _c_float_p, _c_int, _c_stream]),
+    # streaming windows
+    'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
     'nbasr_frame_signal': (_c_int, [_c_float_p, ctypes.c_void_p, _c_float_p] + [_c_int] * 6 + [_c_stream]),
     'nbasr_power_spectrum': (_c_int, [_c_float_p] * 2 + [_c_int] * 4 + [_c_stream]),
@@ -592,6 +596,7 @@ def lstm_seq_workspace(batch, hidden, device):
 
 HIP_ERROR_COOPERATIVE_LAUNCH_TOO_LARGE = 720       # hipErrorCooperativeLaunchTooLarge: nbasr_lstm_recurrence_seq passes a refused grid's code through
 LSTM_SEQ_INJECT_FAULT = 1       # NBASR_LSTM_SEQ_INJECT_FAULT of nbasr_lstm_recurrence_seq (tests)
+LSTM_CONTINUE = 2               # NBASR_LSTM_CONTINUE of nbasr_lstm_recurrence_frames16_state
 
 
 def lstm_recurrence_seq(gates_ws, packed_whh, cell_ws, h_out, seq_ws, flags=0):
@@ -672,6 +677,24 @@ def lstm_recurrence_frames16(gates_ws, packed_whh16, cell_ws, h_out, xcd_ws):
         raise HipError(f'lstm_recurrence_frames16: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace')
     _check(lib.nbasr_lstm_recurrence_frames16(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
                                               xcd_ws.data_ptr(), b, frames, hidden, _stream(h_out)), 'nbasr_lstm_recurrence_frames16')
+    return h_out
+
+
+def lstm_recurrence_frames16_state(gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, h0=None, flags=0):
+    """lstm_recurrence_frames16 with carried state: ``flags=LSTM_CONTINUE`` starts frame 0 from c = ``cell_ws`` and h = ``h0``
+    ((batch, hidden) float32, None = zeros) instead of zeros (nbasr.h).  flags = 0 and h0 = None: bit-identical to lstm_recurrence_frames16."""
+    b, frames, hidden = h_out.shape
+    lib = load_library()
+    if not packed_whh16.is_cuda or packed_whh16.dtype != torch.uint8 or packed_whh16.numel() != lib.nbasr_lstm_packed_whh16_bytes(hidden):
+        raise HipError('packed_whh16 must be the uint8 device tensor returned by lstm_pack_whh16 for this hidden size')
+    need = lstm_xcd_workspace_bytes(b, hidden)
+    if need == 0 or not xcd_ws.is_cuda or xcd_ws.dtype != torch.uint8 or xcd_ws.numel() < need:
+        raise HipError(f'lstm_recurrence_frames16_state: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace')
+    if h0 is not None and h0.numel() != b * hidden:
+        raise HipError(f'lstm_recurrence_frames16_state: h0 must hold ({b}, {hidden}) floats')
+    _check(lib.nbasr_lstm_recurrence_frames16_state(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'),
+                                                    _dev(h_out, 'h_out'), xcd_ws.data_ptr(), _opt(h0, 'h0'), b, frames, hidden, int(flags),
+                                                    _stream(h_out)), 'nbasr_lstm_recurrence_frames16_state')
     return h_out
 
 
@@ -858,6 +881,36 @@ def ctc_postprocess(logits, lengths=None, want_log_probs=True, want_tokens=True,
         None if tokens is None else tokens.data_ptr(), None if counts is None else counts.data_ptr(), b, t, c, blank,
         _stream(logits)), 'nbasr_ctc_postprocess')
     return log_probs, tokens, counts
+
+
+def ctc_greedy_stream(logits, prev, blank=0):
+    """Greedy CTC decoding of one chunk of a stream: logits (B, n, C) float32; ``prev`` (B) int32 device tensor, in/out: the argmax of
+    the frame before the chunk (-1 at an utterance's start), replaced by the chunk's last one.  Returns (tokens (B, n) int32 padded
+    with -1, token_counts (B) int32); repeats are collapsed across chunk boundaries (nbasr.h: nbasr_ctc_greedy_stream)."""
+    _dev(logits, 'logits')
+    b, t, c = logits.shape
+    _int_tensor(prev, 'prev', logits.device, (b,))
+    tokens = torch.empty(b, t, dtype=torch.int32, device=logits.device)
+    counts = torch.empty(b, dtype=torch.int32, device=logits.device)
+    _check(load_library().nbasr_ctc_greedy_stream(logits.data_ptr() if t else None, prev.data_ptr(), tokens.data_ptr() if t else None,
+                                                  counts.data_ptr(), b, t, c, blank, _stream(logits)), 'nbasr_ctc_greedy_stream')
+    return tokens, counts
+
+
+def stream_window(hist, hist_off, n_hist, src, src_off, n_new, dst, absmax=None):
+    """One stage window of a streaming session (nbasr.h: nbasr_stream_window).  ``hist`` / ``src`` / ``dst``: (batch, channels, ld)
+    float32 tensors with their own row pitches (``hist`` / ``src`` may be None when their frame count is 0); ``absmax`` (batch) or None."""
+    b, c, dst_ld = dst.shape
+    for t, what in ((hist, 'hist'), (src, 'src')):
+        if t is not None and (t.shape[0] != b or t.shape[1] != c):
+            raise HipError(f'stream_window: {what} has shape {tuple(t.shape)}, dst {tuple(dst.shape)}')
+    if absmax is not None and absmax.numel() != b:
+        raise HipError('stream_window: absmax must hold one float per utterance')
+    _check(load_library().nbasr_stream_window(
+        _opt(hist, 'hist') if n_hist else None, hist.shape[2] if hist is not None else 0, int(hist_off), int(n_hist),
+        _opt(src, 'src') if n_new else None, src.shape[2] if src is not None else 0, int(src_off), int(n_new),
+        _dev(dst, 'dst'), dst_ld, b, c, _opt(absmax, 'absmax'), _stream(dst)), 'nbasr_stream_window')
+    return dst
 
 
 def _int_tensor(t, what, device, shape=None):

@@ -271,6 +271,13 @@ class ASRModel(nn.Module):
         finally:
             self._plans.release(plan)
 
+    def stream(self, batch, max_chunk=160):
+        """A ``streaming.StreamingSession``: this model's forward chunk by chunk with carried state, for a lockstep batch of ``batch``
+        utterances and pushes of up to ``max_chunk`` input frames (larger ones are split).  ``sess.push(chunk)`` returns the logit frames
+        that have become final, ``sess.flush()`` the rest; together they are ``model(x)`` of the concatenated chunks (to fp32 round-off)."""
+        from .streaming import StreamingSession
+        return StreamingSession(self, batch, max_chunk)
+
     def check(self):
         """Wait for the forwards enqueued so far and raise ``hip.HipError`` if one of them ran the LSTM recurrence as one resident launch
         that timed out (compute units taken away by another process: its logits hold NaN rows).  A plain ``model(x)`` checks the
