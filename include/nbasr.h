@@ -403,6 +403,34 @@ int nbasr_ctc_beam_search(const float* log_probs, const int* lengths, void* ws, 
 int nbasr_token_error_counts(const int* hyp, const int* hyp_len, int ld_hyp, const int* ref, const int* ref_len, int ld_ref,
                              const int* table, int n_table, int blank, int* counts, int batch, nbasr_stream_t stream);
 
+/* ---- streaming beam decode (nb_asr_amd/ctc.py BeamSearchStream) -----------------------------------------------------------
+ * nbasr_ctc_beam_search resumed chunk by chunk: a chain of steps over the frames of a stream gives, after
+ * nbasr_ctc_beam_stream_finish, bit for bit what one nbasr_ctc_beam_search over the concatenated frames gives.
+ *   state: nbasr_ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes), 8-byte aligned, set up by nbasr_ctc_beam_stream_init
+ *   (every utterance at the empty prefix).  Per utterance it holds the live prefixes and a pool of pool_nodes token nodes; the pool
+ *   is last in each utterance's record, so a state grown to more pool nodes keeps its contents when each record's old bytes are
+ *   copied to the start of the new, larger record.
+ * nbasr_ctc_beam_stream_step: one chunk log_probs(batch, frames, classes); chunk_lengths(batch) or NULL: frames of the chunk that
+ *   count; chunk_lengths[b] < frames ends utterance b (later chunks are ignored for it).  Afterwards, per utterance:
+ *   committed(batch, pool_nodes) = the tokens that became final in this chunk (the longest common token prefix of all live
+ *   prefixes, minus what earlier steps committed), committed_counts(batch); partial(batch, pool_nodes) = the best live prefix's
+ *   tokens after the committed ones, partial_counts(batch); usage(batch) = pool nodes in use (at most 1 + the sum over the live
+ *   prefixes of their uncommitted lengths).  A step needs usage + beam_width * frames + 1 <= pool_nodes; an utterance for which
+ *   that does not hold is left as it was and reports usage = -1 (committed and partial counts 0).
+ *   ws: nbasr_ctc_beam_stream_workspace_bytes(batch, frames, classes, pool_nodes), no state between calls.
+ * nbasr_ctc_beam_stream_finish: the live prefixes' uncommitted suffixes, best first: beams(batch, beam_width, ld_beams) padded
+ *   with 0 (ld_beams >= the largest usage - 1 holds every suffix), scores(batch, beam_width) = -log P (FLT_MAX beyond the live
+ *   prefixes), beam_lens(batch, beam_width) = suffix lengths (-1 beyond the live prefixes).  The state is only read.
+ * Limits as nbasr_ctc_beam_search: classes <= 64, beam_width <= 32. */
+size_t nbasr_ctc_beam_stream_state_bytes(int batch, int beam_width, int pool_nodes);
+size_t nbasr_ctc_beam_stream_workspace_bytes(int batch, int frames, int classes, int pool_nodes);
+int nbasr_ctc_beam_stream_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed, int* committed_counts,
+                               int* partial, int* partial_counts, int* usage, int batch, int frames, int classes, int beam_width, int blank,
+                               int cutoff_top_n, int pool_nodes, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_finish(const void* state, int* beams, float* scores, int* beam_lens, int ld_beams, int batch, int beam_width,
+                                 int pool_nodes, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

@@ -19,6 +19,7 @@
 #include "common.h"
 
 #include <cfloat>
+#include <climits>
 
 namespace nbasr {
 
@@ -137,6 +138,157 @@ __device__ __forceinline__ unsigned long long extend_hash(unsigned long long h, 
     return h ^ (h >> 29);
 }
 
+// The state of one utterance's search between two frames: lane j holds live prefix j (lanes >= n_live: unused, at the defaults
+// of beam_lane_reset), lane c holds the merge mask of class c.  Pool nodes are (parent node, class) pairs; node 0 is the root.
+struct BeamLanes {
+    float p_b, p_nb, p_score;
+    int p_last, p_node, p_len;
+    int p_mp;                                       // index of the live prefix that is this one minus its last token, or -1
+    unsigned long long p_hash, p_phash;
+    unsigned merged;                                // class lane c: bit i set = (live prefix i + class c) is itself a live prefix
+    int n_live, n_nodes;
+};
+
+__device__ __forceinline__ void beam_lane_reset(BeamLanes& s)
+{
+    s.p_b = s.p_nb = s.p_score = NEG; s.p_last = -1; s.p_node = 0; s.p_len = 0; s.p_mp = -1; s.p_hash = 0ull; s.p_phash = ~0ull;
+}
+
+// class lanes: the extensions that are live prefixes themselves (from p_mp and p_last of the live prefixes)
+__device__ __forceinline__ unsigned merged_mask(int p_mp, int p_last, int n_live, int lane)
+{
+    unsigned merged = 0u;
+    for (int j = 0; j < n_live; ++j) {
+        const int mp = rl(p_mp, j), last = rl(p_last, j);
+        if (mp >= 0 && lane == last) merged |= 1u << mp;
+    }
+    return merged;
+}
+
+// One frame of the prefix beam search: `lp` = log-probability of class `lane` in this frame (pruned: -FLT_MAX).  New prefixes get
+// pool nodes n_nodes, n_nodes + 1, ... in rank order (at most `width` per frame).  The whole-utterance kernel and the resumable
+// one both run exactly this, so the two cannot drift apart.
+__device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __restrict__ pool, int classes, int width, int blank, int lane)
+{
+    float p_b = st.p_b, p_nb = st.p_nb, p_score = st.p_score;
+    int p_last = st.p_last, p_node = st.p_node, p_len = st.p_len, p_mp = st.p_mp;
+    unsigned long long p_hash = st.p_hash, p_phash = st.p_phash;
+    unsigned merged = st.merged;
+    int n_live = st.n_live, n_nodes = st.n_nodes;
+    const bool keep = lane < classes && lp > NEG;               // pruned by the pre-pass (or impossible): -FLT_MAX
+    const float lpk = keep ? lp : NEG;
+    const float lp_blank = rl(lpk, blank);
+
+    // ---- live prefixes (lane j): stay on blank / repeat the last class / absorb the extension that spells the same tokens
+    const float lp_last = __shfl(lpk, p_last >= 0 ? p_last : 0);
+    const int par = p_mp >= 0 ? p_mp : 0;
+    const float par_score = __shfl(p_score, par), par_b = __shfl(p_b, par);
+    const int par_last = __shfl(p_last, par);
+    float n_b = NEG, n_nb = NEG, n_score = NEG;
+    unsigned long long live_key = 0ull;
+    if (lane < n_live) {
+        n_b = lp_blank > NEG ? lp_blank + p_score : NEG;
+        if (p_last >= 0 && lp_last > NEG) {
+            n_nb = lp_last + p_nb;
+            if (p_mp >= 0) n_nb = log_sum_exp(n_nb, p_last == par_last ? (par_b > NEG ? lp_last + par_b : NEG) : lp_last + par_score);
+        }
+        n_score = log_sum_exp(n_b, n_nb);
+        live_key = beam_key(n_score, p_last + 1, width * BEAM_CLASSES + lane);
+    }
+
+    // The candidates (live prefix i + class c) are spread over the lanes by ROTATING the per-class values (log-probability,
+    // class id, merge mask) one lane per live prefix: neither the extensions of one strong prefix nor those by one strong
+    // class pile up in a single lane (a lane that wins more than twice in a frame has to rescan its candidates).
+    // ---- candidates of column `lane`: the live prefix of this lane and the extensions of every live prefix by class `lane`;
+    //      the best two are tracked, `taken` (bit i: extension of prefix i, bit 32: the live prefix) excludes picked ones
+    unsigned long long taken = 0ull;
+    auto column_scan = [=](unsigned long long excluded) -> ulonglong2 {
+        unsigned long long m1 = (excluded >> 32) & 1ull ? 0ull : live_key, m2 = 0ull;
+        float lp_c = lpk;                                        // log-probability of class (lane + i * step) mod 64
+        int cls = lane, mrg = static_cast<int>(merged);
+        for (int i = 0; i < n_live; ++i) {
+            const float sc = rl(p_score, i), bp = rl(p_b, i);
+            const int last = rl(p_last, i);
+            const float v = (cls == last) ? (bp > NEG ? lp_c + bp : NEG) : lp_c + sc;
+            unsigned long long k = beam_key(v, cls + 1, i * BEAM_CLASSES + cls);
+            if (!(lp_c > NEG) || cls == blank || (((mrg | static_cast<int>(excluded)) >> i) & 1)) k = 0ull;
+            const unsigned long long lo = k < m1 ? k : m1;
+            m1 = k > m1 ? k : m1;
+            m2 = lo > m2 ? lo : m2;
+            lp_c = wave_rotate(lp_c);
+            cls = wave_rotate(cls);
+            mrg = wave_rotate(mrg);
+        }
+        return make_ulonglong2(m1, m2);
+    };
+    ulonglong2 best = column_scan(0ull);
+    unsigned long long mine = best.x, second = best.y;
+    bool second_known = true;
+
+    // ---- the `width` best of everything, best first: lane r keeps the winner of round r
+    unsigned long long my_pick = 0ull;
+    int n_next = 0;
+    for (int r = 0; r < width; ++r) {
+        const unsigned long long top = wave_best_key(mine);
+        if (top == 0ull) break;                                    // fewer candidates than the beam is wide
+        if (lane == r) my_pick = top;
+        bool rescan = false;
+        if (mine == top) {                                         // exactly one lane: the slot makes keys unique
+            const int row = (0xFFFF - static_cast<int>(top & 0xFFFFu)) / BEAM_CLASSES;
+            taken |= 1ull << (row == width ? 32 : row);
+            if (second_known) { mine = second; second_known = false; }
+            else rescan = true;
+        }
+        if (__any(rescan)) {                                       // by ALL lanes: the scan rotates values across the wavefront
+            best = column_scan(taken);
+            mine = best.x; second = best.y; second_known = true;
+        }
+        ++n_next;
+    }
+
+    // ---- the survivors become the live prefixes of the next frame: lane r gathers entry r from its source lane
+    const int slot = 0xFFFF - static_cast<int>(my_pick & 0xFFFFu), row = slot / BEAM_CLASSES, col = slot % BEAM_CLASSES;
+    const bool mine_valid = lane < n_next, survivor = row == width;
+    const int src = mine_valid ? (survivor ? col : row) : 0;
+    const float s_nb_new = __shfl(n_nb, src), s_b_new = __shfl(n_b, src), s_score_new = __shfl(n_score, src);
+    const float s_b = __shfl(p_b, src), s_score = __shfl(p_score, src);
+    const int s_last = __shfl(p_last, src), s_node = __shfl(p_node, src), s_len = __shfl(p_len, src);
+    const unsigned long long s_hash = shfl64(p_hash, src), s_phash = shfl64(p_phash, src);
+    const float lp_col = __shfl(lpk, mine_valid && !survivor ? col : 0);
+    if (mine_valid && survivor) {
+        p_b = s_b_new; p_nb = s_nb_new; p_score = s_score_new;
+        p_last = s_last; p_node = s_node; p_len = s_len; p_hash = s_hash; p_phash = s_phash;
+    } else if (mine_valid) {
+        const float v = (col == s_last) ? (s_b > NEG ? lp_col + s_b : NEG) : lp_col + s_score;
+        p_b = NEG; p_nb = v; p_score = v;
+        p_last = col; p_len = s_len + 1; p_phash = s_hash; p_hash = extend_hash(s_hash, col);
+        p_node = -1 - s_node;                                       // parent's node, until this prefix gets its own
+    } else {
+        p_b = p_nb = p_score = NEG; p_last = -1; p_node = 0; p_len = 0; p_hash = 0ull; p_phash = ~0ull;
+    }
+    // new pool nodes in rank order
+    const bool is_new = mine_valid && p_node < 0;
+    const unsigned long long new_mask = __ballot(is_new);
+    if (is_new) {
+        const int id = n_nodes + __popcll(new_mask & ((1ull << lane) - 1ull));
+        pool[id] = make_int2(-1 - p_node, p_last);
+        p_node = id;
+    }
+    n_nodes += __popcll(new_mask);
+    n_live = n_next;
+    // which live prefix is this one minus its last token (same length - 1, same token string)
+    p_mp = -1;
+    for (int i = 0; i < n_live; ++i)
+        if (rl(p_hash, i) == p_phash && rl(p_len, i) + 1 == p_len) p_mp = i;
+    if (lane >= n_live || p_last < 0) p_mp = -1;
+    // class lanes: the extensions that are live prefixes themselves
+    merged = merged_mask(p_mp, p_last, n_live, lane);
+    st.p_b = p_b; st.p_nb = p_nb; st.p_score = p_score;
+    st.p_last = p_last; st.p_node = p_node; st.p_len = p_len; st.p_mp = p_mp;
+    st.p_hash = p_hash; st.p_phash = p_phash;
+    st.merged = merged; st.n_live = n_live; st.n_nodes = n_nodes;
+}
+
 __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ lengths, int2* __restrict__ pool_all, int* __restrict__ beams,
     float* __restrict__ scores, int* __restrict__ beam_lens, int frames, int classes, int width, int blank)
@@ -146,141 +298,29 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     int2* __restrict__ pool = pool_all + static_cast<size_t>(b) * (static_cast<size_t>(frames) * width + 1);
     const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
 
-    // live prefix `lane` (lanes >= n_live: unused).  The empty prefix: P(blank-ending) = 1, hash 0, pool node 0.
-    float p_b = lane == 0 ? 0.f : NEG, p_nb = NEG, p_score = lane == 0 ? 0.f : NEG;
-    int p_last = -1, p_node = 0, p_len = 0;
-    int p_mp = -1;                                  // index of the live prefix that is this one minus its last token, or -1
-    unsigned long long p_hash = 0ull, p_phash = ~0ull;
-    // The candidates (live prefix i + class c) are spread over the lanes by ROTATING the per-class values (log-probability,
-    // class id, merge mask) one lane per live prefix: neither the extensions of one strong prefix nor those by one strong
-    // class pile up in a single lane (a lane that wins more than twice in a frame has to rescan its candidates).
-    unsigned merged = 0u;                           // class lane c: bit i set = (live prefix i + class c) is itself a live prefix
-    int n_live = 1, n_nodes = 1;
+    // the empty prefix: P(blank-ending) = 1, hash 0, pool node 0
+    BeamLanes st;
+    beam_lane_reset(st);
+    if (lane == 0) st.p_b = st.p_score = 0.f;
+    st.merged = 0u;
+    st.n_live = 1; st.n_nodes = 1;
     if (lane == 0) pool[0] = make_int2(-1, -1);
 
     float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
     for (int t = 0; t < len; ++t) {
         const float lp = lp_next;                                                                       // class `lane` of frame t
         if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];  // in flight during this frame
-        const bool keep = lane < classes && lp > NEG;               // pruned by the pre-pass (or impossible): -FLT_MAX
-        const float lpk = keep ? lp : NEG;
-        const float lp_blank = rl(lpk, blank);
-
-        // ---- live prefixes (lane j): stay on blank / repeat the last class / absorb the extension that spells the same tokens
-        const float lp_last = __shfl(lpk, p_last >= 0 ? p_last : 0);
-        const int par = p_mp >= 0 ? p_mp : 0;
-        const float par_score = __shfl(p_score, par), par_b = __shfl(p_b, par);
-        const int par_last = __shfl(p_last, par);
-        float n_b = NEG, n_nb = NEG, n_score = NEG;
-        unsigned long long live_key = 0ull;
-        if (lane < n_live) {
-            n_b = lp_blank > NEG ? lp_blank + p_score : NEG;
-            if (p_last >= 0 && lp_last > NEG) {
-                n_nb = lp_last + p_nb;
-                if (p_mp >= 0) n_nb = log_sum_exp(n_nb, p_last == par_last ? (par_b > NEG ? lp_last + par_b : NEG) : lp_last + par_score);
-            }
-            n_score = log_sum_exp(n_b, n_nb);
-            live_key = beam_key(n_score, p_last + 1, width * BEAM_CLASSES + lane);
-        }
-
-        // ---- candidates of column `lane`: the live prefix of this lane and the extensions of every live prefix by class `lane`;
-        //      the best two are tracked, `taken` (bit i: extension of prefix i, bit 32: the live prefix) excludes picked ones
-        unsigned long long taken = 0ull;
-        auto column_scan = [=](unsigned long long excluded) -> ulonglong2 {
-            unsigned long long m1 = (excluded >> 32) & 1ull ? 0ull : live_key, m2 = 0ull;
-            float lp_c = lpk;                                        // log-probability of class (lane + i * step) mod 64
-            int cls = lane, mrg = static_cast<int>(merged);
-            for (int i = 0; i < n_live; ++i) {
-                const float sc = rl(p_score, i), bp = rl(p_b, i);
-                const int last = rl(p_last, i);
-                const float v = (cls == last) ? (bp > NEG ? lp_c + bp : NEG) : lp_c + sc;
-                unsigned long long k = beam_key(v, cls + 1, i * BEAM_CLASSES + cls);
-                if (!(lp_c > NEG) || cls == blank || (((mrg | static_cast<int>(excluded)) >> i) & 1)) k = 0ull;
-                const unsigned long long lo = k < m1 ? k : m1;
-                m1 = k > m1 ? k : m1;
-                m2 = lo > m2 ? lo : m2;
-                lp_c = wave_rotate(lp_c);
-                cls = wave_rotate(cls);
-                mrg = wave_rotate(mrg);
-            }
-            return make_ulonglong2(m1, m2);
-        };
-        ulonglong2 best = column_scan(0ull);
-        unsigned long long mine = best.x, second = best.y;
-        bool second_known = true;
-
-        // ---- the `width` best of everything, best first: lane r keeps the winner of round r
-        unsigned long long my_pick = 0ull;
-        int n_next = 0;
-        for (int r = 0; r < width; ++r) {
-            const unsigned long long top = wave_best_key(mine);
-            if (top == 0ull) break;                                    // fewer candidates than the beam is wide
-            if (lane == r) my_pick = top;
-            bool rescan = false;
-            if (mine == top) {                                         // exactly one lane: the slot makes keys unique
-                const int row = (0xFFFF - static_cast<int>(top & 0xFFFFu)) / BEAM_CLASSES;
-                taken |= 1ull << (row == width ? 32 : row);
-                if (second_known) { mine = second; second_known = false; }
-                else rescan = true;
-            }
-            if (__any(rescan)) {                                       // by ALL lanes: the scan rotates values across the wavefront
-                best = column_scan(taken);
-                mine = best.x; second = best.y; second_known = true;
-            }
-            ++n_next;
-        }
-
-        // ---- the survivors become the live prefixes of the next frame: lane r gathers entry r from its source lane
-        const int slot = 0xFFFF - static_cast<int>(my_pick & 0xFFFFu), row = slot / BEAM_CLASSES, col = slot % BEAM_CLASSES;
-        const bool mine_valid = lane < n_next, survivor = row == width;
-        const int src = mine_valid ? (survivor ? col : row) : 0;
-        const float s_nb_new = __shfl(n_nb, src), s_b_new = __shfl(n_b, src), s_score_new = __shfl(n_score, src);
-        const float s_b = __shfl(p_b, src), s_score = __shfl(p_score, src);
-        const int s_last = __shfl(p_last, src), s_node = __shfl(p_node, src), s_len = __shfl(p_len, src);
-        const unsigned long long s_hash = shfl64(p_hash, src), s_phash = shfl64(p_phash, src);
-        const float lp_col = __shfl(lpk, mine_valid && !survivor ? col : 0);
-        if (mine_valid && survivor) {
-            p_b = s_b_new; p_nb = s_nb_new; p_score = s_score_new;
-            p_last = s_last; p_node = s_node; p_len = s_len; p_hash = s_hash; p_phash = s_phash;
-        } else if (mine_valid) {
-            const float v = (col == s_last) ? (s_b > NEG ? lp_col + s_b : NEG) : lp_col + s_score;
-            p_b = NEG; p_nb = v; p_score = v;
-            p_last = col; p_len = s_len + 1; p_phash = s_hash; p_hash = extend_hash(s_hash, col);
-            p_node = -1 - s_node;                                       // parent's node, until this prefix gets its own
-        } else {
-            p_b = p_nb = p_score = NEG; p_last = -1; p_node = 0; p_len = 0; p_hash = 0ull; p_phash = ~0ull;
-        }
-        // new pool nodes in rank order
-        const bool is_new = mine_valid && p_node < 0;
-        const unsigned long long new_mask = __ballot(is_new);
-        if (is_new) {
-            const int id = n_nodes + __popcll(new_mask & ((1ull << lane) - 1ull));
-            pool[id] = make_int2(-1 - p_node, p_last);
-            p_node = id;
-        }
-        n_nodes += __popcll(new_mask);
-        n_live = n_next;
-        // which live prefix is this one minus its last token (same length - 1, same token string)
-        p_mp = -1;
-        for (int i = 0; i < n_live; ++i)
-            if (rl(p_hash, i) == p_phash && rl(p_len, i) + 1 == p_len) p_mp = i;
-        if (lane >= n_live || p_last < 0) p_mp = -1;
-        // class lanes: the extensions that are live prefixes themselves
-        merged = 0u;
-        for (int j = 0; j < n_live; ++j) {
-            const int mp = rl(p_mp, j), last = rl(p_last, j);
-            if (mp >= 0 && lane == last) merged |= 1u << mp;
-        }
+        beam_frame(st, lp, pool, classes, width, blank, lane);
     }
 
     // results, best first (the selection of the last frame already ordered them; a zero-length utterance has the empty prefix)
     __syncthreads();                                                   // pool entries written by other lanes
     if (lane < width) {
         int* out = beams + (static_cast<size_t>(b) * width + lane) * frames;
-        const bool live = lane < n_live;
-        const int n = live ? p_len : 0;
+        const bool live = lane < st.n_live;
+        const int n = live ? st.p_len : 0;
         if (live) {
-            int node = p_node;
+            int node = st.p_node;
             for (int k = n - 1; k >= 0; --k) {
                 const int2 e = pool[node];
                 out[k] = e.y;
@@ -288,9 +328,217 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
             }
         }
         for (int k = n; k < frames; ++k) out[k] = 0;
-        scores[static_cast<size_t>(b) * width + lane] = live ? -p_score : FLT_MAX;     // ctcdecode returns -log P
+        scores[static_cast<size_t>(b) * width + lane] = live ? -st.p_score : FLT_MAX;     // ctcdecode returns -log P
         beam_lens[static_cast<size_t>(b) * width + lane] = n;
     }
+}
+
+// ---- resumable prefix beam search (streaming decode) ---------------------------------------------------------------------------
+// The search of ctc_beam_search_kernel cut into chunks of frames, with the lanes' state stored between them.  Every candidate at
+// frame t + 1 is a live prefix at frame t or a one-token extension of one, so the longest common TOKEN prefix of the live prefixes
+// is a prefix of every beam the search can still return: after each chunk those tokens are committed (written out, never to change)
+// and the pool is compacted -- the committed prefix becomes root node 0, only the nodes below it that a live lane reaches are kept,
+// renumbered in their old order.  Hash and length keep covering the whole token string, so the search itself never sees the cut.
+//
+// State of one utterance, `beam_stream_record_bytes` bytes at a multiple of 8: a header of 16 ints (n_live, n_nodes, committed
+// tokens, ended), then p_hash[width], p_phash[width] (u64), p_b, p_nb, p_score (f32) and p_last, p_node, p_len, p_mp (i32) per lane,
+// then the pool (pool_nodes int2).  The pool comes last, so a larger pool keeps the layout of the smaller one's prefix.
+enum { BS_N_LIVE = 0, BS_N_NODES = 1, BS_COMMITTED = 2, BS_ENDED = 3, BS_HEADER_INTS = 16 };
+
+__host__ __device__ constexpr size_t beam_stream_lanes_bytes(int width) { return (16 * static_cast<size_t>(width) + 28 * static_cast<size_t>(width) + 7) & ~size_t(7); }
+__host__ __device__ constexpr size_t beam_stream_record_bytes(int width, int pool_nodes)
+{
+    return BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width) + static_cast<size_t>(pool_nodes) * sizeof(int2);
+}
+
+struct BeamStreamRecord {
+    int* hdr;
+    unsigned long long *hash, *phash;
+    float *pb, *pnb, *pscore;
+    int *last, *node, *len, *mp;
+    int2* pool;
+};
+
+__device__ __forceinline__ BeamStreamRecord beam_stream_record(char* state, int b, int width, int pool_nodes)
+{
+    char* r = state + static_cast<size_t>(b) * beam_stream_record_bytes(width, pool_nodes);
+    BeamStreamRecord rec;
+    rec.hdr = reinterpret_cast<int*>(r);
+    rec.hash = reinterpret_cast<unsigned long long*>(r + BS_HEADER_INTS * 4);
+    rec.phash = rec.hash + width;
+    rec.pb = reinterpret_cast<float*>(rec.phash + width);
+    rec.pnb = rec.pb + width;
+    rec.pscore = rec.pnb + width;
+    rec.last = reinterpret_cast<int*>(rec.pscore + width);
+    rec.node = rec.last + width;
+    rec.len = rec.node + width;
+    rec.mp = rec.len + width;
+    rec.pool = reinterpret_cast<int2*>(r + BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width));
+    return rec;
+}
+
+__device__ __forceinline__ void beam_stream_store(const BeamStreamRecord& rec, const BeamLanes& st, int lane, int width)
+{
+    if (lane < width) {
+        rec.hash[lane] = st.p_hash; rec.phash[lane] = st.p_phash;
+        rec.pb[lane] = st.p_b; rec.pnb[lane] = st.p_nb; rec.pscore[lane] = st.p_score;
+        rec.last[lane] = st.p_last; rec.node[lane] = st.p_node; rec.len[lane] = st.p_len; rec.mp[lane] = st.p_mp;
+    }
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restrict__ state, int width, int pool_nodes)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes);
+    BeamLanes st;
+    beam_lane_reset(st);
+    if (lane == 0) st.p_b = st.p_score = 0.f;                         // the empty prefix: P(blank-ending) = 1, hash 0, node 0
+    beam_stream_store(rec, st, lane, width);
+    if (lane < BS_HEADER_INTS) rec.hdr[lane] = lane == BS_N_LIVE || lane == BS_N_NODES ? 1 : 0;
+    if (lane == 0) rec.pool[0] = make_int2(-1, -1);
+}
+
+// One chunk of frames for every utterance (one wavefront each).  `ids`: pool_nodes ints of scratch per utterance (the renumbering).
+// committed / partial: rows of pool_nodes ints (the host keeps usage + width * n + 1 <= pool_nodes, which bounds both counts).
+// usage[b] = pool nodes in use afterwards, or -1: the chunk could overflow the pool, nothing was done.
+__global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
+    const float* __restrict__ log_probs, const int* __restrict__ chunk_lengths, char* __restrict__ state, int* __restrict__ ids_all,
+    int* __restrict__ committed, int* __restrict__ committed_counts, int* __restrict__ partial, int* __restrict__ partial_counts,
+    int* __restrict__ usage, int frames, int classes, int width, int blank, int pool_nodes)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes);
+    int2* __restrict__ pool = rec.pool;
+    const int n_live0 = rec.hdr[BS_N_LIVE], n_nodes0 = rec.hdr[BS_N_NODES], c_old = rec.hdr[BS_COMMITTED], ended = rec.hdr[BS_ENDED];
+    const int cl = chunk_lengths ? chunk_lengths[b] : frames;
+    const int len = ended ? 0 : min(max(cl, 0), frames);
+    if (static_cast<long long>(n_nodes0) + static_cast<long long>(width) * len + 1 > pool_nodes) {
+        if (lane == 0) { usage[b] = -1; committed_counts[b] = 0; partial_counts[b] = 0; }
+        return;
+    }
+    const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
+
+    // ---- the lanes as the previous chunk left them (lanes >= n_live: the defaults the frame body gives them)
+    BeamLanes st;
+    beam_lane_reset(st);
+    if (lane < n_live0) {
+        st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
+        st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
+        st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
+    }
+    st.n_live = n_live0; st.n_nodes = n_nodes0;
+    st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
+
+    float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
+    for (int t = 0; t < len; ++t) {
+        const float lp = lp_next;
+        if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];
+        beam_frame(st, lp, pool, classes, width, blank, lane);
+    }
+    __syncthreads();                                                   // pool entries written by other lanes
+
+    // ---- the committed prefix: longest common token prefix of all n_live lanes (walked from the shortest suffix's depth upwards;
+    //      once every lane stands on one node, the tokens above agree)
+    const int n_live = st.n_live;
+    const bool live = lane < n_live;
+    int d_min = INT_MAX;
+    for (int i = 0; i < n_live; ++i) d_min = min(d_min, rl(st.p_len, i));
+    d_min -= c_old;                                                    // >= 0: every live prefix extends the committed one
+    int node = live ? st.p_node : 0;
+    for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node].x;
+    int lcp = d_min;
+    for (int k = d_min; k >= 1; --k) {
+        if (__ballot(live && node != rl(node, 0)) == 0ull) break;
+        const int2 e = live ? pool[node] : make_int2(0, 0);
+        if (__ballot(live && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;
+        node = e.x;
+    }
+    const int c_new = c_old + lcp;
+
+    // ---- mark the nodes below the committed prefix that a live lane reaches; lane 0 (the best prefix) also writes its tokens:
+    //      committed ones [c_old, c_new), then the partial suffix [c_new, p_len)
+    int* __restrict__ ids = ids_all + static_cast<size_t>(b) * pool_nodes;
+    const int n_nodes = st.n_nodes;
+    for (int i = lane; i < n_nodes; i += 64) ids[i] = 0;
+    __syncthreads();
+    int* __restrict__ out_c = committed + static_cast<size_t>(b) * pool_nodes;
+    int* __restrict__ out_p = partial + static_cast<size_t>(b) * pool_nodes;
+    {
+        const int stop = lane == 0 ? c_old : c_new;
+        int k = live ? st.p_len : stop, nd = st.p_node;            // k: depth of node nd
+        while (k > stop) {
+            const int2 e = pool[nd];
+            if (k > c_new) ids[nd] = 1;
+            if (lane == 0) {
+                if (k > c_new) out_p[k - 1 - c_new] = e.y;
+                else out_c[k - 1 - c_old] = e.y;
+            }
+            nd = e.x;
+            --k;
+        }
+    }
+    __syncthreads();
+    // ---- new node ids in the old order (node 0 is never marked, so a marked node i gets an id <= i)
+    int kept = 0;
+    for (int i0 = 0; i0 < n_nodes; i0 += 64) {
+        const int i = i0 + lane;
+        const bool m = i < n_nodes && ids[i] != 0;
+        const unsigned long long mask = __ballot(m);
+        if (m) ids[i] = 1 + kept + __popcll(mask & ((1ull << lane) - 1ull));
+        kept += __popcll(mask);
+    }
+    __syncthreads();
+    // ---- move the kept nodes down, in place: a chunk of 64 reads its entries before it stores (the store data depends on them),
+    //      and it stores only at ids <= its own indices.  The parent of a kept node is kept too, or it is the committed prefix (id 0).
+    for (int i0 = 0; i0 < n_nodes; i0 += 64) {
+        const int i = i0 + lane;
+        const int id = i < n_nodes ? ids[i] : 0;
+        int2 e = make_int2(0, 0);
+        if (id) {
+            e = pool[i];
+            e.x = ids[e.x];
+        }
+        if (id) pool[id] = e;
+    }
+    if (live) st.p_node = st.p_len > c_new ? ids[st.p_node] : 0;
+
+    // ---- store the state
+    beam_stream_store(rec, st, lane, width);
+    if (lane == 0) {
+        rec.hdr[BS_N_LIVE] = n_live;
+        rec.hdr[BS_N_NODES] = 1 + kept;
+        rec.hdr[BS_COMMITTED] = c_new;
+        rec.hdr[BS_ENDED] = ended || (chunk_lengths && cl < frames) ? 1 : 0;
+        usage[b] = 1 + kept;
+        committed_counts[b] = lcp;
+        partial_counts[b] = st.p_len - c_new;
+    }
+}
+
+// The live prefixes' uncommitted suffixes, best first: beams(batch, width, ld) padded with 0, scores = -log P (FLT_MAX beyond
+// n_live), beam_lens = suffix length (-1 beyond n_live).  Reads the state only.
+__global__ __launch_bounds__(64) void ctc_beam_stream_finish_kernel(const char* __restrict__ state, int* __restrict__ beams,
+                                                                    float* __restrict__ scores, int* __restrict__ beam_lens, int ld,
+                                                                    int width, int pool_nodes)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BeamStreamRecord rec = beam_stream_record(const_cast<char*>(state), b, width, pool_nodes);
+    if (lane >= width) return;
+    const int n_live = rec.hdr[BS_N_LIVE], c = rec.hdr[BS_COMMITTED];
+    const bool live = lane < n_live;
+    const int n = live ? rec.len[lane] - c : 0;
+    int* out = beams + (static_cast<size_t>(b) * width + lane) * ld;
+    if (live) {
+        int node = rec.node[lane];
+        for (int k = n - 1; k >= 0; --k) {
+            const int2 e = rec.pool[node];
+            if (k < ld) out[k] = e.y;
+            node = e.x;
+        }
+    }
+    for (int k = n; k < ld; ++k) out[k] = 0;
+    scores[static_cast<size_t>(b) * width + lane] = live ? -rec.pscore[lane] : FLT_MAX;
+    beam_lens[static_cast<size_t>(b) * width + lane] = live ? n : -1;
 }
 
 // ---- CTC loss (forward value) -----------------------------------------------------------------------------------------------
@@ -592,6 +840,75 @@ extern "C" int nbasr_ctc_beam_search(const float* log_probs, const int* lengths,
     hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
                        beam_lens, frames, classes, beam_width, blank);
     return launch_status("nbasr_ctc_beam_search");
+}
+
+extern "C" size_t nbasr_ctc_beam_stream_state_bytes(int batch, int beam_width, int pool_nodes)
+{
+    if (batch <= 0 || beam_width <= 0 || beam_width > BEAM_MAX || pool_nodes <= 0) return 0;
+    return static_cast<size_t>(batch) * beam_stream_record_bytes(beam_width, pool_nodes);
+}
+
+extern "C" size_t nbasr_ctc_beam_stream_workspace_bytes(int batch, int frames, int classes, int pool_nodes)
+{
+    if (batch <= 0 || frames < 0 || classes <= 0 || pool_nodes <= 0) return 0;
+    return static_cast<size_t>(batch) * pool_nodes * sizeof(int) + static_cast<size_t>(batch) * frames * classes * sizeof(float);
+}
+
+extern "C" int nbasr_ctc_beam_stream_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && pool_nodes >= 1, NBASR_EINVAL, "nbasr_ctc_beam_stream_init: bad sizes (batch=%d pool_nodes=%d)", batch, pool_nodes);
+    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "nbasr_ctc_beam_stream_init: beam_width=%d (limit %d) unsupported",
+                  beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(state, NBASR_ENULL, "nbasr_ctc_beam_stream_init: NULL pointer");
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_init: state must be 8-byte aligned");
+    hipLaunchKernelGGL(ctc_beam_stream_init_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
+    return launch_status("nbasr_ctc_beam_stream_init");
+}
+
+extern "C" int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+                                          int* committed_counts, int* partial, int* partial_counts, int* usage, int batch, int frames,
+                                          int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && blank >= 0 && blank < classes && cutoff_top_n > 0 && pool_nodes >= 1,
+                  NBASR_EINVAL, "nbasr_ctc_beam_stream_step: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d pool_nodes=%d)",
+                  batch, frames, classes, blank, cutoff_top_n, pool_nodes);
+    NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
+                  "nbasr_ctc_beam_stream_step: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(state && ws && committed && committed_counts && partial && partial_counts && usage && (frames == 0 || log_probs), NBASR_ENULL,
+                  "nbasr_ctc_beam_stream_step: NULL pointer");
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_step: state must be 8-byte aligned");
+    hipStream_t s = as_stream(stream);
+    const float* src = log_probs;
+    if (cutoff_top_n < classes && frames > 0) {
+        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + static_cast<size_t>(batch) * pool_nodes * sizeof(int));
+        const long long n_frames = static_cast<long long>(batch) * frames;
+        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
+                           classes, cutoff_top_n);
+        src = pruned;
+    }
+    hipLaunchKernelGGL(ctc_beam_stream_kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state), static_cast<int*>(ws),
+                       committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank, pool_nodes);
+    return launch_status("nbasr_ctc_beam_stream_step");
+}
+
+extern "C" int nbasr_ctc_beam_stream_finish(const void* state, int* beams, float* scores, int* beam_lens, int ld_beams, int batch,
+                                            int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && ld_beams >= 0 && pool_nodes >= 1, NBASR_EINVAL,
+                  "nbasr_ctc_beam_stream_finish: bad sizes (batch=%d ld_beams=%d pool_nodes=%d)", batch, ld_beams, pool_nodes);
+    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "nbasr_ctc_beam_stream_finish: beam_width=%d (limit %d) unsupported",
+                  beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(state && scores && beam_lens && (ld_beams == 0 || beams), NBASR_ENULL, "nbasr_ctc_beam_stream_finish: NULL pointer");
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_finish: state must be 8-byte aligned");
+    hipLaunchKernelGGL(ctc_beam_stream_finish_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
+                       scores, beam_lens, ld_beams, beam_width, pool_nodes);
+    return launch_status("nbasr_ctc_beam_stream_finish");
 }
 
 extern "C" int nbasr_ctc_loss(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, float* losses,

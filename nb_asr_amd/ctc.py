@@ -63,6 +63,135 @@ def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n
                                beam_width, blank, cutoff_top_n)
 
 
+class BeamSearchStream:
+    """``beam_decode`` fed chunk by chunk, with committed partial results (nbasr_ctc_beam_stream_*; DESIGN.md §9 "Beam decode").
+
+        dec = BeamSearchStream(batch, beam_width=12, blank=0, cutoff_top_n=40, device=dev)
+        committed, partial = dec.push(log_probs_chunk, lengths=None)   # lists of int32 CPU tensors, one per utterance
+        beams, scores, out_len = dec.finish()     # == beam_decode(all frames, total lengths), bit for bit
+
+    ``committed``: the tokens that became final with this chunk -- a prefix of every beam the search can still return, so they
+    never change; the committed tokens of all pushes, concatenated, start every finite-score beam of ``finish()``.  ``partial``:
+    the current best beam's tokens after everything committed so far.  ``lengths`` (B) gives each utterance's frames in this
+    chunk; fewer than the chunk has ends that utterance, and it takes no frames after that.  The token pool of the search keeps only
+    the uncommitted parts of the live beams and grows (keeping its contents) when a push could overflow it: memory depends on how
+    far the beams diverge, not on the length of the stream."""
+
+    def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None):
+        batch, beam_width = int(batch), int(beam_width)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        if not 1 <= beam_width <= 32:
+            raise ValueError(f'beam_width must be in [1, 32] (got {beam_width})')
+        self.batch, self.beam_width, self.blank, self.cutoff_top_n = batch, beam_width, int(blank), int(cutoff_top_n)
+        device = torch.device('cuda' if device is None else device)
+        if device.type != 'cuda':
+            raise ValueError(f'the beam search runs on a HIP device (got {device}); this package has no CPU path')
+        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        self.initial_pool_nodes = int(pool_nodes) if pool_nodes is not None else 1 + beam_width * 4 * 40
+        self.state = None
+        self.reset()
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the search state (live beams and token pool)."""
+        return 0 if self.state is None else self.state.numel() * self.state.element_size()
+
+    def reset(self):
+        """Start a new batch of utterances at the empty prefix (the state keeps its current pool size)."""
+        if self.state is None:
+            self.pool_nodes = self.initial_pool_nodes
+            self.state = torch.empty(self._words(self.pool_nodes), dtype=torch.int64, device=self.device)
+        hip.ctc_beam_stream_init(self.state, self.batch, self.beam_width, self.pool_nodes)
+        self.usage = torch.ones(self.batch, dtype=torch.int64)
+        self.ended = torch.zeros(self.batch, dtype=torch.bool)
+        self.committed = [[] for _ in range(self.batch)]
+        self.partial = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
+        self.frames = 0
+        self.classes = None
+        self.grown = 0
+        self._finished = False
+
+    def _words(self, pool_nodes):
+        return (hip.ctc_beam_stream_state_bytes(self.batch, self.beam_width, pool_nodes) + 7) // 8
+
+    def _grow(self, need):
+        """Enlarge the pool to at least ``need`` nodes: every utterance's record keeps its bytes at the start of its new record."""
+        new_nodes = max(need, 2 * self.pool_nodes)
+        old_rec = self.state.numel() // self.batch
+        new = torch.empty(self._words(new_nodes), dtype=torch.int64, device=self.device)
+        new.view(self.batch, -1)[:, :old_rec].copy_(self.state.view(self.batch, -1))
+        self.state, self.pool_nodes = new, new_nodes
+        self.grown += 1
+
+    def push(self, log_probs, lengths=None):
+        """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``."""
+        if self._finished:
+            raise ValueError('push after finish(): call reset() to start the next utterances')
+        if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.shape[0] != self.batch:
+            raise ValueError(f'expected log-probabilities ({self.batch}, frames, classes), got {tuple(getattr(log_probs, "shape", ()))}')
+        if log_probs.dtype != torch.float32 or log_probs.device != self.device:
+            raise ValueError(f'log-probabilities must be float32 on {self.device} (got {log_probs.dtype} on {log_probs.device})')
+        n, c = log_probs.shape[1], log_probs.shape[2]
+        if self.classes is not None and c != self.classes:
+            raise ValueError(f'every chunk must have {self.classes} classes (got {c})')
+        if lengths is None:
+            rows = torch.full((self.batch,), n, dtype=torch.int64)
+        else:
+            rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
+            if rows.numel() != self.batch:
+                raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
+            if bool(((rows < 0) | (rows > n)).any()):
+                raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
+        if bool((self.ended & (rows > 0)).any()):
+            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        self.classes = c
+        if n == 0:
+            return [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)], list(self.partial)
+        need = int(self.usage.max()) + self.beam_width * n + 1
+        if need > self.pool_nodes:
+            self._grow(need)
+        chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
+        committed, partial, counts = hip.ctc_beam_stream_step(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width,
+                                                              self.pool_nodes, self.blank, self.cutoff_top_n)
+        counts = counts.cpu()
+        if bool((counts[2] < 0).any()):
+            raise hip.HipError('ctc_beam_stream_step: the token pool was too small for the chunk')
+        self.usage = counts[2].to(torch.int64)
+        n_c, n_p = int(counts[0].max()), int(counts[1].max())
+        host = torch.cat([committed[:, :n_c], partial[:, :n_p]], 1).cpu()
+        new_c = [host[i, : int(counts[0, i])].clone() for i in range(self.batch)]
+        self.partial = [host[i, n_c: n_c + int(counts[1, i])].clone() for i in range(self.batch)]
+        for i in range(self.batch):
+            self.committed[i].append(new_c[i])
+        self.ended |= rows < n
+        self.frames += n
+        return new_c, list(self.partial)
+
+    def finish(self):
+        """End the utterances: ``(beams (B, W, T) int32, scores (B, W), out_len (B, W) int32)`` on the device, ``beam_decode``'s layout
+        over the T frames pushed."""
+        if self._finished:
+            raise ValueError('finish() called twice: call reset() to start the next utterances')
+        self._finished = True
+        ld = max(int(self.usage.max()) - 1, 1)
+        suffix, scores, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld)
+        suffix, lens = suffix.cpu(), lens.cpu()
+        beams = torch.zeros(self.batch, self.beam_width, self.frames, dtype=torch.int32)
+        out_len = torch.zeros(self.batch, self.beam_width, dtype=torch.int32)
+        for i in range(self.batch):
+            head = torch.cat(self.committed[i]) if self.committed[i] else torch.zeros(0, dtype=torch.int32)
+            n_c = head.numel()
+            for r in range(self.beam_width):
+                n_s = int(lens[i, r])
+                if n_s < 0:
+                    continue                                     # no such beam: length 0, padded with 0
+                beams[i, r, :n_c] = head
+                beams[i, r, n_c: n_c + n_s] = suffix[i, r, :n_s]
+                out_len[i, r] = n_c + n_s
+        return beams.to(self.device), scores, out_len.to(self.device)
+
+
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):
     """Per-utterance token error rate, ``torch_edit_distance.compute_wer(hyp, ref, hyp_len, ref_len, blank, sep=[])``
     (trainer.py:245): Levenshtein distance / reference length, after mapping both sides through ``table`` (optional int32

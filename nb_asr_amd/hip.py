@@ -104,6 +104,11 @@ SIGNATURES = {
     'nbasr_ctc_beam_search': (_c_int, [_c_float_p] * 6 + [_c_int] * 6 + [_c_stream]),
     'nbasr_token_error_counts': (_c_int, [_c_float_p, _c_float_p, _c_int, _c_float_p, _c_float_p, _c_int, _c_float_p, _c_int, _c_int,
                                           _c_float_p, _c_int, _c_stream]),
+    'nbasr_ctc_beam_stream_state_bytes': (ctypes.c_size_t, [_c_int] * 3),
+    'nbasr_ctc_beam_stream_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
+    'nbasr_ctc_beam_stream_init': (_c_int, [ctypes.c_void_p] + [_c_int] * 3 + [_c_stream]),
+    'nbasr_ctc_beam_stream_step': (_c_int, [_c_float_p] * 9 + [_c_int] * 7 + [_c_stream]),
+    'nbasr_ctc_beam_stream_finish': (_c_int, [ctypes.c_void_p] + [_c_float_p] * 3 + [_c_int] * 4 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -937,6 +942,59 @@ def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_
     _check(lib.nbasr_ctc_beam_search(log_probs.data_ptr(), None if lengths is None else lengths.data_ptr(), ws.data_ptr(),
                                      beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n,
                                      _stream(log_probs)), 'nbasr_ctc_beam_search')
+    return beams, scores, lens
+
+
+def ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes):
+    """Bytes of the state of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_state_bytes); 0 for bad sizes."""
+    return int(load_library().nbasr_ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes))
+
+
+def _state(state, what='state'):
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or not state.is_contiguous():
+        raise HipError(f'{what} must be a contiguous tensor on a HIP device')
+    return state.data_ptr()
+
+
+def ctc_beam_stream_init(state, batch, beam_width, pool_nodes):
+    """Every utterance of ``state`` (a device tensor of ``ctc_beam_stream_state_bytes`` bytes) to the empty prefix."""
+    if state.numel() * state.element_size() < ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes):
+        raise HipError('ctc_beam_stream_init: state tensor too small (ctc_beam_stream_state_bytes)')
+    _check(load_library().nbasr_ctc_beam_stream_init(_state(state), batch, beam_width, pool_nodes, _stream(state)),
+           'nbasr_ctc_beam_stream_init')
+
+
+def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40):
+    """One chunk of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_step): log_probs (B, n, C) float32, chunk_lengths (B)
+    int32 device tensor or None.  Returns device tensors (committed (B, pool_nodes), partial (B, pool_nodes), counts (3, B) int32 =
+    committed counts, partial counts, pool usage (-1: refused, the pool is too small for this chunk))."""
+    _dev(log_probs, 'log_probs')
+    b, t, c = log_probs.shape
+    dev = log_probs.device
+    if chunk_lengths is not None:
+        _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
+    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes):
+        raise HipError('ctc_beam_stream_step: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
+    lib = load_library()
+    out = torch.empty(2, b, pool_nodes, dtype=torch.int32, device=dev)
+    counts = torch.empty(3, b, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(lib.nbasr_ctc_beam_stream_workspace_bytes(b, t, c, pool_nodes), 8) // 4 + 1, dtype=torch.int32, device=dev)
+    _check(lib.nbasr_ctc_beam_stream_step(log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr(),
+                                          _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(),
+                                          counts[1].data_ptr(), counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes,
+                                          _stream(log_probs)), 'nbasr_ctc_beam_stream_step')
+    return out[0], out[1], counts
+
+
+def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld):
+    """The live prefixes' uncommitted suffixes (nbasr.h: nbasr_ctc_beam_stream_finish): (suffixes (B, W, ld) int32, scores (B, W),
+    suffix lengths (B, W) int32, -1 beyond the live prefixes)."""
+    dev = state.device
+    beams = torch.empty(batch, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
+    scores = torch.empty(batch, beam_width, dtype=torch.float32, device=dev)
+    lens = torch.empty(batch, beam_width, dtype=torch.int32, device=dev)
+    _check(load_library().nbasr_ctc_beam_stream_finish(_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2],
+                                                       batch, beam_width, pool_nodes, _stream(state)), 'nbasr_ctc_beam_stream_finish')
     return beams, scores, lens
 
 

@@ -6,6 +6,9 @@
     tail = sess.flush()                          # the rest, with the full forward's zero right-padding
     # torch.cat([*pushes, tail], 1) == model(torch.cat(chunks, 2))   (to fp32 round-off)
 
+    logits, committed, partial = sess.push(chunk, decode='beam')       # also the prefix beam search of ctc.beam_decode
+    logits, (beams, scores, out_len) = sess.flush(decode='beam')
+
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
 bounded window of future input frames plus the LSTM state.  The model is cut into STAGES -- the four downsample convolutions with their
@@ -190,7 +193,7 @@ class StreamingSession:
     state and packed weights (never a plan of ``model._plans``: plain ``model(x)`` calls in between keep working); every launch goes to
     the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here."""
 
-    def __init__(self, model, batch, max_chunk=160):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40):
         from .ops import PadConvRelu, Linear, Zero
         p0 = model.model[0].conv.weight
         if p0.dtype != torch.float32:
@@ -203,6 +206,8 @@ class StreamingSession:
         if batch < 1 or max_chunk < 1:
             raise ValueError(f'batch and max_chunk must be positive (got {batch}, {max_chunk})')
         self.model, self.batch, self.max_chunk, self.device = model, batch, max_chunk, p0.device
+        self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
+        self._beam = None                         # ctc.BeamSearchStream, made by the first push with decode='beam'
         arch = [[type(n.op).__name__, *(int(type(br).__name__ == 'Identity') for br in n.branch_ops)] for n in model.model[2].nodes]
         names = []
         for (kind, *flags), node in zip(arch, model.model[2].nodes):
@@ -298,8 +303,8 @@ class StreamingSession:
     # ---- public ----------------------------------------------------------------------------------------------------------------
     @property
     def buffer_bytes(self):
-        """Device bytes the session owns (windows, scratch, LSTM state, packed weights)."""
-        return sum(t.numel() * t.element_size() for t in self._bufs)
+        """Device bytes the session owns (windows, scratch, LSTM state, packed weights, and the beam search state once it exists)."""
+        return sum(t.numel() * t.element_size() for t in self._bufs) + (self._beam.state_bytes if self._beam is not None else 0)
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -310,10 +315,15 @@ class StreamingSession:
         self._lstm_started = False
         self._ld_prev = [0] * len(self.specs)     # row pitch of every stage's current window
         self.prev_token.fill_(-1)
+        self._beam_frames = 0                    # logit frames fed to the beam search in this utterance
+        if self._beam is not None:
+            self._beam.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
-        the greedy CTC tokens of those frames (a list of int32 CPU tensors), repeats collapsed across pushes."""
+        the greedy CTC tokens of those frames (a list of int32 CPU tensors), repeats collapsed across pushes.  ``decode='beam'`` returns
+        ``(logits, committed, partial)``: the prefix beam search of ``ctc.beam_decode`` run over the log-probabilities of the final frames
+        (``ctc.BeamSearchStream``): tokens that are now final, and the best beam's tokens after all committed ones."""
         if self._flushed:
             raise ValueError('push after flush: call reset() to start the next utterance')
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or chunk.shape[0] != self.batch or chunk.shape[1] != FEATURES:
@@ -321,6 +331,8 @@ class StreamingSession:
         if chunk.dtype != torch.float32 or chunk.device != self.device:
             raise ValueError(f'the chunk must be float32 on {self.device} (got {chunk.dtype} on {chunk.device})')
         self._check_params()
+        if decode == 'beam':
+            self._beam_ready()
         chunk = chunk.detach().contiguous()
         outs, n = [], chunk.shape[2]
         for off in range(0, n, self.max_chunk):
@@ -328,16 +340,36 @@ class StreamingSession:
         if not outs:
             outs.append(self._step(None, 0, 0, False))
         logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+        if decode == 'beam':
+            return (logits,) + self._beam_push(logits)
         return (logits, self._decode(logits)) if decode else logits
 
     def flush(self, decode=False):
-        """End the utterance: the remaining logits, computed with the full forward's zero right-padding."""
+        """End the utterance: the remaining logits, computed with the full forward's zero right-padding.  ``decode='beam'`` returns
+        ``(logits, (beams, scores, out_len))``: ``ctc.beam_decode`` of the log-probabilities of all the utterance's logits."""
         if self._flushed:
             raise ValueError('flush called twice: call reset() to start the next utterance')
         self._check_params()
+        if decode == 'beam':
+            self._beam_ready()
         logits = self._step(None, 0, 0, True)
         self._flushed = True
+        if decode == 'beam':
+            self._beam_push(logits)
+            return logits, self._beam.finish()
         return (logits, self._decode(logits)) if decode else logits
+
+    def _beam_ready(self):
+        if self._beam_frames != self.frames_out:
+            raise ValueError("decode='beam' must see every logit frame of the utterance: use it from the first push on (or reset())")
+        if self._beam is None:
+            from .ctc import BeamSearchStream
+            self._beam = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device)
+
+    def _beam_push(self, logits):
+        log_probs = hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits
+        self._beam_frames += logits.shape[1]
+        return self._beam.push(log_probs)
 
     def _decode(self, logits):
         tokens, counts = hip.ctc_greedy_stream(logits, self.prev_token)
