@@ -581,6 +581,33 @@ int nbasr_lstm_backward_step(const float* dh_out, const float* w_hh_t, float* dc
 int nbasr_stream_window(const float* hist, int hist_ld, int hist_off, int n_hist, const float* src, int src_ld, int src_off, int n_new,
                         float* dst, int dst_ld, int batch, int channels, float* absmax, nbasr_stream_t stream);
 
+/* ---- front-end of a waveform stream (nb_asr_amd/frontend.py FrontendStream) --------------------------------------------------
+ * The feature front-end above, push by push, as ONE launch: frame t covers samples [t*hop - win/2, t*hop + win/2), negative
+ * indices reflected (i -> -i) and, in the final step only, i >= total_len -> 2 (total_len - 1) - i.  The CALLER decides which
+ * frames a step computes (frontend.py: frames_final / frames_total / retain_from); the step refuses frames whose samples the
+ * stream does not hold.  Built for win = n_fft = 400, hop = 160, bins = 201, n_mels = 80 (anything else: NBASR_EINVAL).
+ *   state: two tails of round_up4(win + 1) floats per utterance (nbasr_frontend_stream_state_bytes), used in turn.
+ *   tail_in(batch, 404): the retained samples [tail_first, tail_first + tail_len) of every utterance (NULL when tail_len == 0);
+ *   wave(batch, n_new) with row pitch ld_wave: this step's samples (NULL when n_new == 0);
+ *   total_len = tail_first + tail_len + n_new: samples of the stream so far (the utterance's length when final != 0).
+ *   feats(batch, n_mels, ld_feats): frames first_frame .. first_frame + n_frames - 1 are written to columns col0 ..; no other
+ *   column is touched (ld_feats % 4 == 0).
+ *   tail_out(batch, 404), != tail_in, 16-byte aligned: receives samples tail_first + tail_out_first_rel .. total_len - 1 (at most
+ *   404; the rest of each row is zeroed).  NULL, or final != 0: nothing is retained (a caller may emit the frames of one push in
+ *   several steps over the same tail_in / wave and retain in the last one).
+ *   dft, fbank: operand images of the windowed DFT matrix and the mel filterbank in the order the lanes of
+ *   v_mfma_f32_16x16x4_f32 read them, 16-byte aligned (rows beyond bins / k beyond bins are zero):
+ *     dft   [13][2][25][64][4] floats: element s of lane l in (tile i, part p, block kb) = M_p[16 i + (l & 15)][16 kb + 4 s + (l >> 4)],
+ *           M_0[f][n] = w[n] cos(2 pi f n / 400), M_1[f][n] = -w[n] sin(2 pi f n / 400), w the periodic Hann window;
+ *     fbank [5][13][64][4] floats, the same map over fbank(80, 208).
+ *   Every feature is one ascending-k fp32 fma chain per GEMM: the same bits whatever the step sizes, col0 or the batch.
+ * n_frames == 0 with nothing to retain is a no-op; final != 0 with total_len <= win / 2 is refused as nbasr_frame_signal refuses it. */
+size_t nbasr_frontend_stream_state_bytes(int batch, int win);
+int nbasr_frontend_stream_step(const float* tail_in, int tail_len, long long tail_first, const float* wave, int n_new, int ld_wave,
+                               float* tail_out, int tail_out_first_rel, const float* dft, const float* fbank, const float* mean,
+                               const float* inv_scale, float* feats, int ld_feats, int col0, int first_frame, int n_frames,
+                               long long total_len, int final, int batch, int win, int hop, int bins, int n_mels, nbasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,30 @@ def windowed_dft_matrix(n_fft, win_length):
     return np.concatenate([np.cos(ang) * window, -np.sin(ang) * window], axis=0)
 
 
+# ---- which frames of a waveform stream are final (pure python; hop <= win / 2) -------------------------------------------------------
+# Frame t covers samples [hop t - win/2, hop t + win/2), negative indices reflected (i -> -i) and, once the length L is known,
+# i >= L -> 2 (L - 1) - i; an utterance of L > win/2 samples has L // hop + 1 frames.
+def frames_final(samples, hop=160, win=400):
+    """Frames that can no longer change after ``samples`` samples, while the end is unknown: those with hop t + win/2 <= samples.
+    Frame 0 reflects sample win/2 into its left half, so it needs one sample more."""
+    half = win // 2
+    return 0 if samples <= half else (samples - half) // hop + 1
+
+
+def frames_total(samples, hop=160, win=400):
+    """Frames of an utterance of ``samples`` samples (its last frame is never final earlier: a flush emits 1 or 2 frames)."""
+    if samples <= win // 2:
+        raise ValueError(f'reflect padding needs more than {win // 2} samples (the utterance has {samples})')
+    return samples // hop + 1
+
+
+def retain_from(frames_emitted, hop=160, win=400):
+    """First sample a stream must keep once ``frames_emitted`` frames are out.  One more than the next frame's left edge: when the
+    length turns out to be a multiple of hop, the last frame's end reflection reaches back to sample L - win/2 - 1.  With
+    ``frames_emitted = frames_final(L)`` this keeps at most ``win`` samples."""
+    return max(0, hop * frames_emitted - win // 2 - 1)
+
+
 class LogMelFrontend:
     """``frontend(wave, lengths=None) -> (B, n_mels, T)`` float32 on ``wave``'s HIP device, ``T = L // hop + 1``.
 
@@ -81,6 +105,29 @@ class LogMelFrontend:
     def num_frames(self, samples):
         return samples // self.hop_length + 1 if samples > 0 else 0
 
+    def stream(self, batch):
+        """A ``FrontendStream``: this front-end push by push for a lockstep batch of ``batch`` waveform streams."""
+        return FrontendStream(self, batch)
+
+    def stream_images(self):
+        """(dft image, fbank image) of nbasr_frontend_stream_step: the two matrices, rows padded to 208 bins, in the order the lanes of
+        the fp32 MFMA read them (include/nbasr.h).  Built once, shared by every stream of this front-end."""
+        if getattr(self, '_images', None) is None:
+            if (self.win_length, self.n_fft, self.hop_length, self.n_mels) != (400, 400, 160, 80):
+                raise ValueError('the streaming front-end is built for win = n_fft = 400, hop = 160, 80 mel bands')
+            rows = 208
+            dft = self.dft.cpu().numpy()                                         # the float32 values __call__ multiplies by
+            m = np.zeros((2, rows, self.n_fft), dtype=np.float32)
+            m[0, :self.bins], m[1, :self.bins] = dft[:self.bins], dft[self.bins:]
+            # (part, tile, row i, block, s, q) -> [tile][part][block][lane = 16 q + i][s]: element s of lane l holds k = 16 kb + 4 s + (l >> 4)
+            dft_image = m.reshape(2, rows // 16, 16, self.n_fft // 16, 4, 4).transpose(1, 0, 3, 5, 2, 4)
+            fb = np.zeros((self.n_mels, rows), dtype=np.float32)
+            fb[:, :self.bins] = self.fbank.cpu().numpy()[:, :self.bins]
+            fb_image = fb.reshape(self.n_mels // 16, 16, rows // 16, 4, 4).transpose(0, 2, 4, 1, 3)
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).reshape(-1).to(self.device)
+            self._images = (dev(dft_image), dev(fb_image))
+        return self._images
+
     def __call__(self, wave, lengths=None):
         if wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
             raise hip.HipError('wave must be a (batch, samples) float32 tensor on a HIP device; this package has no CPU path')
@@ -104,3 +151,121 @@ class LogMelFrontend:
         hip.pointwise_linear(power, t, self.fbank, self.zero_bias, mel)
         hip.log_normalize(mel, lengths, self.mean, self.inv_scale, mel, samples, self.hop_length)
         return mel[:, :, :t] if ld != t else mel
+
+
+class FrontendStream:
+    """``LogMelFrontend`` push by push (``LogMelFrontend.stream``): one fused HIP launch per push, state carried in two sample tails.
+
+        fs = frontend.stream(batch=B)
+        for chunk in waveform_chunks:              # (B, n) float32 on the device, any n >= 0
+            feats = fs.push(chunk)                 # (B, 80, m): the frames that are final now (frames_final)
+        last = fs.flush()                          # (B, 80, 1 or 2): the frames that needed the utterance's end
+        # torch.cat([*pushes, last], 2) has the L // 160 + 1 frames of frontend(whole waveform); the bits do not depend on the chunking
+
+    ``out=(tensor, col0)``: write the frames into columns ``col0`` .. of a caller's contiguous (B, 80, ld) float32 tensor (ld % 4 == 0)
+    and return that view.  The batch is lockstep: every lane receives the same number of samples.  Apart from returned features all
+    memory is allocated here (``state_bytes``: the two tails of 404 samples per lane; the matrices belong to the front-end)."""
+
+    def __init__(self, frontend, batch):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        self.frontend, self.batch, self.device = frontend, batch, frontend.device
+        self.hop, self.win = frontend.hop_length, frontend.n_fft
+        self.lookahead_samples = self.win // 2
+        self._dft_image, self._fbank_image = frontend.stream_images()
+        self._tails = torch.zeros(2, batch, hip.round_up4(self.win + 1), device=self.device)
+        self.state_bytes = self._tails.numel() * self._tails.element_size()
+        assert self.state_bytes == hip.frontend_stream_state_bytes(batch, self.win)
+        self.reset()
+
+    def reset(self):
+        """Start the next batch of utterances; the tails are re-used."""
+        self.samples_in = 0
+        self.frames_out = 0
+        self._tail_first = 0
+        self._tail_len = 0
+        self._turn = 0
+        self._flushed = False
+
+    # ---- public ----------------------------------------------------------------------------------------------------------------
+    def push(self, wave_chunk, out=None):
+        """Feed (batch, n) samples; returns the (batch, 80, m) frames that became final, m = frames_final(samples_in) - frames_out."""
+        wave = self._admit(wave_chunk)
+        m = frames_final(self.samples_in + wave.shape[1], self.hop, self.win) - self.frames_out
+        feats, col0, view = self._destination(out, m)
+        self._step(wave, m, feats, col0, self.frames_out, True, False)
+        return view
+
+    def push_tiled(self, wave_chunk, out, max_frames):
+        """``push`` for a caller that consumes at most ``max_frames`` frames at a time from one buffer: a generator that writes the next
+        frames to columns 0 .. of ``out`` and yields their count (once, with 0, when the push completes no frame).  Drain it: the stream
+        advances with the last launch."""
+        wave = self._admit(wave_chunk)
+        m = frames_final(self.samples_in + wave.shape[1], self.hop, self.win) - self.frames_out
+        first = self.frames_out
+        for off in range(0, max(m, 1), max_frames):
+            k = min(max_frames, m - off)
+            feats, col0, _ = self._destination((out, 0), k)
+            self._step(wave, k, feats, col0, first + off, off + k == m, False)
+            yield k
+
+    def flush(self, out=None):
+        """End the utterance: its last 1 or 2 frames, with the end's reflect padding."""
+        if self._flushed:
+            raise ValueError('flush called twice: call reset() to start the next utterance')
+        m = frames_total(self.samples_in, self.hop, self.win) - self.frames_out
+        feats, col0, view = self._destination(out, m)
+        self._step(None, m, feats, col0, self.frames_out, True, True)
+        self._flushed = True
+        return view
+
+    # ---- one launch ------------------------------------------------------------------------------------------------------------
+    def _admit(self, wave):
+        if self._flushed:
+            raise ValueError('push after flush: call reset() to start the next utterance')
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.batch:
+            raise ValueError(f'expected a ({self.batch}, samples) chunk, got {tuple(getattr(wave, "shape", ()))}')
+        if wave.dtype != torch.float32 or wave.device != self.device:
+            raise ValueError(f'the chunk must be float32 on {self.device} (got {wave.dtype} on {wave.device})')
+        wave = wave.detach()
+        if wave.shape[1] and (wave.stride(1) != 1 or (self.batch > 1 and wave.stride(0) < wave.shape[1])):
+            wave = wave.contiguous()
+        return wave
+
+    def _destination(self, out, m):
+        """(tensor the launch writes, first column, the view of the m frames)."""
+        fe = self.frontend
+        if out is None:
+            buf = torch.empty(self.batch, fe.n_mels, hip.round_up4(m), device=self.device)
+            return buf, 0, (buf[:, :, :m] if buf.shape[2] != m else buf)
+        buf, col0 = out
+        col0 = int(col0)
+        if (not isinstance(buf, torch.Tensor) or buf.dim() != 3 or buf.shape[0] != self.batch or buf.shape[1] != fe.n_mels or buf.shape[2] % 4
+                or buf.dtype != torch.float32 or buf.device != self.device or not buf.is_contiguous()):
+            raise ValueError(f'out must be a contiguous float32 ({self.batch}, {fe.n_mels}, ld) tensor on {self.device}, ld a multiple of 4')
+        if col0 < 0 or col0 + m > buf.shape[2]:
+            raise ValueError(f'out holds {buf.shape[2]} columns: {m} frames do not fit at column {col0}')
+        return buf, col0, buf[:, :, col0:col0 + m]
+
+    def _step(self, wave, m, feats, col0, first, commit, final):
+        """Frames first .. first + m - 1 from the tail and ``wave``; ``commit``: the push / flush ends with this launch (retain, advance)."""
+        fe = self.frontend
+        n = 0 if wave is None else wave.shape[1]
+        tail_in, tail_out, rel = self._tails[self._turn], None, 0
+        new_first = self._tail_first
+        if commit and not final:
+            new_first = retain_from(first + m, self.hop, self.win)
+            rel = new_first - self._tail_first
+            if n:                                            # (an empty push leaves the tail where it is: nothing to copy)
+                tail_out = self._tails[self._turn ^ 1]
+        if m or tail_out is not None:
+            hip.frontend_stream_step(tail_in, self._tail_len, self._tail_first, wave if n else None, tail_out, rel, self._dft_image,
+                                     self._fbank_image, fe.mean, fe.inv_scale, feats, col0, first, m, final, self.win, self.hop, fe.bins)
+        if commit:
+            self.samples_in += n
+            self.frames_out = first + m
+            if tail_out is not None:
+                self._turn ^= 1
+                self._tail_first = new_first
+                self._tail_len = self.samples_in - new_first

@@ -115,6 +115,9 @@ SIGNATURES = {
     'nbasr_frame_signal': (_c_int, [_c_float_p, ctypes.c_void_p, _c_float_p] + [_c_int] * 6 + [_c_stream]),
     'nbasr_power_spectrum': (_c_int, [_c_float_p] * 2 + [_c_int] * 4 + [_c_stream]),
     'nbasr_log_normalize': (_c_int, [_c_float_p, ctypes.c_void_p] + [_c_float_p] * 3 + [_c_int] * 5 + [_c_stream]),
+    'nbasr_frontend_stream_state_bytes': (ctypes.c_size_t, [_c_int] * 2),
+    'nbasr_frontend_stream_step': (_c_int, [_c_float_p, _c_int, ctypes.c_longlong, _c_float_p, _c_int, _c_int, _c_float_p, _c_int] + [_c_float_p] * 5
+                                   + [_c_int] * 4 + [ctypes.c_longlong] + [_c_int] * 6 + [_c_stream]),
     # backward building blocks
     'nbasr_grouped_conv1d_backward_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
     'nbasr_grouped_conv1d_backward': (_c_int, [_c_float_p] * 8 + [_c_int] * 7 + [_c_stream]),
@@ -842,6 +845,43 @@ def log_normalize(mel, lengths, mean, inv_scale, feats, samples, hop):
     _check(load_library().nbasr_log_normalize(_dev(mel, 'mel'), _lengths_ptr(lengths, b), _dev(mean, 'mean'),
                                               _dev(inv_scale, 'inv_scale'), _dev(feats, 'feats'), b, samples, hop, n_mels, ld,
                                               _stream(mel)), 'nbasr_log_normalize')
+    return feats
+
+
+def frontend_stream_state_bytes(batch, win):
+    """Bytes of the two sample tails of a front-end stream (nbasr.h: nbasr_frontend_stream_state_bytes); 0 for bad sizes."""
+    return int(load_library().nbasr_frontend_stream_state_bytes(batch, win))
+
+
+def frontend_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out_first_rel, dft_image, fbank_image, mean, inv_scale, feats,
+                         col0, first_frame, n_frames, final, win, hop, bins):
+    """One step of a front-end stream (nbasr.h: nbasr_frontend_stream_step).  ``tail_in`` / ``tail_out``: (B, round_up4(win + 1)) float32
+    tails (``tail_out`` None: retain nothing); ``wave`` (B, n) float32 or None; ``feats`` (B, n_mels, ld) receives frames ``first_frame`` ..
+    at columns ``col0`` .. (None when ``n_frames`` is 0).  Returns ``feats``."""
+    b, tail_ld = tail_in.shape
+    if tail_ld != round_up4(win + 1) or (tail_out is not None and tuple(tail_out.shape) != (b, tail_ld)):
+        raise HipError(f'frontend_stream_step: the tails must be ({b}, {round_up4(win + 1)}) tensors')
+    n_new = 0
+    if wave is not None:
+        if wave.dim() != 2 or wave.shape[0] != b or wave.device != tail_in.device:
+            raise HipError(f'frontend_stream_step: wave must be a ({b}, samples) tensor on {tail_in.device}')
+        n_new = wave.shape[1]
+        if n_new and (wave.stride(1) != 1 or (b > 1 and wave.stride(0) < n_new)):
+            raise HipError('frontend_stream_step: the samples of an utterance must be contiguous, the utterances must not overlap')
+    ld_wave = wave.stride(0) if n_new else 0
+    if n_new and wave.dtype != torch.float32:
+        raise HipError(f'wave must be float32 (got {wave.dtype})')
+    n_mels = mean.numel()
+    ld_feats = 0
+    if n_frames:
+        if feats.dim() != 3 or feats.shape[0] != b or feats.shape[1] != n_mels or feats.device != tail_in.device:
+            raise HipError(f'frontend_stream_step: feats must be a ({b}, {n_mels}, ld) tensor on {tail_in.device}')
+        ld_feats = feats.shape[2]
+    _check(load_library().nbasr_frontend_stream_step(
+        _dev(tail_in, 'tail_in'), int(tail_len), int(tail_first), wave.data_ptr() if n_new else None, n_new, max(ld_wave, n_new),
+        _opt(tail_out, 'tail_out'), int(tail_out_first_rel), _dev(dft_image, 'dft_image'), _dev(fbank_image, 'fbank_image'), _dev(mean, 'mean'),
+        _dev(inv_scale, 'inv_scale'), _dev(feats, 'feats') if n_frames else None, ld_feats, int(col0), int(first_frame), int(n_frames),
+        int(tail_first) + int(tail_len) + n_new, int(bool(final)), b, win, hop, bins, n_mels, _stream(tail_in)), 'nbasr_frontend_stream_step')
     return feats
 
 

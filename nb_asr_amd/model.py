@@ -271,13 +271,15 @@ class ASRModel(nn.Module):
         finally:
             self._plans.release(plan)
 
-    def stream(self, batch, max_chunk=160, beam_width=12, cutoff_top_n=40):
+    def stream(self, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None):
         """A ``streaming.StreamingSession``: this model's forward chunk by chunk with carried state, for a lockstep batch of ``batch``
         utterances and pushes of up to ``max_chunk`` input frames (larger ones are split).  ``sess.push(chunk)`` returns the logit frames
         that have become final, ``sess.flush()`` the rest; together they are ``model(x)`` of the concatenated chunks (to fp32 round-off).
-        ``push(chunk, decode='beam')`` also runs ``ctc.beam_decode``'s search with ``beam_width`` and ``cutoff_top_n`` as the frames arrive."""
+        ``push(chunk, decode='beam')`` also runs ``ctc.beam_decode``'s search with ``beam_width`` and ``cutoff_top_n`` as the frames arrive.
+        ``frontend``: a ``frontend.LogMelFrontend`` on the model's device; the session then also takes the waveform,
+        ``sess.push_audio(wave_chunk)`` with (batch, n) float32 samples, and ``flush`` ends the front-end's stream first."""
         from .streaming import StreamingSession
-        return StreamingSession(self, batch, max_chunk, beam_width, cutoff_top_n)
+        return StreamingSession(self, batch, max_chunk, beam_width, cutoff_top_n, frontend)
 
     def check(self):
         """Wait for the forwards enqueued so far and raise ``hip.HipError`` if one of them ran the LSTM recurrence as one resident launch

@@ -9,6 +9,9 @@
     logits, committed, partial = sess.push(chunk, decode='beam')       # also the prefix beam search of ctc.beam_decode
     logits, (beams, scores, out_len) = sess.flush(decode='beam')
 
+    sess = model.eval().stream(batch=B, frontend=fe)                   # fe: frontend.LogMelFrontend on the model's device
+    logits = sess.push_audio(wave_chunk)         # (B, n) float32 samples: the front-end's stream (frontend.FrontendStream), then push
+
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
 bounded window of future input frames plus the LSTM state.  The model is cut into STAGES -- the four downsample convolutions with their
@@ -193,8 +196,11 @@ class StreamingSession:
     state and packed weights (never a plan of ``model._plans``: plain ``model(x)`` calls in between keep working); every launch goes to
     the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None):
         from .ops import PadConvRelu, Linear, Zero
+        from .frontend import LogMelFrontend
+        if frontend is not None and not isinstance(frontend, LogMelFrontend):
+            raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
         p0 = model.model[0].conv.weight
         if p0.dtype != torch.float32:
             raise ValueError(f'streaming runs float32 models only (this one is {p0.dtype})')
@@ -262,6 +268,17 @@ class StreamingSession:
             self.c_state = buf(B * LSTM_HIDDEN)
             self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
         self.prev_token = buf(B, torch.int32)[:B]
+        # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
+        self._frontend, self.lookahead_samples = None, None
+        if frontend is not None:
+            if frontend.device != dev:
+                raise ValueError(f'the front-end lives on {frontend.device}, the model on {dev}')
+            if frontend.n_mels != FEATURES:
+                raise ValueError(f'the model reads {FEATURES} features per frame, the front-end makes {frontend.n_mels}')
+            self._frontend = frontend.stream(B)
+            ld = hip.round_up4(max_chunk)
+            self._staging = buf(B * FEATURES * ld).view(B, FEATURES, ld)
+            self.lookahead_samples = self._frontend.lookahead_samples + frontend.hop_length * self.lookahead_frames
         self._pack()
         self.reset()
 
@@ -303,8 +320,10 @@ class StreamingSession:
     # ---- public ----------------------------------------------------------------------------------------------------------------
     @property
     def buffer_bytes(self):
-        """Device bytes the session owns (windows, scratch, LSTM state, packed weights, and the beam search state once it exists)."""
-        return sum(t.numel() * t.element_size() for t in self._bufs) + (self._beam.state_bytes if self._beam is not None else 0)
+        """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, and with a
+        front-end its sample tails and the staging buffer)."""
+        return (sum(t.numel() * t.element_size() for t in self._bufs) + (self._beam.state_bytes if self._beam is not None else 0)
+                + (self._frontend.state_bytes if self._frontend is not None else 0))
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -318,6 +337,9 @@ class StreamingSession:
         self._beam_frames = 0                    # logit frames fed to the beam search in this utterance
         if self._beam is not None:
             self._beam.reset()
+        self._fed = None                         # 'features' (push) or 'audio' (push_audio): one utterance takes one of them
+        if self._frontend is not None:
+            self._frontend.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
@@ -330,19 +352,47 @@ class StreamingSession:
             raise ValueError(f'expected a ({self.batch}, {FEATURES}, frames) chunk, got {tuple(getattr(chunk, "shape", ()))}')
         if chunk.dtype != torch.float32 or chunk.device != self.device:
             raise ValueError(f'the chunk must be float32 on {self.device} (got {chunk.dtype} on {chunk.device})')
+        if self._fed == 'audio':
+            raise ValueError('push after push_audio: an utterance is fed features or samples, not both (reset() starts the next one)')
         self._check_params()
         if decode == 'beam':
             self._beam_ready()
+        self._fed = 'features'
         chunk = chunk.detach().contiguous()
         outs, n = [], chunk.shape[2]
         for off in range(0, n, self.max_chunk):
             outs.append(self._step(chunk, off, min(self.max_chunk, n - off), False))
         if not outs:
             outs.append(self._step(None, 0, 0, False))
+        return self._pushed(outs, decode)
+
+    def _pushed(self, outs, decode):
         logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
         if decode == 'beam':
             return (logits,) + self._beam_push(logits)
         return (logits, self._decode(logits)) if decode else logits
+
+    def push_audio(self, wave_chunk, decode=False):
+        """Feed (batch, n) float32 samples of the waveform (a session made with ``frontend=``): the front-end's stream turns them into the
+        frames that are final now (``frontend.FrontendStream``, one launch per ``max_chunk`` frames, written to the session's staging
+        buffer), and those go the way of ``push`` -- same steps, same results, same ``decode`` forms as pushing them as features."""
+        if self._frontend is None:
+            raise ValueError('push_audio needs a front-end: model.stream(..., frontend=LogMelFrontend(...))')
+        if self._flushed:
+            raise ValueError('push after flush: call reset() to start the next utterance')
+        if self._fed == 'features':
+            raise ValueError('push_audio after push: an utterance is fed features or samples, not both (reset() starts the next one)')
+        if (not isinstance(wave_chunk, torch.Tensor) or wave_chunk.dim() != 2 or wave_chunk.shape[0] != self.batch
+                or wave_chunk.dtype != torch.float32 or wave_chunk.device != self.device):
+            raise ValueError(f'expected a ({self.batch}, samples) float32 chunk on {self.device}, got {tuple(getattr(wave_chunk, "shape", ()))} '
+                             f'{getattr(wave_chunk, "dtype", None)} on {getattr(wave_chunk, "device", None)}')
+        self._check_params()
+        if decode == 'beam':
+            self._beam_ready()
+        self._fed = 'audio'
+        outs = [self._step(self._staging if k else None, 0, k, False)
+                for k in self._frontend.push_tiled(wave_chunk, self._staging, self.max_chunk)]
+        return self._pushed(outs, decode)
 
     def flush(self, decode=False):
         """End the utterance: the remaining logits, computed with the full forward's zero right-padding.  ``decode='beam'`` returns
@@ -352,7 +402,13 @@ class StreamingSession:
         self._check_params()
         if decode == 'beam':
             self._beam_ready()
+        last = []
+        if self._fed == 'audio':                 # the front-end's last 1 or 2 frames first, as a push of features
+            m = self._frontend.flush(out=(self._staging, 0)).shape[2]
+            last = [self._step(self._staging, off, min(self.max_chunk, m - off), False) for off in range(0, m, self.max_chunk)]
         logits = self._step(None, 0, 0, True)
+        if last:
+            logits = torch.cat(last + [logits], 1)
         self._flushed = True
         if decode == 'beam':
             self._beam_push(logits)
