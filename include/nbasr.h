@@ -608,6 +608,49 @@ int nbasr_frontend_stream_step(const float* tail_in, int tail_len, long long tai
                                const float* inv_scale, float* feats, int ld_feats, int col0, int first_frame, int n_frames,
                                long long total_len, int final, int batch, int win, int hop, int bins, int n_mels, nbasr_stream_t stream);
 
+/* ---- optimisation step (reference training/torch/trainer.py:221-225 Trainer.step and :84 Trainer.train) ----------
+ * The rest of the reference's training step after loss.backward(), over a whole parameter set in three launches (reduce, finalise,
+ * apply), stream-ordered, without host synchronisation, read-back or floating-point atomics:
+ *   regulariser   0.01 * sum(torch.norm(conv.weight)): tensors flagged NBASR_OPTIM_WEIGHT_NORM take the gradient g + c_t w,
+ *                 c_t = weight_norm_coef / ||w_t||_2 (0 where ||w_t|| = 0, torch.norm's backward);
+ *   clipping      total_norm = the 2-norm of all effective gradients (sums in float64, fixed order), written to *total_norm;
+ *                 scale = min(1, max_norm / (total_norm + 1e-6)) (clip_grad_norm_); max_norm <= 0: no clipping;
+ *   Adam          gh = (g + c_t w) scale;  m <- m + (1 - beta1)(gh - m);  v <- v beta2 + (1 - beta2) gh gh;
+ *                 p <- p - step_size m / (sqrt(v) / bc2_sqrt + eps)   (torch's single-tensor Adam; no weight decay / amsgrad / maximize).
+ * grad is only read.  Everything is float32 and dense.
+ *
+ * table (device memory, 8-byte aligned, nbasr_optim_table_bytes): n_tensors nbasr_optim_tensor rows, then n_chunks
+ * nbasr_optim_chunk entries.  The CALLER fills it (host side, copied to the device before the step): the chunks of tensor t are
+ * entries first_chunk .. first_chunk + n_chunks - 1, cover [0, count) exactly once in ascending order, every offset a multiple
+ * of 4 elements and every length >= 1; a tensor has at least one chunk (count >= 1).  One workgroup handles one chunk: 16 384
+ * elements per chunk is what nb_asr_amd/optim.py uses.  step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) are
+ * per tensor (t = that tensor's own step count, this step included), computed by the caller in double.
+ * Rows whose four pointers are all 16-byte aligned take 128-bit loads and stores; any other alignment of 4 works.
+ * workspace (device memory, 8-byte aligned, nbasr_optim_workspace_bytes): per-chunk partial sums, c_t, scale; no initialisation. */
+#define NBASR_OPTIM_WEIGHT_NORM 1
+typedef struct {
+    float* p;                /* parameter, updated in place */
+    const float* grad;       /* its gradient */
+    float* exp_avg;          /* Adam's first moment, updated in place */
+    float* exp_avg_sq;       /* Adam's second moment, updated in place */
+    long long count;         /* elements */
+    int flags;               /* NBASR_OPTIM_WEIGHT_NORM or 0 */
+    int first_chunk;
+    int n_chunks;
+    float step_size;
+    float bc2_sqrt;
+    int reserved;
+} nbasr_optim_tensor;        /* 64 bytes */
+typedef struct {
+    int tensor;              /* row of the tensor this chunk belongs to */
+    int length;              /* elements, >= 1 */
+    long long offset;        /* first element, a multiple of 4 */
+} nbasr_optim_chunk;         /* 16 bytes */
+size_t nbasr_optim_table_bytes(int n_tensors, int n_chunks);
+size_t nbasr_optim_workspace_bytes(int n_tensors, int n_chunks);
+int nbasr_optim_adam_step(const void* table, int n_tensors, int n_chunks, void* workspace, float* total_norm, double beta1, double beta2,
+                          double eps, double max_norm, double weight_norm_coef, nbasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,10 @@ SIGNATURES = {
     'nbasr_frontend_stream_state_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_frontend_stream_step': (_c_int, [_c_float_p, _c_int, ctypes.c_longlong, _c_float_p, _c_int, _c_int, _c_float_p, _c_int] + [_c_float_p] * 5
                                    + [_c_int] * 4 + [ctypes.c_longlong] + [_c_int] * 6 + [_c_stream]),
+    # optimisation step
+    'nbasr_optim_table_bytes': (ctypes.c_size_t, [_c_int] * 2),
+    'nbasr_optim_workspace_bytes': (ctypes.c_size_t, [_c_int] * 2),
+    'nbasr_optim_adam_step': (_c_int, [ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_float_p] + [ctypes.c_double] * 5 + [_c_stream]),
     # backward building blocks
     'nbasr_grouped_conv1d_backward_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
     'nbasr_grouped_conv1d_backward': (_c_int, [_c_float_p] * 8 + [_c_int] * 7 + [_c_stream]),
