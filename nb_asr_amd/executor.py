@@ -1,4 +1,4 @@
-"""Host-side executor: walks the model's layer list and enqueues the HIP kernels.
+"""Host-side executor: the plan behind the walk over the model's layer list that enqueues the HIP kernels.
 
 Replaces the isinstance-dispatch loop of the reference's ``ASRModel.forward`` (model.py:116-131),
 ``SearchCell.forward`` (model.py:49-59) and ``Node.forward`` (model.py:13-22):
@@ -14,6 +14,11 @@ except the returned logits.  A plan belongs to a DEVICE, not to a (batch, frames
 object: its workspaces only ever grow (a stream of TIMIT batches whose length differs every step re-uses the
 same memory), and the model is passed to every call, so ``torch.nn.DataParallel`` replicas (shallow copies of
 the module that share the plan pool) each run with their own parameters.
+
+This module keeps what outlives a call: ``ForwardPlan`` (workspaces, derived-weight cache, tile choices, the LSTM recurrence, launch
+tapes, captured graphs, the pipelined tail's streams and buffers) and ``PlanPool``.  The launch sequence of ONE forward -- a dispatch
+loop over ``model.model`` with one step per layer kind, shared by the fp32 and the bf16 storage path, and the state that forward
+carries -- is ``walk.py``; ``node_into`` below is the one node launch both of them (and ``Node.forward``, ``streaming``) go through.
 """
 import collections
 import math
@@ -26,15 +31,19 @@ import torch
 from . import hip
 
 
-def node_into(node, inputs, frames, out, ln0=None, stats=None, linear_ctx=None, gc_variant=0):
+def node_into(node, inputs, frames, out, ln0=None, stats=None, linear_ctx=None, gc_variant=0, copies=None):
     """Enqueue one cell node: ``out = op(inputs[-1]) + sum(flagged inputs)`` (left-to-right).
 
     ``ln0`` = (stats, gamma, beta): ``inputs[0]`` (the cell input) is stored un-normalised with a pending LayerNorm that
     the kernel applies while loading -- as the main input when the node is the cell's first, as skip0 when flagged.
     ``stats`` = (stats_out, workspace, eps): a grouped-conv node also emits the LayerNorm statistics of ``out``.
     ``linear_ctx`` = (packed_weights(op), workspace(c_in, ld)) callables of a ForwardPlan: `linear` ops then run on the fp16
-    matrix cores (packed weights, pre-split activations); None = the exact-fp32 MFMA GEMM."""
+    matrix cores (packed weights, pre-split activations); None = the exact-fp32 MFMA GEMM.
+    ``copies``: the ForwardPlan of a forward on bf16 rows.  Its parameters are bfloat16 tensors while the kernels read fp32 weights, so
+    they come from the plan's derived copies: fp32 values, the [group][ci][tap][co] order for a GC_WPERM variant, the one-term bf16
+    operand image of a `linear` op (one bf16 MFMA per product, gemm_pointwise_bf16.hip)."""
     from .ops import PadConvRelu, Linear, Zero, Identity
+    f32 = copies._f32 if copies is not None else torch.Tensor.detach
     if len(inputs) != len(node.branch_ops):
         raise AssertionError('Branch op and input list have different lenghts')
     skips = [src for branch, src in zip(node.branch_ops, inputs) if isinstance(branch, Identity)]
@@ -44,13 +53,17 @@ def node_into(node, inputs, frames, out, ln0=None, stats=None, linear_ctx=None, 
     ln = ln0 if (on_x or on_s0) else None
     if isinstance(op, PadConvRelu):
         # with `stats` the epilogue writes partial statistics to the workspace; the caller merges them (finalize)
-        hip.grouped_conv1d_node(last, op.conv.weight.detach(), op.conv.bias.detach(), skips, out, frames,
+        weight = copies._packed_grouped(op) if copies is not None and gc_variant & hip.GC_WPERM else f32(op.conv.weight)
+        hip.grouped_conv1d_node(last, weight, f32(op.conv.bias), skips, out, frames,
                                 op.groups, op.kernel_size, op.dilation, ln, on_x, on_s0,
                                 stats[1] if stats is not None else None, gc_variant)
     elif isinstance(op, Linear):
         if stats is not None:
             raise ValueError('statistics from the epilogue are only available for grouped-conv nodes')
-        if linear_ctx is not None:
+        if copies is not None:
+            packed, ws = copies._packed_linear_bf16(op.linear.weight), copies._pointwise_bf16_ws(*last.shape)
+            hip.linear_fused_bf16(last, frames, packed, op.linear.out_features, f32(op.linear.bias), skips, out, ws, ln, on_x, on_s0)
+        elif linear_ctx is not None:
             packed, workspace = linear_ctx
             hip.linear_fused_packed(last, frames, packed(op.linear), op.linear.out_features, op.linear.bias.detach(), skips, out,
                                     workspace(last.shape[1], last.shape[2]), ln, on_x, on_s0)
@@ -251,7 +264,6 @@ class ForwardPlan:
         # (round 3: the A/B switches of rounds 1-2 whose alternatives lost everywhere are gone -- NBASR_IMAGE_MODE, NBASR_ROW_TILE,
         # NBASR_LN_MODE, NBASR_EPILOGUE_STATS, NBASR_LSTM_UNPACKED, NBASR_GC_TABLE, NBASR_GC_BF16_VARIANT, NBASR_GC_BF16_MFMA; what is
         # left: NBASR_DENSE_MODE (also read by autograd.py), NBASR_LINEAR_MODE, NBASR_CELL_FUSION, NBASR_GC_F32_VARIANT, NBASR_LSTM_SEQ, NBASR_TAPE, NBASR_CONV_STATS)
-        self._act_image = None
         self.dense_schemes = {}      # block -> scheme used by the last run (read by bench.py)
         self.dense_row_tiles = {}    # block -> rows per workgroup of the image-path GEMM in the last run
         self.dense_frame_tiles = {}  # block -> frames per workgroup (256, or 128 where the measured table says so)
@@ -283,7 +295,6 @@ class ForwardPlan:
         self._seq_last = None        # (event, slot) of the status copy the forward being enqueued has just added
         # statistics of a downsample convolution's output from its own epilogue (round 5); NBASR_CONV_STATS=0: a pass over the output
         self.conv_stats = os.environ.get('NBASR_CONV_STATS', '1') != '0'
-        self._conv_part = None       # partials the dense convolution just enqueued left for the LayerNorm behind it
         self._seq_flags = hip.LSTM_SEQ_INJECT_FAULT if os.environ.get('NBASR_LSTM_SEQ_FAULT') == '1' else 0     # tests: force a timeout
         # fp32 node kernel variant per launch from the measured table (_gc_variant); NBASR_GC_F32_VARIANT=<bits> forces one (0: the
         # default kernel everywhere)
@@ -460,7 +471,7 @@ class ForwardPlan:
         self._bufs.clear()
         self.side_stream = None                     # (streams.py remembers it for the main stream: a plan built again gets the same one)
 
-    def _set_shape(self, batch, frames, use_rnn):
+    def _set_shape(self, batch, frames, use_rnn, dtype=torch.float32):
         from .model import FILTERS, DOWN_STRIDES, LSTM_HIDDEN
         self.batch, self.frames = batch, frames
         t, self.block_frames = frames, []
@@ -484,6 +495,9 @@ class ForwardPlan:
                 .view(batch, self.out_frames, LSTM_HIDDEN)
         else:
             self.h_out = None
+        if dtype == torch.bfloat16:                      # activations stored as bf16 rows, pitched to 8 frames
+            elems = max(batch * c * hip.row_pitch(t, dtype) for c, t in zip(FILTERS, self.block_frames))
+            self.pool16 = [self._buf(f'pool16_{i}', elems, dtype) for i in range(4)]
 
     def _timed(self, kind, meta, launch):
         """Run ``launch()``; when ``self.timer`` is a list, bracket it with HIP events on the current stream
@@ -586,7 +600,11 @@ class ForwardPlan:
     def _packed_linear(self, linear):
         """Packed (fp16 split) copy of an nn.Linear-like weight (c_out, c_in), rebuilt whenever the parameter changes."""
         w = linear.weight if hasattr(linear, 'weight') else linear
-        return self._cached(w, 'pointwise', lambda: hip.pack_pointwise_weights(w.detach()))
+        return self._cached(w, 'pointwise', lambda: hip.pack_pointwise_weights(self._f32(w)))
+
+    def _packed_linear_bf16(self, w):
+        """One-term bf16 operand image of a per-frame linear map's (c_out, c_in) weight (bf16 storage), rebuilt whenever the parameter changes."""
+        return self._cached(w, 'pointwise_bf16', lambda: hip.pack_pointwise_weights_bf16(self._f32(w)))
 
     def _packed_grouped(self, op):
         """[group][ci][tap][co] copy of a grouped conv's weights (what the fused cell's scalar loads read), rebuilt whenever the parameter changes."""
@@ -616,92 +634,13 @@ class ForwardPlan:
         need = hip.load_library().nbasr_pointwise_workspace_bytes(self.batch, c_in, ld)
         return self._buf('pointwise_ws', max(need, 16), torch.uint8)
 
+    def _pointwise_bf16_ws(self, batch, c_in, ld):
+        return self._buf('pointwise_bf16_ws', max(hip.load_library().nbasr_pointwise_bf16_workspace_bytes(batch, c_in, ld), 16), torch.uint8)
+
     def _dense_part(self, c_out, ld_out):
         """Workspace for the statistics partials a dense convolution emits from its epilogue (one row pair per 16 channels)."""
         n = hip.dense_stats_part_floats(self.batch, c_out, ld_out)
         return self._buf('dense_part', n)[:n]
-
-    def _dense(self, layer, act, act_frames, out, ln, absmax=None, blk=None, image=None, want_stats=False):
-        """``absmax``: (B,) device bounds of max|act[b]| when `act` was just written by the LayerNorm kernel, else None.
-        ``image`` = (image, bound): the LayerNorm of `act` was written as the pre-split operand image instead.
-        ``want_stats``: the block LayerNorm behind this convolution is deferred -- the image-path kernel then emits its statistics
-        partials itself (``self._conv_part``; merged in ``_norm``) instead of a statistics pass over the output."""
-        if image is not None:
-            self.dense_schemes[blk] = 'f16x2-image'
-            b, c, ld = act.shape
-            rows, ftile = self._dense_tile(layer, (act_frames + layer.strides - 1) // layer.strides)
-            self.dense_row_tiles[blk], self.dense_frame_tiles[blk] = rows, ftile
-            part = None
-            if want_stats:
-                part = self._conv_part = self._dense_part(layer.conv.out_channels, out.shape[2])
-            return hip.dense_conv1d_fused_packed_f16_img(image[0], image[1], b, c, act_frames, ld,
-                                                         self._packed_weights(layer, 'f16x2', rows), layer.conv.out_channels,
-                                                         layer.kernel_size, layer.conv.bias.detach(), out, layer.strides, rows, part, ftile)
-        if self.dense_mode != 'f32' and layer.kernel_size == 8:
-            scheme = 'f16x2' if self.dense_mode == 'auto' and absmax is not None and ln is None else 'bf16x3'
-            self.dense_schemes[blk] = scheme
-            part = None
-            if want_stats:                             # (the same 16-channel partials as the image path: the statistics do not depend on the route)
-                part = self._conv_part = self._dense_part(layer.conv.out_channels, out.shape[2])
-            return hip.dense_conv1d_fused_packed(act, act_frames, self._packed_weights(layer, scheme), layer.conv.out_channels,
-                                                 layer.kernel_size, layer.conv.bias.detach(), (), out, layer.strides, ln, scheme,
-                                                 absmax if scheme == 'f16x2' else None, part)
-        self.dense_schemes[blk] = 'f32'
-        return hip.dense_conv1d_fused(act, act_frames, layer.conv.weight.detach(), layer.conv.bias.detach(), (), out,
-                                      layer.strides, ln, ln is not None, False)
-
-    @staticmethod
-    def _cheap_consumer(nxt):
-        """Deferral pays only where normalising on load is nearly free: a following cell whose first node is a grouped
-        convolution (or `zero`).  GEMM consumers (the next block's dense conv, a `linear` first node, the LSTM, the head)
-        stage their input through a register pipeline where the extra per-element work costs more than the LayerNorm
-        pass it saves (measured: +2 ms on the dense convs, +1.2 ms on the LSTM projection)."""
-        from .model import SearchCell
-        from .ops import Linear
-        return isinstance(nxt, SearchCell) and not isinstance(nxt.nodes[0].op, Linear)
-
-    def _norm(self, norm, act, act_frames, kind_meta, taps, tap_idx, nxt, out=None, defer=None):
-        """LayerNorm of ``act``: returns the pending descriptor (deferred) or None after normalising in place (or into
-        ``out``).  ``defer``: the caller's decision whether the consumer normalises on load (default: _cheap_consumer)."""
-        if defer is None:
-            defer = self._cheap_consumer(nxt)
-        if not defer or out is not None:
-            dst = act if out is None else out
-            from .ops import PadConvRelu
-            want_range = self.dense_mode == 'auto' and isinstance(nxt, PadConvRelu) and nxt.groups == 1 and nxt.kernel_size == 8
-            if want_range and taps is None and out is None:
-                # the consumer is the fp16-split convolution: write its pre-split operand image instead of the fp32 tensor
-                # (same traffic; the convolution then gathers its tiles by LDS-DMA and does no vector staging)
-                b, c, ld = act.shape
-                image = self._buf('image', max(hip.load_library().nbasr_split_image_bytes(b, c, ld), 16), torch.uint8)
-                self._stat_turn ^= 1
-                stats = self.stats[self._stat_turn][: b * 2 * ld].view(b, 2, ld)
-                bound = self.absmax[:b]
-                self._timed('layernorm', kind_meta, lambda: hip.layernorm_split_image(act, norm.weight.detach(), norm.bias.detach(),
-                                                                                   stats, bound, image, act_frames, norm.eps))
-                self._act_image = (image, bound)
-                self._act_absmax = None
-                return None
-            absmax = self.absmax[: act.shape[0]] if want_range else None
-            self._timed('layernorm', kind_meta, lambda: hip.layernorm_channels(act, norm.weight.detach(), norm.bias.detach(),
-                                                                               dst, act_frames, norm.eps, absmax))
-            self._act_absmax = absmax
-            return None
-        self._stat_turn ^= 1
-        b, _, ld = act.shape
-        stats = self.stats[self._stat_turn][: b * 2 * ld].view(b, 2, ld)
-        conv_part, self._conv_part = self._conv_part, None
-        if conv_part is not None:
-            # the convolution that wrote `act` left per-row-tile partials: merge them (a few rows per utterance) -- no pass over `act`
-            c = act.shape[1]
-            self._timed('stats_finalize', kind_meta, lambda: hip.grouped_stats_finalize(conv_part, stats, c, act_frames, c, norm.eps, hip.DENSE_STATS_UNIT))
-        else:
-            self._timed('channel_stats', kind_meta, lambda: hip.channel_stats(act, stats, act_frames, norm.eps))
-        if taps is not None:                         # parity debugging: materialise a copy, the flow stays deferred
-            copy = torch.empty_like(act)
-            hip.layernorm_channels(act, norm.weight.detach(), norm.bias.detach(), copy, act_frames, norm.eps)
-            taps[tap_idx] = copy[:, :, :act_frames].clone()
-        return (stats, norm.weight.detach(), norm.bias.detach())
 
     def _gc_variant(self, view, node=None, ln0=None, stats=None, n_inputs=0):
         """Kernel variant of the fp32 grouped-conv node op for this launch (speed only: every variant computes the same sums in the
@@ -733,9 +672,10 @@ class ForwardPlan:
             v = self.gc_table.get(head + 'lnx' + tail)
         return v or 0
 
-    def _view(self, idx, channels, frames):
-        ld = hip.round_up4(frames)
-        return self.pool[idx][: self.batch * channels * ld].view(self.batch, channels, ld)
+    def _view(self, idx, channels, frames, dtype=torch.float32):
+        ld = hip.row_pitch(frames, dtype)
+        pool = self.pool16 if dtype == torch.bfloat16 else self.pool
+        return pool[idx][: self.batch * channels * ld].view(self.batch, channels, ld)
 
     # ---- whole-forward HIP graph ------------------------------------------------------------------------------------
     def _signature(self, model):
@@ -912,10 +852,8 @@ class ForwardPlan:
             raise hip.HipError(f'input must be float32 or bfloat16 (got {x.dtype})')
         x = x.detach().contiguous()
         group = self._group_or_none(model, x, taps, pipelined, _capturing, group)
-        if group is not None:
-            body = lambda m, xx, tp, pl, cp: self._run_f32(m, xx, tp, pl, cp, group)          # noqa: E731
-        else:
-            body = self._run_bf16 if x.dtype == torch.bfloat16 else self._run_f32
+        from . import walk
+        body = lambda m, xx, tp, pl, cp: walk.run(self, m, xx, tp, pl, cp, group)          # noqa: E731
         key = None
         if self.tape_mode and taps is None and not _capturing and self.timer is None:
             key = self._tape_key(model, x, pipelined, group)
@@ -975,224 +913,6 @@ class ForwardPlan:
             self._group_handles = []
         return handle
 
-    def _run_f32(self, model, x, taps, pipelined, _capturing, group=None):
-        from .model import SearchCell
-        from .ops import PadConvRelu
-        import torch.nn as nn
-        pipe = bool(pipelined) and model.use_rnn and taps is None and self._tail_on_side_stream(x.shape[0])
-        if not pipe and not _capturing:
-            # the plain path shares the gate / cell / h buffers with pipelined tails that may still be running
-            self.wait_tails()
-        self._set_shape(x.shape[0], x.shape[2], model.use_rnn)
-        act, act_frames, cur = x, self.frames, None      # `cur`: pool index holding `act` (None: caller's x)
-        if self.dense_mode != 'f32' and (x.shape[-1] % 4 or x.data_ptr() % 16):
-            # the packed dense conv fetches aligned 4-frame quads: bring a ragged-length input into the pitched layout
-            cur = 2
-            act = hip.repitch(x, self._view(cur, x.shape[1], self.frames), self.frames)
-        pending = None                                   # (stats, gamma, beta) when `act` still awaits its LayerNorm
-        self._act_absmax = None                          # set by _norm when it wrote `act` together with max|act[b]|
-        self._act_image = None                           # set by _norm when it wrote the LayerNorm of `act` as the conv's image
-        input_range = None
-        if self.dense_mode == 'auto' and act.shape[0] > 0:
-            # the model input is caller data: one small reduction gives the first conv its range AND decides, per utterance
-            # and on the device, whether that range is tame enough for the scaled fp16 scheme (nbasr.h: nbasr_input_range)
-            input_range = hip.input_range(act, act_frames, self._buf('input_range', 4 * act.shape[0])[: 4 * act.shape[0]])
-        pipe_k, tail_ctx = None, None
-        self._stat_turn = 0
-        lin_ctx = (self._packed_linear, self._pointwise_ws) if self.linear_mode == 'f16x2' else None
-        blk = -1
-        logits = None
-        n_layers = len(model.model)
-        for idx, layer in enumerate(model.model):
-            if isinstance(layer, PadConvRelu):
-                blk += 1
-                dst = 0 if cur != 0 else 1
-                t_out = self.block_frames[blk]
-                out = self._view(dst, layer.conv.out_channels, t_out)
-                ln, src, src_frames, amax, blk_now, img = pending, act, act_frames, self._act_absmax, blk, self._act_image
-                meta = (blk, layer.conv.in_channels, layer.conv.out_channels, layer.kernel_size, t_out, 0)
-                # the block LayerNorm behind this convolution is deferred into the next cell's load: its statistics then come out of
-                # the convolution's own epilogue (round 5) instead of a pass over the output
-                nxt1 = model.model[idx + 1] if idx + 1 < n_layers else None
-                nxt2 = model.model[idx + 2] if idx + 2 < n_layers else None
-                # (the finalize kernel merges <= 128 partial rows: wider than 128 x 16 channels falls back to the statistics pass)
-                want_stats = (self.conv_stats and isinstance(nxt1, nn.LayerNorm) and self._cheap_consumer(nxt2) and layer.kernel_size == 8
-                              and -(-layer.conv.out_channels // hip.DENSE_STATS_UNIT) <= 128)
-                self._conv_part = None
-                if input_range is not None and layer.kernel_size == 8 and ln is None and img is None:
-                    rng, input_range = input_range, None
-                    # fp16 split with per-utterance fall-back to bf16x3 (extreme / non-finite input); image path: one split
-                    # pass over the input, then the same DMA-only GEMM as convs 1-3
-                    bi, ci, ldi = src.shape
-                    image = self._buf('input_image', max(hip.load_library().nbasr_split_image_bytes(bi, ci, ldi), 16), torch.uint8)
-                    rows, ftile = self._dense_tile(layer, t_out)
-                    self.dense_row_tiles[blk], self.dense_frame_tiles[blk] = rows, ftile
-                    self.dense_schemes[blk] = 'f16x2' if image is None else 'f16x2-image'
-                    w16 = self._packed_weights(layer, 'f16x2', rows) if image is not None else self._packed_weights(layer, 'f16x2')
-                    part = None
-                    if want_stats:                         # (both legs -- fp16 image, bf16x3 for extreme utterances -- write their utterances' partials)
-                        part = self._conv_part = self._dense_part(layer.conv.out_channels, out.shape[2])
-                    self._timed('dense_conv', meta, lambda: hip.dense_conv1d_first_ranged(
-                        src, src_frames, rng, w16, self._packed_weights(layer, 'bf16x3'),
-                        layer.conv.out_channels, layer.kernel_size, layer.conv.bias.detach(), out, layer.strides, image, rows, part, ftile))
-                else:
-                    input_range = None
-                    self._timed('dense_conv', meta, lambda: self._dense(layer, src, src_frames, out, ln, amax, blk_now, img, want_stats))
-                act, act_frames, cur, pending, self._act_absmax, self._act_image = out, t_out, dst, None, None, None
-                if taps is not None:
-                    taps[idx] = self._tap(act, act_frames)
-            elif isinstance(layer, nn.LayerNorm):
-                if act.dim() != 3 or pending is not None:
-                    raise RuntimeError('LayerNorm in an unexpected position of the layer list')
-                pending = self._norm(layer, act, act_frames, (blk, act.shape[1], act.shape[1], 0, act_frames, 0), taps, idx,
-                                     model.model[idx + 1] if idx + 1 < n_layers else None)
-                if taps is not None and pending is None:
-                    taps[idx] = self._tap(act, act_frames)
-            elif isinstance(layer, SearchCell):
-                free = [i for i in range(4) if i != cur]
-                if len(layer.nodes) > len(free):
-                    raise NotImplementedError(f'cells with {len(layer.nodes)} nodes need a larger buffer pool')
-                nxt = model.model[idx + 1] if idx + 1 < n_layers else None
-                feeds_tail = pipe and isinstance(nxt, (nn.Dropout, nn.LSTM))
-                # the LSTM's input projection pre-splits its operand in a streaming pass that applies a pending LayerNorm while
-                # loading (gemm_pointwise_split.hip), and it runs on the MAIN stream in both modes: the cell in front of it defers
-                # its LayerNorm like a cell in front of a grouped conv does -- no materialised copy of the encoder output
-                after = model.model[idx + 2] if isinstance(nxt, nn.Dropout) and idx + 2 < n_layers else nxt
-                defer = self._cheap_consumer(nxt) or (isinstance(after, nn.LSTM) and self.linear_mode == 'f16x2')
-                # a deferred cell LayerNorm whose producer is a grouped conv gets its statistics from that node's
-                # epilogue (no statistics pass over the tensor)
-                last_op = layer.nodes[-1].op
-                cell_gpp = (hip.grouped_cell_fits(layer.filters, hip.round_up4(act_frames), last_op.groups)
-                            if (self.cell_fusion and len(layer.nodes) == 3
-                                and all(isinstance(n.op, PadConvRelu) and n.op.groups > 1 for n in layer.nodes)) else 0)
-                fused = cell_gpp > 0
-                epilogue_stats = (layer.use_norm and defer
-                                  and isinstance(last_op, PadConvRelu) and last_op.groups > 1)
-                if fused:
-                    mask = 0
-                    for bit, (j, i) in enumerate(((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))):
-                        if type(layer.nodes[j].branch_ops[i]).__name__ == 'Identity':
-                            mask |= 1 << bit
-                    view = self._view(free[2], layer.filters, act_frames)
-                    specs = [(self._packed_grouped(n.op), n.op.conv.bias.detach(), n.op.kernel_size, n.op.dilation) for n in layer.nodes]
-                    n_skips = [sum(type(br).__name__ == 'Identity' for br in n.branch_ops) for n in layer.nodes]
-                    meta = (blk, layer.filters, tuple(sp[2] for sp in specs), tuple(n_skips), act_frames, 0)
-                    src, ln0 = act, pending
-                    if epilogue_stats:
-                        self._stat_turn ^= 1
-                        ld = view.shape[2]
-                        new_stats = self.stats[self._stat_turn][: self.batch * 2 * ld].view(self.batch, 2, ld)
-                    cell_ws = self.stats_ws if epilogue_stats else None
-                    self._timed('grouped_cell', meta, lambda: hip.grouped_cell_fused(src, specs, mask, view, act_frames, last_op.groups, ln0, cell_ws))
-                    outs = [act, None, None, view]
-                if not fused:
-                    outs = [act]
-                for j, (node, dst) in enumerate(zip(layer.nodes, free) if not fused else ()):
-                    n_skips = sum(type(br).__name__ == 'Identity' for br in node.branch_ops)
-                    kind = {'PadConvRelu': 'grouped_conv', 'Linear': 'linear_op', 'Zero': 'skip_sum'}[type(node.op).__name__]
-                    meta = (blk, layer.filters, layer.filters, getattr(node.op, 'kernel_size', 1), act_frames, n_skips)
-                    view = self._view(dst, layer.filters, act_frames)
-                    ln0, st = pending, None
-                    if epilogue_stats and j == len(layer.nodes) - 1:
-                        self._stat_turn ^= 1
-                        ld = view.shape[2]
-                        new_stats = self.stats[self._stat_turn][: self.batch * 2 * ld].view(self.batch, 2, ld)
-                        st = (new_stats, self.stats_ws, layer.norm_layer.eps)
-                    outs.append(self._timed(kind, meta, lambda: node_into(node, outs, act_frames, view, ln0, st, lin_ctx, self._gc_variant(view, node, ln0, st, len(outs)))))
-                act, cur, pending = outs[-1], free[len(layer.nodes) - 1], None
-                if feeds_tail:
-                    pipe_k, _ = self._pipeline_buffers(layer.filters, act_frames, need_enc=False, group=group)
-                if epilogue_stats:
-                    norm = layer.norm_layer
-                    self._timed('stats_finalize', (blk, layer.filters, layer.filters, 0, act_frames, 0),
-                                lambda: hip.grouped_stats_finalize(self.stats_ws, new_stats, layer.filters, act_frames,
-                                                                   last_op.groups, norm.eps, cell_gpp if fused else 4))
-                    pending = (new_stats, norm.weight.detach(), norm.bias.detach())
-                    if taps is not None:
-                        copy = torch.empty_like(act)
-                        hip.layernorm_channels(act, norm.weight.detach(), norm.bias.detach(), copy, act_frames, norm.eps)
-                        taps[idx] = copy[:, :, :act_frames].clone()
-                elif layer.use_norm:
-                    pending = self._norm(layer.norm_layer, act, act_frames, (blk, layer.filters, layer.filters, 0, act_frames, 0),
-                                         taps, idx, nxt, None, defer)
-                if taps is not None and pending is None:
-                    taps[idx] = self._tap(act, act_frames)
-            elif isinstance(layer, nn.Dropout):
-                if taps is not None:                      # identity: eval mode or p == 0 (checked by the model)
-                    taps[idx] = taps[idx - 1]
-            elif isinstance(layer, nn.LSTM):
-                ln, src, src_frames = pending, act, act_frames
-                w_ih, w_hh = layer.weight_ih_l0.detach(), layer.weight_hh_l0.detach()
-                b_ih, b_hh = layer.bias_ih_l0.detach(), layer.bias_hh_l0.detach()
-                gates = self.gates_pipe[pipe_k] if pipe else self.gates_ws
-                if group is not None:
-                    # TAIL GROUP (round 6): this forward's gates become utterances g * batch .. of the group's (frames, n * batch, 4 hidden)
-                    # gate tensor; the last member runs ONE recurrence and ONE head over all of them -- a frame of the recurrence costs
-                    # at 32 utterances what it costs at 8, and no utterance's h depends on the batch it is computed in (bit-identical)
-                    g, n = group
-                    gb = n * self.batch
-                    gates_all = self.gates_group[pipe_k]
-                    packed_ih, ws = self._packed_linear(layer.weight_ih_l0), self._pointwise_ws(src.shape[1], src.shape[2])
-                    self._timed('lstm_projection', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_input_projection_packed(src, src_frames, packed_ih, b_ih, b_hh, gates_all, layer.hidden_size,
-                                                                         ws, ln, batch_total=gb, batch_offset=g * self.batch))
-                    if g < n - 1:
-                        return self._group_member(group, None)
-                    self._to_side_stream()
-                    tail_ctx = torch.cuda.stream(self.side_stream)
-                    tail_ctx.__enter__()
-                    hidden = layer.hidden_size
-                    xcd_ws = self._buf('lstm_xcd_group', hip.lstm_xcd_workspace_bytes(gb, hidden), torch.uint8)
-                    cell_all = self._buf('cell_group', gb * hidden)[: gb * hidden]
-                    h_all = self._buf('h_out_group', gb * act_frames * hidden)[: gb * act_frames * hidden].view(gb, act_frames, hidden)
-                    gview = gates_all[: act_frames * gb * 4 * hidden].view(act_frames, gb, 4 * hidden)
-                    self._timed('lstm', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_recurrence_frames16(gview, self._packed_whh16(layer.weight_hh_l0), cell_all, h_all, xcd_ws))
-                    head = model.model[idx + 1]
-                    logits = self._new_logits((gb, act_frames, head.out_features), torch.float32, True)
-                    hip.linear_head(h_all, head.weight.detach(), head.bias.detach(), logits)
-                    self._tail_enqueued(pipe_k)
-                    tail_ctx.__exit__(None, None, None)
-                    return self._group_member(group, logits)
-                # the input projection is one large GEMM: it stays with the encoder; only the recurrence moves over
-                if self.linear_mode == 'f16x2':
-                    packed_ih, ws = self._packed_linear(layer.weight_ih_l0), self._pointwise_ws(src.shape[1], src.shape[2])
-                    self._timed('lstm_projection', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_input_projection_packed(src, src_frames, packed_ih, b_ih, b_hh, gates,
-                                                                         layer.hidden_size, ws, ln))
-                else:
-                    self._timed('lstm_projection', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_input_projection(src, src_frames, w_ih, b_ih, b_hh, gates, layer.hidden_size, ln))
-                if pipe:                                   # everything from here on runs on the side stream
-                    self._to_side_stream()
-                    tail_ctx = torch.cuda.stream(self.side_stream)
-                    tail_ctx.__enter__()
-                self._timed('lstm', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                            lambda: self._recurrence(gates, layer.weight_hh_l0, layer.hidden_size, pipe, _capturing))
-                act, pending = self.h_out, None            # (batch, frames, hidden)
-                if taps is not None:
-                    taps[idx] = self._tap(act, act_frames)
-            elif isinstance(layer, nn.Linear):
-                logits = self._new_logits((self.batch, act_frames, layer.out_features), torch.float32, tail_ctx is not None)
-                if act is self.__dict__.get('h_out'):
-                    hip.linear_head(act, layer.weight.detach(), layer.bias.detach(), logits)
-                else:
-                    hip.linear_head_bct(act, act_frames, layer.weight.detach(), layer.bias.detach(), logits, pending)
-                act, pending = logits, None
-            else:
-                raise TypeError(f'unsupported layer {type(layer).__name__} in the model list')
-        if tail_ctx is not None:
-            self._tail_enqueued(pipe_k)
-            tail_ctx.__exit__(None, None, None)
-        if idx != n_layers - 1 or logits is None:
-            raise RuntimeError('the model list does not end in the CTC head')
-        if pipelined:
-            return PendingLogits(logits, self.tail_done[pipe_k] if tail_ctx is not None else None)
-        if taps is not None:
-            taps[len(model.model) - 1] = logits.clone()
-        return logits
-
-    # ---- bf16 storage path (BASELINE config 4) ----------------------------------------------------------------------------
     def _f32(self, param):
         """fp32 copy of a (bf16) parameter, rebuilt when it changes: the kernels read weights of the node ops, biases,
         gamma / beta and the LSTM / head matrices as fp32 whatever the storage type of the activations (exact: every bf16
@@ -1200,288 +920,6 @@ class ForwardPlan:
         if param.dtype == torch.float32:
             return param.detach()
         return self._cached(param, 'f32', lambda: param.detach().float().contiguous())
-
-    def _view16(self, idx, channels, frames):
-        ld = hip.row_pitch(frames, torch.bfloat16)
-        return self.pool16[idx][: self.batch * channels * ld].view(self.batch, channels, ld)
-
-    def _run_bf16(self, model, x, taps, pipelined, capturing):
-        """The forward with activations and GEMM operands STORED as bfloat16 (what `model.to(torch.bfloat16)(x.bfloat16())`
-        is in the reference): dense convs as one bf16 MFMA per product on a producer-written operand image, node ops /
-        LayerNorm reading and writing bf16 rows (half the HBM bytes) with fp32 arithmetic and ONE rounding per tensor,
-        LayerNorm statistics, LSTM gates / state and the head in fp32; logits returned as bfloat16."""
-        from .model import SearchCell, FILTERS, LSTM_HIDDEN, LN_EPS
-        from .ops import PadConvRelu, Linear, Zero, Identity
-        import torch.nn as nn
-        bf16 = torch.bfloat16
-        pipe = bool(pipelined) and model.use_rnn and taps is None and self._tail_on_side_stream(x.shape[0])
-        if not pipe and not capturing:
-            self.wait_tails()
-        self._set_shape(x.shape[0], x.shape[2], model.use_rnn)
-        B = self.batch
-        lds = [hip.row_pitch(t, bf16) for t in self.block_frames]
-        elems = max(B * c * ld for c, ld in zip(FILTERS, lds))
-        self.pool16 = [self._buf(f'pool16_{i}', elems, bf16) for i in range(4)]
-        lib = hip.load_library()
-
-        def variant_for(frames):
-            # 8 frames per lane (16-byte accesses) where rows are long; the narrow blocks run better as more, lighter waves
-            # (tools/bench_gc_variants.py on an MI355X: 40 vs 49 us at 1 600 frames, 39 vs 37 us at 400)
-            return (hip.GC_FPL8 | hip.GC_WPERM) if frames >= 512 else hip.GC_WPERM
-
-        def image_of(act, frames, norm=None, stats=None, eps=0.0):
-            b, c, ld = act.shape
-            img = self._buf('image16', max(lib.nbasr_bf16_image_bytes(b, c, ld), 16), torch.uint8)
-            return hip.bf16_image(act, img, frames, norm, stats, eps)
-
-        def grouped_weight(op, variant):
-            w = op.conv.weight
-            if variant & hip.GC_WPERM:
-                return self._cached(w, 'gc_wperm', lambda: hip.pack_grouped_weights(self._f32(w).contiguous(), op.groups))
-            return self._f32(w)
-
-        # model input -> pitched bf16 rows (whole 16-byte chunks)
-        act, act_frames, cur = x, self.frames, None
-        if x.shape[-1] % 8 or x.data_ptr() % 16:
-            cur = 2
-            act = hip.repitch(x, self._view16(cur, x.shape[1], self.frames), self.frames)
-        pending, image = None, None            # deferred LayerNorm of `act` / operand image holding (the LayerNorm of) `act`
-        self._stat_turn = 0
-        pipe_k, tail_ctx, logits = None, None, None
-        blk, n_layers = -1, len(model.model)
-        act_is_f32 = False                     # set once the encoder output has been handed over to the fp32 tail
-        for idx, layer in enumerate(model.model):
-            nxt = model.model[idx + 1] if idx + 1 < n_layers else None
-            if isinstance(layer, PadConvRelu):
-                blk += 1
-                if pending is not None:
-                    raise RuntimeError('a dense convolution cannot take a deferred LayerNorm in the bf16 path')
-                if image is None:
-                    image = image_of(act, act_frames)
-                dst = 0 if cur != 0 else 1
-                t_out = self.block_frames[blk]
-                out = self._view16(dst, layer.conv.out_channels, t_out)
-                rows, ftile = self._bf16_tile(layer.conv.out_channels, t_out, pipe)
-                self.dense_row_tiles[blk], self.dense_frame_tiles[blk] = rows, ftile
-                w = layer.conv.weight
-                packed = self._cached(w, ('bf16', rows, layer.strides),
-                                      lambda: hip.pack_dense_weights_bf16(self._f32(w), layer.strides, rows))
-                bias, src_shape, img_now, frames_now = self._f32(layer.conv.bias), act.shape, image, act_frames
-                self.dense_schemes[blk] = 'bf16'
-                self._timed('dense_conv', (blk, layer.conv.in_channels, layer.conv.out_channels, layer.kernel_size, t_out, 0),
-                            lambda: hip.dense_conv1d_bf16_img(img_now, B, src_shape[1], frames_now, src_shape[2], packed,
-                                                              layer.conv.out_channels, layer.kernel_size, bias, out, layer.strides, rows, ftile))
-                act, act_frames, cur, image = out, t_out, dst, None
-                if taps is not None:
-                    taps[idx] = act[:, :, :act_frames].clone()
-            elif isinstance(layer, (nn.LayerNorm, SearchCell)):
-                if isinstance(layer, SearchCell):
-                    free = [i for i in range(4) if i != cur]
-                    if len(layer.nodes) > len(free):
-                        raise NotImplementedError(f'cells with {len(layer.nodes)} nodes need a larger buffer pool')
-                    last_op = layer.nodes[-1].op
-                    norm = layer.norm_layer if layer.use_norm else None
-                    after_cell = model.model[idx + 2] if isinstance(nxt, nn.Dropout) and idx + 2 < n_layers else nxt
-                    epilogue_stats = (norm is not None and (self._cheap_consumer(nxt) or isinstance(after_cell, nn.LSTM))
-                                      and isinstance(last_op, PadConvRelu) and last_op.groups > 1)
-                    outs = [act]
-                    # three grouped convs: ONE launch where a row fits a workgroup (grouped_cell.hip; x1 and x2 rounded to bf16 exactly
-                    # where the node launches store them, so the result is the same bit for bit)
-                    cell_gpp = (hip.grouped_cell_fits(layer.filters, act.shape[2], last_op.groups)
-                                if (self.cell_fusion and len(layer.nodes) == 3
-                                    and all(isinstance(n.op, PadConvRelu) and n.op.groups > 1 for n in layer.nodes)) else 0)
-                    if cell_gpp:
-                        mask = 0
-                        for bit, (j, i) in enumerate(((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))):
-                            if isinstance(layer.nodes[j].branch_ops[i], Identity):
-                                mask |= 1 << bit
-                        view = self._view16(free[2], layer.filters, act_frames)
-                        specs = [(None, self._f32(n.op.conv.bias), n.op.kernel_size, n.op.dilation) for n in layer.nodes]
-                        n_sk = [sum(isinstance(br, Identity) for br in n.branch_ops) for n in layer.nodes]
-                        meta = (blk, layer.filters, tuple(sp[2] for sp in specs), tuple(n_sk), act_frames, 0)
-                        src, ln0, cell_ws = act, pending, (self.stats_ws if epilogue_stats else None)
-                        if self.cell_mfma and hip.grouped_cell_mfma_fits(layer.filters, act.shape[2], last_op.groups):
-                            # every tensor of the bf16 model is a bfloat16 tensor: the products go to the matrix cores unchanged (grouped_cell_mfma.hip;
-                            # 133 against 281 us for a 32 x 800 x 1600 cell).  That kernel has no statistics by-product: a consumer that
-                            # normalises on load gets them from a read pass over the result (~25 us)
-                            groups, epilogue_stats = last_op.groups, False
-                            mspecs = [(self._cached(n.op.conv.weight, 'cell_mfma', (lambda w=n.op.conv.weight: hip.grouped_cell_mfma_pack(self._f32(w), groups))),
-                                       sp[1], sp[2], sp[3]) for n, sp in zip(layer.nodes, specs)]
-                            self._timed('grouped_cell_mfma', meta, lambda: hip.grouped_cell_mfma(src, mspecs, mask, view, act_frames, groups, ln0))
-                        else:
-                            vspecs = [(self._packed_grouped(n.op), sp[1], sp[2], sp[3]) for n, sp in zip(layer.nodes, specs)]
-                            self._timed('grouped_cell', meta, lambda: hip.grouped_cell_fused(src, vspecs, mask, view, act_frames, last_op.groups, ln0, cell_ws))
-                        outs = [act, None, None, view]
-                    for j, (node, dst) in enumerate(zip(layer.nodes, free) if not cell_gpp else ()):
-                        if len(outs) != len(node.branch_ops):
-                            raise AssertionError('Branch op and input list have different lenghts')
-                        skips = [src for br, src in zip(node.branch_ops, outs) if isinstance(br, Identity)]
-                        n_skips = len(skips)
-                        on_x = pending is not None and len(outs) == 1
-                        on_s0 = pending is not None and isinstance(node.branch_ops[0], Identity)
-                        ln = pending if (on_x or on_s0) else None
-                        view, op, last = self._view16(dst, layer.filters, act_frames), node.op, outs[-1]
-                        meta = (blk, layer.filters, layer.filters, getattr(op, 'kernel_size', 1), act_frames, n_skips)
-                        if isinstance(op, PadConvRelu):
-                            ws = self.stats_ws if (epilogue_stats and j == len(layer.nodes) - 1) else None
-                            variant = variant_for(act_frames)
-                            wt, bs = grouped_weight(op, variant), self._f32(op.conv.bias)
-                            self._timed('grouped_conv', meta, lambda: hip.grouped_conv1d_node(
-                                last, wt, bs, skips, view, act_frames, op.groups, op.kernel_size, op.dilation, ln, on_x, on_s0, ws, variant))
-                        elif isinstance(op, Zero):
-                            self._timed('skip_sum', meta, lambda: hip.skip_sum(skips, view, act_frames, ln if on_s0 else None, on_s0))
-                        elif isinstance(op, Linear):
-                            # round 4: one bf16 MFMA per product on a bf16 operand image (gemm_pointwise_bf16.hip); rounds 2-3 bridged the op
-                            # through the fp32 split GEMM (x -> fp32, two fp16 terms, three MFMAs, y -> bf16, a separate skip sum)
-                            b_, c_, ld_ = last.shape
-                            wl = op.linear.weight
-                            packed = self._cached(wl, 'pointwise_bf16', lambda: hip.pack_pointwise_weights_bf16(self._f32(wl)))
-                            ws16 = self._buf('pointwise_bf16_ws', max(lib.nbasr_pointwise_bf16_workspace_bytes(b_, c_, ld_), 16), torch.uint8)
-                            self._timed('linear_op', meta, lambda: hip.linear_fused_bf16(
-                                last, act_frames, packed, op.linear.out_features, self._f32(op.linear.bias), skips, view, ws16, ln, on_x, on_s0))
-                        else:
-                            raise TypeError(f'unsupported node operation {type(op).__name__}')
-                        outs.append(view)
-                    act, cur, pending = outs[-1], free[len(layer.nodes) - 1], None
-                else:
-                    norm, epilogue_stats, cell_gpp = layer, False, 0
-                    if act.dim() != 3 or pending is not None:
-                        raise RuntimeError('LayerNorm in an unexpected position of the layer list')
-                feeds_tail = isinstance(nxt, (nn.Dropout, nn.LSTM, nn.Linear))
-                after = model.model[idx + 2] if isinstance(nxt, nn.Dropout) and idx + 2 < n_layers else nxt
-                meta = (blk, act.shape[1], act.shape[1], 0, act_frames, 0)
-                if feeds_tail and isinstance(after, nn.LSTM):
-                    # the LSTM's input projection takes the bf16 encoder output itself (round 4: bf16 operand image, one MFMA per
-                    # product) and applies a pending LayerNorm while writing that image: statistics only, no fp32 copy of the tensor
-                    if pipe:
-                        pipe_k, _ = self._pipeline_buffers(act.shape[1], act.shape[2], need_enc=False)
-                    if norm is not None:
-                        g32, b32 = self._f32(norm.weight), self._f32(norm.bias)
-                        self._stat_turn ^= 1
-                        b, c, ld = act.shape
-                        stats = self.stats[self._stat_turn][: b * 2 * ld].view(b, 2, ld)
-                        src = act
-                        if epilogue_stats:
-                            self._timed('stats_finalize', meta, lambda: hip.grouped_stats_finalize(self.stats_ws, stats, c, act_frames,
-                                                                                                 last_op.groups, norm.eps, cell_gpp or 4))
-                        else:
-                            self._timed('channel_stats', meta, lambda: hip.channel_stats(src, stats, act_frames, norm.eps))
-                        pending = (stats, g32, b32)
-                        if taps is not None:                 # parity debugging: materialise a copy, the flow stays deferred
-                            copy = torch.empty_like(act)
-                            hip.layernorm_channels(act, g32, b32, copy, act_frames, norm.eps)
-                            taps[idx] = copy[:, :, :act_frames].clone()
-                    elif taps is not None:
-                        taps[idx] = act[:, :, :act_frames].clone()
-                elif feeds_tail:
-                    # hand-over to the fp32 tail (LSTM projection / head): the last LayerNorm writes fp32
-                    b, c, ld = act.shape
-                    if pipe:
-                        pipe_k, enc = self._pipeline_buffers(c, ld)           # fp32 (B, C, ld) double buffer
-                    else:
-                        enc = self._buf('enc32', b * c * ld)[: b * c * ld].view(b, c, ld)
-                    src = act
-                    if norm is not None:
-                        g32, b32 = self._f32(norm.weight), self._f32(norm.bias)
-                        self._timed('layernorm', meta, lambda: hip.layernorm_channels(src, g32, b32, enc, act_frames, norm.eps))
-                    else:
-                        hip.convert(src, enc)
-                    act, cur, act_is_f32 = enc, None, True
-                    if taps is not None:
-                        taps[idx] = act[:, :, :act_frames].clone()
-                elif norm is None:
-                    if taps is not None:
-                        taps[idx] = act[:, :, :act_frames].clone()
-                else:
-                    g32, b32 = self._f32(norm.weight), self._f32(norm.bias)
-                    self._stat_turn ^= 1
-                    b, c, ld = act.shape
-                    stats = self.stats[self._stat_turn][: b * 2 * ld].view(b, 2, ld)
-                    src = act
-                    if isinstance(nxt, PadConvRelu):
-                        # the consumer is a dense conv: the LayerNorm writes its operand image (statistics on the way)
-                        self._timed('layernorm', meta, lambda: image_of(src, act_frames, (g32, b32), stats, norm.eps))
-                        image = self._bufs['image16']
-                        if taps is not None:
-                            copy = torch.empty_like(act)
-                            hip.layernorm_channels(act, g32, b32, copy, act_frames, norm.eps)
-                            taps[idx] = copy[:, :, :act_frames].clone()
-                    elif self._cheap_consumer(nxt):
-                        if epilogue_stats:
-                            self._timed('stats_finalize', meta, lambda: hip.grouped_stats_finalize(self.stats_ws, stats, c, act_frames,
-                                                                                                 last_op.groups, norm.eps, cell_gpp or 4))
-                        else:
-                            self._timed('channel_stats', meta, lambda: hip.channel_stats(src, stats, act_frames, norm.eps))
-                        pending = (stats, g32, b32)
-                        if taps is not None:
-                            copy = torch.empty_like(act)
-                            hip.layernorm_channels(act, g32, b32, copy, act_frames, norm.eps)
-                            taps[idx] = copy[:, :, :act_frames].clone()
-                    else:
-                        self._timed('layernorm', meta, lambda: hip.layernorm_channels(src, g32, b32, src, act_frames, norm.eps))
-                        if taps is not None:
-                            taps[idx] = act[:, :, :act_frames].clone()
-            elif isinstance(layer, nn.Dropout):
-                if taps is not None:
-                    taps[idx] = taps[idx - 1]
-            elif isinstance(layer, nn.LSTM):
-                src, src_frames = act, act_frames
-                b_ih, b_hh = self._f32(layer.bias_ih_l0), self._f32(layer.bias_hh_l0)
-                gates = self.gates_pipe[pipe_k] if pipe else self.gates_ws
-                w_ih32, w_hh32 = self._f32(layer.weight_ih_l0), self._f32(layer.weight_hh_l0)
-                if act_is_f32:
-                    # (an fp32 hand-over copy of the encoder output, should a caller have made one: the fp16-split GEMM of rounds 2-3)
-                    packed_ih = self._cached(layer.weight_ih_l0, 'pointwise', lambda: hip.pack_pointwise_weights(w_ih32))
-                    ws = self._pointwise_ws(src.shape[1], src.shape[2])
-                    self._timed('lstm_projection', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_input_projection_packed(src, src_frames, packed_ih, b_ih, b_hh, gates, layer.hidden_size, ws, None))
-                else:
-                    packed_ih = self._cached(layer.weight_ih_l0, 'pointwise_bf16', lambda: hip.pack_pointwise_weights_bf16(w_ih32))
-                    ws16 = self._buf('pointwise_bf16_ws', max(lib.nbasr_pointwise_bf16_workspace_bytes(B, src.shape[1], src.shape[2]), 16), torch.uint8)
-                    ln_x, pending = pending, None
-                    self._timed('lstm_projection', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                                lambda: hip.lstm_input_projection_bf16(src, src_frames, packed_ih, b_ih, b_hh, gates, layer.hidden_size, ws16, ln_x))
-                if pipe:
-                    self._to_side_stream()
-                    tail_ctx = torch.cuda.stream(self.side_stream)
-                    tail_ctx.__enter__()
-                self._timed('lstm', (blk, layer.input_size, layer.hidden_size, 0, act_frames, 0),
-                            lambda: self._recurrence(gates, layer.weight_hh_l0, layer.hidden_size, pipe, capturing))
-                act = self.h_out
-                if taps is not None:
-                    taps[idx] = act.permute(0, 2, 1).clone()
-            elif isinstance(layer, nn.Linear):
-                n = B * act_frames * layer.out_features
-                n8 = (n + 7) & ~7
-                logits32 = self._buf('logits32', max(n8, 8))[: max(n8, 8)]      # tails run one after another on the side stream
-                l32 = logits32[:n].view(B, act_frames, layer.out_features)
-                w32, b32 = self._f32(layer.weight), self._f32(layer.bias)
-                if act is self.h_out:
-                    hip.linear_head(act, w32, b32, l32)
-                else:
-                    hip.linear_head_bct(act, act_frames, w32, b32, l32, None)
-                # (the conversion works in 8-element chunks: the last chunk's padding is converted too and never returned)
-                out16 = self._new_logits((B, act_frames, layer.out_features), bf16, tail_ctx is not None, numel=max(n8, 8))
-                hip.convert(logits32, out16)
-                logits = out16[:n].view(B, act_frames, layer.out_features)
-                act = logits
-            else:
-                raise TypeError(f'unsupported layer {type(layer).__name__} in the model list')
-        if tail_ctx is not None:
-            self._tail_enqueued(pipe_k)
-            tail_ctx.__exit__(None, None, None)
-        if logits is None:
-            raise RuntimeError('the model list does not end in the CTC head')
-        if pipelined:
-            return PendingLogits(logits, self.tail_done[pipe_k] if tail_ctx is not None else None)
-        if taps is not None:
-            taps[len(model.model) - 1] = logits.clone()
-        return logits
-
-    def _tap(self, act, frames):
-        if act is self.__dict__.get('h_out'):
-            return act.permute(0, 2, 1).clone()              # (B, H, T) like the oracle's LSTM tap
-        return act[:, :, :frames].clone()
 
 
 class PlanPool:

@@ -153,8 +153,6 @@ class HipError(RuntimeError):
     code = None
 
 
-
-
 _lib = None
 _tls = threading.local()
 

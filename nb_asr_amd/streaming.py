@@ -458,7 +458,7 @@ class StreamingSession:
 
     def _step(self, chunk, off, n, final):
         from .executor import node_into
-        from .ops import PadConvRelu
+        from .walk import fused_cell
         plans = self.planner.step(n, final)
         m, B = self.model.model, self.batch
         self.frames_in += n
@@ -495,13 +495,8 @@ class StreamingSession:
                 out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
                 nodes = cell.nodes
                 groups = getattr(nodes[-1].op, 'groups', 0)
-                fused = (len(nodes) == 3 and all(isinstance(nd.op, PadConvRelu) and nd.op.groups > 1 for nd in nodes)
-                         and hip.grouped_cell_fits(sp.c_out, ld, groups) > 0)
+                fused, mask = fused_cell(cell, ld)
                 if fused:                        # the executor's one-launch cell (bit-identical to the three node launches)
-                    mask = 0
-                    for bit, (j, i) in enumerate(((0, 0), (1, 0), (1, 1), (2, 0), (2, 1), (2, 2))):
-                        if type(nodes[j].branch_ops[i]).__name__ == 'Identity':
-                            mask |= 1 << bit
                     specs = [(self._packed[id(nd.op)], nd.op.conv.bias.detach(), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
                     hip.grouped_cell_fused(win, specs, mask, out, n_w, groups)
                 else:
