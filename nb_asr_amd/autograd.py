@@ -1,6 +1,7 @@
 """The differentiable path: one ``torch.autograd.Function`` per op of the model, forward AND backward through the
 C ABI, and ``model_forward`` which strings them together -- what ``ASRModel.forward`` runs in training mode with gradients enabled,
-so that the reference's ``loss.backward()`` (trainer.py:220-223) reaches every parameter.
+so that the reference's ``loss.backward()`` (trainer.py:220-223) reaches every parameter.  The backward passes that are host algorithms
+(the dense / linear maps, the LSTM's BPTT) live in backward.py; the others are single wrappers of hip.py.
 
 * ``grouped_pad_conv_relu``  reference ``ops.PadConvRelu`` with groups > 1 (ops.py:24-30): vector-ALU dgrad, MFMA wgrad
 * ``dense_pad_conv_relu``    the dense k = 8 downsample convs (model.py:82-89) and the per-frame ``linear`` op (ops.py:42-50)
@@ -14,11 +15,9 @@ the reference modules' own autograd (tests/golden/grad_fixtures.npz, tests/test_
 autograd through the oracle (tests/test_model_gpu.py).  Training-mode dropout (p > 0) is ATen's dropout on each op's output, as the
 reference places it (ops.py:22,29).  The fused inference executor (executor.py) stays the fast path for eval() / torch.no_grad().
 """
-import os
-
 import torch
 
-from . import hip
+from . import backward, hip
 
 
 def _pitched(t):
@@ -74,7 +73,7 @@ class _LayerNormChannels(torch.autograd.Function):
 
 class _DensePadConvRelu(torch.autograd.Function):
     """Dense k = 8 downsample conv (stride 1 | 2) or the per-frame `linear` op (k = 1) with ReLU and clamp; forward of the k = 8 convs on the
-    split 16-bit GEMMs (NBASR_DENSE_MODE = auto (default: two-term fp16 split) | bf16x3 | f32: the exact-fp32 MFMA GEMM), backward through hip.dense_conv1d_backward."""
+    split 16-bit GEMMs (NBASR_DENSE_MODE = auto (default: two-term fp16 split) | bf16x3 | f32: the exact-fp32 MFMA GEMM), backward through backward.dense_conv1d_backward."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, normalized_input=False):
@@ -83,7 +82,7 @@ class _DensePadConvRelu(torch.autograd.Function):
         w3 = weight.detach() if weight.dim() == 3 else weight.detach().unsqueeze(-1)
         t_out = (frames + stride - 1) // stride
         y = torch.empty(xp.shape[0], weight.shape[0], hip.round_up4(t_out), device=xp.device, dtype=xp.dtype)
-        mode = os.environ.get('NBASR_DENSE_MODE', 'auto')
+        mode = hip.dense_mode()
         if kernel == 8 and mode == 'bf16x3' and xp.data_ptr() % 16 == 0:
             # the three-term bf16 split (fp32's range, no range information needed, fp32-level error): half the time of the exact-fp32
             # MFMA GEMM; the weights change every step, so they are packed per call (tens of microseconds)
@@ -114,7 +113,7 @@ class _DensePadConvRelu(torch.autograd.Function):
         frames, stride, t_out, _ = ctx.cfg
         dyp, _ = _pitched(dy)
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        dx, dw, db = hip.dense_conv1d_backward(xp, weight, y, dyp, frames, stride, need_dx, need_dw)
+        dx, dw, db = backward.dense_conv1d_backward(xp, weight, y, dyp, frames, stride, need_dx, need_dw)
         return (dx[:, :, :frames] if dx is not None else None), dw, db, None, None
 
 
@@ -128,7 +127,7 @@ class _LSTM(torch.autograd.Function):
         gates = torch.empty(max(frames, 1), b, 4 * hidden, device=xp.device, dtype=torch.float32)
         cell = torch.empty(b, hidden, device=xp.device, dtype=torch.float32)
         h_out = torch.empty(b, frames, hidden, device=xp.device, dtype=torch.float32)
-        if frames and hidden % 4 == 0 and os.environ.get('NBASR_DENSE_MODE', 'auto') != 'f32':
+        if frames and hidden % 4 == 0 and hip.dense_mode() != 'f32':
             # as in the inference executor: the projection on the fp16-split GEMM, the recurrence on the fragment-ordered copy of w_hh
             # (bit-identical to the unpacked step kernel); both weights change every step, so they are packed per call
             hip.lstm_input_projection_packed(xp, frames, hip.pack_pointwise_weights(w_ih.detach().contiguous()), b_ih.detach(), b_hh.detach(), gates,
@@ -146,7 +145,7 @@ class _LSTM(torch.autograd.Function):
         xp, gates, h_out, w_ih, w_hh = ctx.saved_tensors
         if ctx.frames == 0:
             return torch.zeros_like(xp[:, :, :0]), torch.zeros_like(w_ih), torch.zeros_like(w_hh), w_ih.new_zeros(w_ih.shape[0]), w_ih.new_zeros(w_ih.shape[0])
-        dx, dw_ih, dw_hh, db = hip.lstm_backward(xp, ctx.frames, gates, h_out, w_ih, w_hh, dh.contiguous())
+        dx, dw_ih, dw_hh, db = backward.lstm_backward(xp, ctx.frames, gates, h_out, w_ih, w_hh, dh.contiguous())
         return dx, dw_ih, dw_hh, db, db.clone()
 
 
@@ -177,7 +176,7 @@ class _PointwiseLinear(torch.autograd.Function):
         dyp = torch.zeros_like(y)
         dyp[:, :c_out, :frames] = dy
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        dx, dw, db = hip.dense_conv1d_backward(xp, w, y, dyp, frames, 1, need_dx, need_dw, activation=False)
+        dx, dw, db = backward.dense_conv1d_backward(xp, w, y, dyp, frames, 1, need_dx, need_dw, activation=False)
         return (dx[:, :, :frames] if dx is not None else None), (dw[:c_out] if dw is not None else None), (db[:c_out] if db is not None else None)
 
 

@@ -247,14 +247,7 @@ class ForwardPlan:
         self.batch = self.frames = self.out_frames = 0
         self.block_frames = []
         self.timer = None
-        # dense k=8 convs, all fp32-accurate:
-        #   'auto' (default) = 2-way fp16 split (3 MFMAs per product) wherever the input has just been written by the
-        #                      LayerNorm kernel (which also emits the per-utterance max|x| the scheme's range scaling
-        #                      needs), the 3-way bf16 split (6 MFMAs per product, fp32's exponent range) elsewhere;
-        #   'bf16x3' = 3-way bf16 split everywhere;  'f32' = the exact-fp32 MFMA kernel
-        self.dense_mode = os.environ.get('NBASR_DENSE_MODE', 'auto')
-        if self.dense_mode not in ('auto', 'bf16x3', 'f32'):
-            raise ValueError(f'NBASR_DENSE_MODE must be auto, bf16x3 or f32, got {self.dense_mode!r}')
+        self.dense_mode = hip.dense_mode()        # dense k=8 convs: 'auto' | 'bf16x3' | 'f32', all fp32-accurate (what each means: there)
         self._packed = {}            # (id(parameter), tag) -> (weakref(parameter), version, packed tensor)
         # per-frame linear maps (`linear` node ops, LSTM input projection): 'f16x2' = fp16 matrix cores with pre-split
         # activations (default), 'f32' = the exact-fp32 MFMA GEMM
@@ -263,7 +256,7 @@ class ForwardPlan:
             raise ValueError(f'NBASR_LINEAR_MODE must be f16x2 or f32, got {self.linear_mode!r}')
         # (round 3: the A/B switches of rounds 1-2 whose alternatives lost everywhere are gone -- NBASR_IMAGE_MODE, NBASR_ROW_TILE,
         # NBASR_LN_MODE, NBASR_EPILOGUE_STATS, NBASR_LSTM_UNPACKED, NBASR_GC_TABLE, NBASR_GC_BF16_VARIANT, NBASR_GC_BF16_MFMA; what is
-        # left: NBASR_DENSE_MODE (also read by autograd.py), NBASR_LINEAR_MODE, NBASR_CELL_FUSION, NBASR_GC_F32_VARIANT, NBASR_LSTM_SEQ, NBASR_TAPE, NBASR_CONV_STATS)
+        # left: NBASR_DENSE_MODE (hip.dense_mode(): also autograd.py, backward.py), NBASR_LINEAR_MODE, NBASR_CELL_FUSION, NBASR_GC_F32_VARIANT, NBASR_LSTM_SEQ, NBASR_TAPE, NBASR_CONV_STATS)
         self.dense_schemes = {}      # block -> scheme used by the last run (read by bench.py)
         self.dense_row_tiles = {}    # block -> rows per workgroup of the image-path GEMM in the last run
         self.dense_frame_tiles = {}  # block -> frames per workgroup (256, or 128 where the measured table says so)

@@ -2,10 +2,10 @@
 
 PyTorch is used here only as plumbing: device memory (``tensor.data_ptr()``) and the current HIP
 stream.  Every wrapper validates device / dtype / contiguity on the host, passes raw pointers
-and sizes, and raises ``HipError`` with the library's message on a non-zero return code.
-
-There is NO fallback: if the library is missing or the tensors are not on a HIP device the
-call fails loudly (build with ``python -m nb_asr_amd.build``).
+and sizes, and raises ``HipError`` with the library's message on a non-zero return code.  A wrapper
+allocates at most its outputs and scratch; the host algorithms that string wrappers together are next
+door (walk.py: the forward; backward.py: the dense and LSTM gradients).  There is NO fallback: a missing
+library or a tensor off the HIP device fails loudly (build with ``python -m nb_asr_amd.build``).
 """
 import ctypes
 import os
@@ -299,6 +299,20 @@ def round_up4(n):
     return (n + 3) & ~3
 
 
+def dense_mode():
+    """NBASR_DENSE_MODE as it is set NOW, validated; the one place that reads it.  Dense k = 8 convs, fp32-accurate in every mode: 'auto' (default)
+    = 2-way fp16 split (3 MFMAs per product) wherever the input has just been written by the LayerNorm kernel (which also emits the per-utterance
+    max|x| its range scaling needs), else the 3-way bf16 split (6 MFMAs, fp32's exponent range); 'bf16x3' = that everywhere; 'f32' = exact-fp32 MFMA."""
+    mode = os.environ.get('NBASR_DENSE_MODE', 'auto')
+    if mode not in ('auto', 'bf16x3', 'f32'):
+        raise ValueError(f'NBASR_DENSE_MODE must be auto, bf16x3 or f32, got {mode!r}')
+    return mode
+
+
+def _skips3(skips):
+    return list(skips) + [None] * (3 - len(skips))
+
+
 # ---------------------------------------------------------------------------------------------
 # device entry points; activations are (batch, channels, ld) float32 tensors whose last dimension
 # is the row pitch ld (a multiple of 4) and `frames` <= ld the number of valid frames
@@ -384,7 +398,7 @@ def skip_sum(skips, y, frames, ln=None, ln_on_skip0=False):
     """Node whose main op is `zero`: y = sum of the skips (float32 or bfloat16 tensors, all of y's type)."""
     b, c, ld = y.shape
     dt = y.dtype
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check(load_library().nbasr_skip_sum(_act_opt(s[0], 'skip0', dt), _act_opt(s[1], 'skip1', dt), _act_opt(s[2], 'skip2', dt),
                                          _act(y, 'y'), b, c, frames, ld, _ln(ln), int(ln_on_skip0), dtype_code(dt), _stream(y)),
            'nbasr_skip_sum')
@@ -477,7 +491,7 @@ def dense_conv1d_fused(x, frames_in, weight, bias, skips, y, stride, ln=None, ln
     b, c_in, ld_in = x.shape
     c_out, _, kernel = weight.shape if weight.dim() == 3 else (weight.shape[0], weight.shape[1], 1)
     ld_out = y.shape[2]
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check(load_library().nbasr_dense_conv1d_fused(
         _dev(x, 'x'), _dev(weight, 'weight'), _dev(bias, 'bias'), _opt(s[0], 'skip0'), _opt(s[1], 'skip1'),
         _opt(s[2], 'skip2'), _dev(y, 'y'), b, c_in, frames_in, ld_in, c_out, ld_out, kernel, stride, _ln(ln), int(ln_on_x),
@@ -552,7 +566,7 @@ def dense_conv1d_fused_packed(x, frames_in, packed, c_out, kernel, bias, skips, 
     ``x_absmax``: a (B,) float32 device tensor of upper bounds of max|x[b]| (see nbasr.h) and takes no deferred LayerNorm.
     ``stats_part`` (no skips): also emit the partial LayerNorm statistics of y (dense_stats_part_floats)."""
     b, c_in, ld_in = x.shape
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check_packed(packed, scheme, c_out, c_in, kernel)
     if scheme == 'f16x2':
         if ln is not None:
@@ -588,10 +602,15 @@ def lstm_pack_whh(w_hh):
     return packed
 
 
-def lstm_recurrence_packed(gates_ws, packed_whh, cell_ws, h_out):
-    b, frames, hidden = h_out.shape
+def _check_whh(packed_whh, h_out):
+    hidden = h_out.shape[2]
     if not packed_whh.is_cuda or packed_whh.dtype != torch.uint8 or packed_whh.numel() != load_library().nbasr_lstm_packed_whh_bytes(hidden):
         raise HipError('packed_whh must be the uint8 device tensor returned by lstm_pack_whh for this hidden size')
+    return h_out.shape
+
+
+def lstm_recurrence_packed(gates_ws, packed_whh, cell_ws, h_out):
+    b, frames, hidden = _check_whh(packed_whh, h_out)
     _check(load_library().nbasr_lstm_recurrence_packed(_dev(gates_ws, 'gates_ws'), packed_whh.data_ptr(), _dev(cell_ws, 'cell_ws'),
                                                        _dev(h_out, 'h_out'), b, frames, hidden, _stream(h_out)),
            'nbasr_lstm_recurrence_packed')
@@ -612,16 +631,13 @@ LSTM_CONTINUE = 2               # NBASR_LSTM_CONTINUE of nbasr_lstm_recurrence_f
 def lstm_recurrence_seq(gates_ws, packed_whh, cell_ws, h_out, seq_ws, flags=0):
     """lstm_recurrence_packed with all frames in ONE (cooperative) launch: w_hh resident in registers, h exchanged in payload-tagged
     granules; same h_out, bit for bit.  The first int32 of ``seq_ws`` is the status word (non-zero: a step timed out, h_out holds NaN)."""
-    b, frames, hidden = h_out.shape
-    lib = load_library()
-    if not packed_whh.is_cuda or packed_whh.dtype != torch.uint8 or packed_whh.numel() != lib.nbasr_lstm_packed_whh_bytes(hidden):
-        raise HipError('packed_whh must be the uint8 device tensor returned by lstm_pack_whh for this hidden size')
+    b, frames, hidden = _check_whh(packed_whh, h_out)
     need = lstm_seq_workspace_bytes(b, hidden, h_out.device)
     if need == 0 or seq_ws is None or not seq_ws.is_cuda or seq_ws.dtype != torch.uint8 or seq_ws.numel() < need:
         raise HipError(f'lstm_recurrence_seq: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_seq_workspace '
                        '(0 = this form does not apply)')
-    _check(lib.nbasr_lstm_recurrence_seq(_dev(gates_ws, 'gates_ws'), packed_whh.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
-                                         seq_ws.data_ptr(), b, frames, hidden, int(flags), _stream(h_out)), 'nbasr_lstm_recurrence_seq')
+    _check(load_library().nbasr_lstm_recurrence_seq(_dev(gates_ws, 'gates_ws'), packed_whh.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
+                                                    seq_ws.data_ptr(), b, frames, hidden, int(flags), _stream(h_out)), 'nbasr_lstm_recurrence_seq')
     return h_out
 
 
@@ -660,51 +676,42 @@ def lstm_xcd_workspace(batch, hidden, device):
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
+def _check_whh16(packed_whh16, xcd_ws, h_out, who, hint=''):
+    batch, _, hidden = h_out.shape
+    if not packed_whh16.is_cuda or packed_whh16.dtype != torch.uint8 or packed_whh16.numel() != load_library().nbasr_lstm_packed_whh16_bytes(hidden):
+        raise HipError('packed_whh16 must be the uint8 device tensor returned by lstm_pack_whh16 for this hidden size')
+    need = lstm_xcd_workspace_bytes(batch, hidden)
+    if need == 0 or not xcd_ws.is_cuda or xcd_ws.dtype != torch.uint8 or xcd_ws.numel() < need:
+        raise HipError(f'{who}: batch={batch} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace{hint}')
+    return h_out.shape
+
+
 def lstm_recurrence_xcd(gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, flags=0):
     """The recurrence as ONE resident launch, a tile of 16 utterances per XCD, on the fp16 matrix cores (nbasr.h, ABI 6): h_out agrees
     with lstm_recurrence_packed to fp32 round-off.  The status word of ``xcd_ws`` is read by ``lstm_seq_status``."""
-    b, frames, hidden = h_out.shape
-    lib = load_library()
-    if not packed_whh16.is_cuda or packed_whh16.dtype != torch.uint8 or packed_whh16.numel() != lib.nbasr_lstm_packed_whh16_bytes(hidden):
-        raise HipError('packed_whh16 must be the uint8 device tensor returned by lstm_pack_whh16 for this hidden size')
-    need = lstm_xcd_workspace_bytes(b, hidden)
-    if need == 0 or not xcd_ws.is_cuda or xcd_ws.dtype != torch.uint8 or xcd_ws.numel() < need:
-        raise HipError(f'lstm_recurrence_xcd: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace '
-                       f'(0 = the form does not apply)')
-    _check(lib.nbasr_lstm_recurrence_xcd(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
-                                         xcd_ws.data_ptr(), b, frames, hidden, int(flags), _stream(h_out)), 'nbasr_lstm_recurrence_xcd')
+    b, frames, hidden = _check_whh16(packed_whh16, xcd_ws, h_out, 'lstm_recurrence_xcd', ' (0 = the form does not apply)')
+    _check(load_library().nbasr_lstm_recurrence_xcd(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
+                                                    xcd_ws.data_ptr(), b, frames, hidden, int(flags), _stream(h_out)), 'nbasr_lstm_recurrence_xcd')
     return h_out
 
 
 def lstm_recurrence_frames16(gates_ws, packed_whh16, cell_ws, h_out, xcd_ws):
     """lstm_recurrence_xcd's arithmetic as one launch per frame (bit-identical h_out): the form of a pipelined tail and of a demoted plan."""
-    b, frames, hidden = h_out.shape
-    lib = load_library()
-    if not packed_whh16.is_cuda or packed_whh16.dtype != torch.uint8 or packed_whh16.numel() != lib.nbasr_lstm_packed_whh16_bytes(hidden):
-        raise HipError('packed_whh16 must be the uint8 device tensor returned by lstm_pack_whh16 for this hidden size')
-    need = lstm_xcd_workspace_bytes(b, hidden)
-    if need == 0 or not xcd_ws.is_cuda or xcd_ws.dtype != torch.uint8 or xcd_ws.numel() < need:
-        raise HipError(f'lstm_recurrence_frames16: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace')
-    _check(lib.nbasr_lstm_recurrence_frames16(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
-                                              xcd_ws.data_ptr(), b, frames, hidden, _stream(h_out)), 'nbasr_lstm_recurrence_frames16')
+    b, frames, hidden = _check_whh16(packed_whh16, xcd_ws, h_out, 'lstm_recurrence_frames16')
+    _check(load_library().nbasr_lstm_recurrence_frames16(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'), _dev(h_out, 'h_out'),
+                                                         xcd_ws.data_ptr(), b, frames, hidden, _stream(h_out)), 'nbasr_lstm_recurrence_frames16')
     return h_out
 
 
 def lstm_recurrence_frames16_state(gates_ws, packed_whh16, cell_ws, h_out, xcd_ws, h0=None, flags=0):
     """lstm_recurrence_frames16 with carried state: ``flags=LSTM_CONTINUE`` starts frame 0 from c = ``cell_ws`` and h = ``h0``
     ((batch, hidden) float32, None = zeros) instead of zeros (nbasr.h).  flags = 0 and h0 = None: bit-identical to lstm_recurrence_frames16."""
-    b, frames, hidden = h_out.shape
-    lib = load_library()
-    if not packed_whh16.is_cuda or packed_whh16.dtype != torch.uint8 or packed_whh16.numel() != lib.nbasr_lstm_packed_whh16_bytes(hidden):
-        raise HipError('packed_whh16 must be the uint8 device tensor returned by lstm_pack_whh16 for this hidden size')
-    need = lstm_xcd_workspace_bytes(b, hidden)
-    if need == 0 or not xcd_ws.is_cuda or xcd_ws.dtype != torch.uint8 or xcd_ws.numel() < need:
-        raise HipError(f'lstm_recurrence_frames16_state: batch={b} hidden={hidden} needs a uint8 device workspace of {need} bytes from lstm_xcd_workspace')
+    b, frames, hidden = _check_whh16(packed_whh16, xcd_ws, h_out, 'lstm_recurrence_frames16_state')
     if h0 is not None and h0.numel() != b * hidden:
         raise HipError(f'lstm_recurrence_frames16_state: h0 must hold ({b}, {hidden}) floats')
-    _check(lib.nbasr_lstm_recurrence_frames16_state(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'),
-                                                    _dev(h_out, 'h_out'), xcd_ws.data_ptr(), _opt(h0, 'h0'), b, frames, hidden, int(flags),
-                                                    _stream(h_out)), 'nbasr_lstm_recurrence_frames16_state')
+    _check(load_library().nbasr_lstm_recurrence_frames16_state(_dev(gates_ws, 'gates_ws'), packed_whh16.data_ptr(), _dev(cell_ws, 'cell_ws'),
+                                                               _dev(h_out, 'h_out'), xcd_ws.data_ptr(), _opt(h0, 'h0'), b, frames, hidden,
+                                                               int(flags), _stream(h_out)), 'nbasr_lstm_recurrence_frames16_state')
     return h_out
 
 
@@ -741,7 +748,7 @@ def linear_fused_packed(x, frames, packed, c_out, bias, skips, y, ws, ln=None, l
     """The `linear` node op on the fp16 matrix cores: y = min(relu(W x + b), 20) + skips (see nbasr.h)."""
     b, c_in, ld = x.shape
     _check_pointwise(packed, ws, c_out, c_in, b, ld)
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check(load_library().nbasr_linear_fused_packed(
         _dev(x, 'x'), ws.data_ptr(), packed.data_ptr(), _dev(bias, 'bias'), _opt(s[0], 'skip0'), _opt(s[1], 'skip1'),
         _opt(s[2], 'skip2'), _dev(y, 'y'), b, c_in, frames, ld, c_out, _ln(ln), int(ln_on_x), int(ln_on_skip0), _stream(x)),
@@ -793,7 +800,7 @@ def linear_fused_bf16(x, frames, packed, c_out, bias, skips, y, ws, ln=None, ln_
     b, c_in, ld = x.shape
     bf = torch.bfloat16
     _check_pointwise_bf16(packed, ws, c_out, c_in, b, ld)
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check(load_library().nbasr_linear_fused_bf16(
         _act(x, 'x', bf), ws.data_ptr(), packed.data_ptr(), _dev(bias, 'bias'), _act_opt(s[0], 'skip0', bf), _act_opt(s[1], 'skip1', bf),
         _act_opt(s[2], 'skip2', bf), _act(y, 'y', bf), b, c_in, frames, ld, c_out, _ln(ln), int(ln_on_x), int(ln_on_skip0), _stream(x)),
@@ -917,14 +924,11 @@ def ctc_postprocess(logits, lengths=None, want_log_probs=True, want_tokens=True,
     """logits (B, T', C) -> (log_probs or None, tokens (B, T') int32 padded with -1 or None, token_counts (B) or None)."""
     _dev(logits, 'logits')
     b, t, c = logits.shape
-    if lengths is not None:
-        if not lengths.is_cuda or lengths.dtype != torch.int32 or not lengths.is_contiguous() or lengths.numel() != b:
-            raise HipError('lengths must be a contiguous int32 device tensor with one entry per utterance')
     log_probs = torch.empty_like(logits) if want_log_probs else None
     tokens = torch.empty(b, t, dtype=torch.int32, device=logits.device) if want_tokens else None
     counts = torch.empty(b, dtype=torch.int32, device=logits.device) if want_tokens else None
     _check(load_library().nbasr_ctc_postprocess(
-        logits.data_ptr(), None if lengths is None else lengths.data_ptr(), None if log_probs is None else log_probs.data_ptr(),
+        logits.data_ptr(), _lengths_ptr(lengths, b), None if log_probs is None else log_probs.data_ptr(),
         None if tokens is None else tokens.data_ptr(), None if counts is None else counts.data_ptr(), b, t, c, blank,
         _stream(logits)), 'nbasr_ctc_postprocess')
     return log_probs, tokens, counts
@@ -1061,9 +1065,7 @@ def token_error_counts(hyp, hyp_len, ref, ref_len, table=None, blank=0):
     return counts
 
 
-def ctc_loss(log_probs, lengths, targets, target_lengths, blank=0, divide_by_length=False):
-    """log_probs (B, T', C) float32, lengths (B) int32, targets (B, L) int32, target_lengths (B) int32 (all on the device)
-    -> per-utterance negative log-likelihood (B) float32 with zero_infinity semantics, optionally divided by ``lengths``."""
+def _ctc_args(log_probs, lengths, targets, target_lengths):
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     dev = log_probs.device
@@ -1072,6 +1074,13 @@ def ctc_loss(log_probs, lengths, targets, target_lengths, blank=0, divide_by_len
     _int_tensor(targets, 'targets', dev)
     if targets.dim() != 2 or targets.shape[0] != b:
         raise HipError(f'targets must be (batch, labels), got {tuple(targets.shape)}')
+    return b, t, c, dev
+
+
+def ctc_loss(log_probs, lengths, targets, target_lengths, blank=0, divide_by_length=False):
+    """log_probs (B, T', C) float32, lengths (B) int32, targets (B, L) int32, target_lengths (B) int32 (all on the device)
+    -> per-utterance negative log-likelihood (B) float32 with zero_infinity semantics, optionally divided by ``lengths``."""
+    b, t, c, dev = _ctc_args(log_probs, lengths, targets, target_lengths)
     losses = torch.empty(b, dtype=torch.float32, device=dev)
     _check(load_library().nbasr_ctc_loss(log_probs.data_ptr(), lengths.data_ptr(), targets.data_ptr(), target_lengths.data_ptr(),
                                          losses.data_ptr(), b, t, c, targets.shape[1], blank, 1 if divide_by_length else 0,
@@ -1081,21 +1090,12 @@ def ctc_loss(log_probs, lengths, targets, target_lengths, blank=0, divide_by_len
 
 def ctc_loss_grad(log_probs, lengths, targets, target_lengths, blank=0):
     """-> (per-utterance loss / length (B), d mean(loss / length) / d logits (B, T', C)) for log_probs = log_softmax(logits)."""
-    _dev(log_probs, 'log_probs')
-    b, t, c = log_probs.shape
-    dev = log_probs.device
-    _int_tensor(lengths, 'lengths', dev, (b,))
-    _int_tensor(target_lengths, 'target_lengths', dev, (b,))
-    _int_tensor(targets, 'targets', dev)
-    if targets.dim() != 2 or targets.shape[0] != b:
-        raise HipError(f'targets must be (batch, labels), got {tuple(targets.shape)}')
-    lib = load_library()
+    b, t, c, dev = _ctc_args(log_probs, lengths, targets, target_lengths)
     losses = torch.empty(b, dtype=torch.float32, device=dev)
     grad = torch.empty_like(log_probs)
-    ws = torch.empty(max(lib.nbasr_ctc_grad_workspace_bytes(b, t, targets.shape[1]) // 4, 1), dtype=torch.float32, device=dev)
-    _check(lib.nbasr_ctc_loss_grad(log_probs.data_ptr(), lengths.data_ptr(), targets.data_ptr(), target_lengths.data_ptr(),
-                                   ws.data_ptr(), losses.data_ptr(), grad.data_ptr(), b, t, c, targets.shape[1], blank,
-                                   _stream(log_probs)), 'nbasr_ctc_loss_grad')
+    ws = torch.empty(max(load_library().nbasr_ctc_grad_workspace_bytes(b, t, targets.shape[1]) // 4, 1), dtype=torch.float32, device=dev)
+    _check(load_library().nbasr_ctc_loss_grad(log_probs.data_ptr(), lengths.data_ptr(), targets.data_ptr(), target_lengths.data_ptr(), ws.data_ptr(),
+                                              losses.data_ptr(), grad.data_ptr(), b, t, c, targets.shape[1], blank, _stream(log_probs)), 'nbasr_ctc_loss_grad')
     return losses, grad
 
 
@@ -1117,7 +1117,7 @@ def grouped_conv1d_node(x, weight, bias, skips, y, frames, groups, kernel, dilat
     layout the variant wants: torch's, or pack_grouped_weights' for GC_WPERM)."""
     b, c, ld = x.shape
     dt = x.dtype
-    s = list(skips) + [None] * (3 - len(skips))
+    s = _skips3(skips)
     _check(load_library().nbasr_grouped_conv1d_node(
         _act(x, 'x'), _dev(weight, 'weight'), _dev(bias, 'bias'), _act_opt(s[0], 'skip0', dt), _act_opt(s[1], 'skip1', dt),
         _act_opt(s[2], 'skip2', dt), _act(y, 'y', dt), b, c, frames, ld, groups, kernel, dilation, _ln(ln), int(ln_on_x),
@@ -1164,7 +1164,7 @@ def dense_conv1d_bf16_img(image, batch, c_in, frames_in, ld_in, packed, c_out, k
 
 
 # ---------------------------------------------------------------------------------------------
-# backward building blocks
+# backward building blocks; backward.py strings the last eight together (nbasr.h says what each computes)
 # ---------------------------------------------------------------------------------------------
 def grouped_conv1d_backward(x, weight, z, dz, frames, groups, kernel, dilation, need_dx=True, need_dw=True):
     """Gradients of z = min(relu(grouped_conv(x, weight) + bias), 20) given dz: (dx or None, dw or None, db or None).
@@ -1198,176 +1198,48 @@ def layernorm_channels_backward(x, stats, gamma, dy, frames):
     return dx, dgamma, dbeta
 
 
-def dense_conv1d_backward(x, weight, y, dy, frames_in, stride, need_dx=True, need_dw=True, activation=True):
-    """Backward of ``y = min(relu(conv1d(zero_pad(x), weight, bias, stride)), 20)`` for the dense k = 8 downsample convs (stride 1 | 2) and
-    the per-frame ``linear`` op (k = 1): x (B, C_in, ld_in), y / dy (B, C_out, ld_out) pitched -> (dx, dw, db).  ``activation=False``: the map
-    without ReLU / clamp (the CTC head).
+def relu_clamp_backward(y, dy, dz):
+    _check(load_library().nbasr_relu_clamp_backward(_dev(y, 'y'), _dev(dy, 'dy'), _dev(dz, 'dz'), y.numel(), _stream(y)), 'nbasr_relu_clamp_backward')
+    return dz
 
-    Correctness-first.  Weight and bias gradients: ONE (C_out, B * T') x (B * T', C_in * k + 1) GEMM on a materialised
-    column matrix.  Input gradient of the k = 8 convs: ONE (C_in * 8, C_out) x (C_out, B * T') GEMM, then a fold of the 8 tap rows onto
-    the input frames (nbasr_conv_fold).  Both GEMMs run on the fp16 matrix cores with the fp32-accurate two-term split;
-    ``NBASR_DENSE_MODE=f32`` keeps every product on the exact-fp32 MFMA GEMMs of the forward (there the input gradient is a stride-1 conv
-    of the zero-stuffed, masked output gradient with the flipped, channel-transposed kernel)."""
-    lib = load_library()
+
+def zero_stuff(dz, up, frames, frames_up, stride, shift):
+    b, c, ld = dz.shape
+    _check(load_library().nbasr_zero_stuff(_dev(dz, 'dz'), _dev(up, 'up'), b * c, frames, ld, frames_up, up.shape[2], stride, shift, _stream(dz)),
+           'nbasr_zero_stuff')
+
+
+def dense_conv1d_linear(x, frames, weight, bias, y, lpad):
     b, c_in, ld_in = x.shape
-    c_out, _, kernel = weight.shape if weight.dim() == 3 else (weight.shape[0], weight.shape[1], 1)
-    ld_out = y.shape[2]
-    frames_out = (frames_in + stride - 1) // stride
-    lpad = pad_amounts(kernel, 1, stride)[0]
-    stream = _stream(x)
-    if activation:
-        dz = torch.empty_like(y)
-        _check(lib.nbasr_relu_clamp_backward(_dev(y, 'y'), _dev(dy, 'dy'), _dev(dz, 'dz'), y.numel(), stream), 'nbasr_relu_clamp_backward')
-    else:
-        dz = dy                                             # a plain linear map (the CTC head): no mask
-    dx = dw = db = None
-    if need_dx:
-        dx = torch.empty(b, c_in, ld_in, device=x.device, dtype=torch.float32)
-        zero = torch.zeros(c_in, device=x.device, dtype=torch.float32)
-        if kernel == 1:
-            wt = weight.detach().reshape(c_out, c_in).t().contiguous()
-            _check(lib.nbasr_pointwise_linear(_dev(dz, 'dz'), _dev(wt, 'wt'), _dev(zero, 'zero'), _dev(dx, 'dx'), b, c_out, frames_in, ld_out,
-                                              c_in, ld_in, stream), 'nbasr_pointwise_linear')
-        elif kernel == 8 and (c_in * kernel) % 16 == 0 and os.environ.get('NBASR_DENSE_MODE', 'auto') != 'f32':
-            # ONE GEMM on the fp16 matrix cores (fp32-accurate two-term split, the kernel of the LSTM input projection): rows (ci, tap) of
-            # w^T times the masked output gradient, stored time-major, every tap's contribution to dx in its own row; nbasr_conv_fold adds
-            # the 8 (stride 1) or 4 (stride 2) rows that land on one input frame.  No zero-stuffing: half the products at stride 2.
-            rows_w = c_in * kernel
-            wt = weight.detach().permute(1, 2, 0).reshape(rows_w, c_out).contiguous()
-            packed = pack_pointwise_weights(wt)
-            ws = pointwise_workspace(b, c_out, ld_out, x.device)
-            zero_r = torch.zeros(rows_w, device=x.device, dtype=torch.float32)
-            taps = torch.empty(max(frames_out, 1), b, rows_w, device=x.device, dtype=torch.float32)
-            lstm_input_projection_packed(dz, frames_out, packed, zero_r, zero_r, taps, rows_w // 4, ws)
-            _check(lib.nbasr_conv_fold(_dev(taps, 'taps'), _dev(dx, 'dx'), b, c_in, frames_in, ld_in, frames_out, kernel, stride, lpad, stream),
-                   'nbasr_conv_fold')
-        else:
-            up = torch.empty(b, c_out, ld_in, device=x.device, dtype=torch.float32)
-            _check(lib.nbasr_zero_stuff(_dev(dz, 'dz'), _dev(up, 'up'), b * c_out, frames_out, ld_out, frames_in, ld_in, stride, 0, stream),
-                   'nbasr_zero_stuff')
-            wf = weight.detach().flip(2).permute(1, 0, 2).contiguous()                 # (C_in, C_out, k): flipped taps, channels swapped
-            _check(lib.nbasr_dense_conv1d_linear(_dev(up, 'up'), _dev(wf, 'wf'), _dev(zero, 'zero'), _dev(dx, 'dx'), b, c_out, frames_in, ld_in,
-                                                 c_in, ld_in, kernel, kernel - 1 - lpad, stream), 'nbasr_dense_conv1d_linear')
-    if need_dw:
-        t_pad = round_up4(max(frames_out, 1))
-        ld_cols = round_up4(c_in * kernel + 1)
-        cols = torch.empty(b * t_pad, ld_cols, device=x.device, dtype=torch.float32)
-        _check(lib.nbasr_conv_cols(_dev(x, 'x'), _dev(cols, 'cols'), b, c_in, frames_in, ld_in, frames_out, t_pad, kernel, stride, lpad, ld_cols,
-                                   stream), 'nbasr_conv_cols')
-        rows = torch.empty(c_out, b * t_pad, device=x.device, dtype=torch.float32)
-        _check(lib.nbasr_rows_of_channels(_dev(dz, 'dz'), _dev(rows, 'rows'), b, c_out, frames_out, ld_out, t_pad, stream), 'nbasr_rows_of_channels')
-        zero_o = torch.zeros(c_out, device=x.device, dtype=torch.float32)
-        if os.environ.get('NBASR_DENSE_MODE', 'auto') != 'f32':
-            # the (C_out, B T') x (B T', C_in k + 1) product on the fp16 matrix cores, fp32-accurate two-term split (the GEMM of the LSTM
-            # input projection: "weights" = the masked output gradient packed per call, "x" = the column matrix pre-split per column tile);
-            # it stores time-major, i.e. the transpose (C_in k + 1, C_out).  3-5 x the exact-fp32 MFMA GEMM, which was half of a training step
-            c_pad = (c_out + 15) & ~15                       # (that entry point takes 4 * hidden rows, hidden % 4 == 0)
-            if c_pad != c_out:
-                rows = torch.cat([rows, rows.new_zeros(c_pad - c_out, rows.shape[1])])
-            zero_p = torch.zeros(c_pad, device=x.device, dtype=torch.float32)
-            packed = pack_pointwise_weights(rows)
-            ws = pointwise_workspace(1, b * t_pad, ld_cols, x.device)
-            out_t = torch.empty(ld_cols, 1, c_pad, device=x.device, dtype=torch.float32)
-            lstm_input_projection_packed(cols.view(1, b * t_pad, ld_cols), c_in * kernel + 1, packed, zero_p, zero_p, out_t, c_pad // 4, ws)
-            out = out_t.view(ld_cols, c_pad).t()[:c_out]
-        else:
-            out3 = torch.empty(1, c_out, ld_cols, device=x.device, dtype=torch.float32)
-            _check(lib.nbasr_pointwise_linear(_dev(cols, 'cols'), _dev(rows, 'rows'), _dev(zero_o, 'zero'), _dev(out3, 'out'), 1, b * t_pad,
-                                              c_in * kernel + 1, ld_cols, c_out, ld_cols, stream), 'nbasr_pointwise_linear')
-            out = out3[0]
-        dw = out[:, : c_in * kernel].reshape(c_out, c_in, kernel).contiguous()
-        if weight.dim() == 2:
-            dw = dw.reshape(c_out, c_in)
-        db = out[:, c_in * kernel].contiguous()
-    return dx, dw, db
+    c_out, _, kernel = weight.shape
+    _check(load_library().nbasr_dense_conv1d_linear(_dev(x, 'x'), _dev(weight, 'weight'), _dev(bias, 'bias'), _dev(y, 'y'), b, c_in, frames, ld_in,
+                                                    c_out, y.shape[2], kernel, lpad, _stream(x)), 'nbasr_dense_conv1d_linear')
 
 
-def lstm_backward(xp, frames, gates, h_out, w_ih, w_hh, dh_out):
-    """BPTT of the single-layer LSTM (reference model.py:100,118-121): xp (B, C, ld) the layer input, gates (T, B, 4H) its saved input
-    projection (both biases included), h_out (B, T, H) the saved output, dh_out (B, T, H) -> (dx (B, C, T), dw_ih, dw_hh, db).
+def conv_cols(x, cols, frames_in, frames_out, t_pad, taps, stride, lpad):
+    b, c_in, ld_in = x.shape
+    _check(load_library().nbasr_conv_cols(_dev(x, 'x'), _dev(cols, 'cols'), b, c_in, frames_in, ld_in, frames_out, t_pad, taps, stride, lpad,
+                                          cols.shape[-1], _stream(x)), 'nbasr_conv_cols')
 
-    Correctness first: gate pre-activations of all frames are recomputed from the saved h by ONE GEMM, a serial
-    scan restores the cell states, the reverse recurrence is T launches of a step kernel that forms w_hh^T . dpre of the next frame in place, and the weight / input gradients
-    are batched GEMMs -- on the fp16 matrix cores with the fp32-accurate two-term split (``NBASR_DENSE_MODE=f32``: the exact-fp32 MFMA GEMM
-    nbasr_pointwise_linear); tensor re-layouts are torch copies."""
-    lib = load_library()
-    b, c, _ = xp.shape
-    t_n, hidden = frames, w_hh.shape[1]
-    g4 = 4 * hidden
-    dev, f32 = xp.device, torch.float32
-    if hidden % 4:
-        raise HipError('lstm_backward: hidden must be a multiple of 4')
-    ldb = round_up4(b)
-    n = t_n * ldb                                              # GEMM column count; (frame, utterance) pairs, utterance innermost
-    stream = _stream(xp)
 
-    def gemm(x_ptr, c_in, cols, ld_in, w, y):
-        """y (1, c_out, ld_out) = w (c_out, c_in) . x (c_in rows of `cols` floats at pitch ld_in)"""
-        zero = torch.zeros(w.shape[0], device=dev, dtype=f32)
-        _check(lib.nbasr_pointwise_linear(x_ptr, _dev(w, 'w'), _dev(zero, 'zero'), _dev(y, 'y'), 1, c_in, cols, ld_in, w.shape[0], y.shape[2],
-                                          stream), 'nbasr_pointwise_linear')
-        return y
+def rows_of_channels(dz, rows, frames, t_pad):
+    b, c, ld = dz.shape
+    _check(load_library().nbasr_rows_of_channels(_dev(dz, 'dz'), _dev(rows, 'rows'), b, c, frames, ld, t_pad, _stream(dz)), 'nbasr_rows_of_channels')
 
-    split = os.environ.get('NBASR_DENSE_MODE', 'auto') != 'f32'
 
-    def gemm_t(x3, cols, w):
-        """(w (rows, K) . x3 (1, K, ld))^T -> (cols, rows): the same product on the fp16 matrix cores (fp32-accurate two-term split; the
-        GEMM of the LSTM input projection, which stores time-major, i.e. transposed); w is packed per call."""
-        rows, k = w.shape
-        r_pad = (rows + 15) & ~15                               # (that entry point takes 4 * hidden rows, hidden % 4 == 0)
-        if r_pad != rows:
-            w = torch.cat([w, w.new_zeros(r_pad - rows, k)])
-        zero = torch.zeros(r_pad, device=dev, dtype=f32)
-        out_t = torch.empty(x3.shape[2], 1, r_pad, device=dev, dtype=f32)
-        lstm_input_projection_packed(x3, cols, pack_pointwise_weights(w.contiguous()), zero, zero, out_t, r_pad // 4,
-                                     pointwise_workspace(1, k, x3.shape[2], dev))
-        return out_t.view(x3.shape[2], r_pad)[:cols, :rows]
+def conv_fold(cols, dx, frames_in, frames_out, taps, stride, lpad):
+    b, c_in, ld_in = dx.shape
+    _check(load_library().nbasr_conv_fold(_dev(cols, 'cols'), _dev(dx, 'dx'), b, c_in, frames_in, ld_in, frames_out, taps, stride, lpad, _stream(dx)),
+           'nbasr_conv_fold')
 
-    # h_(t-1) for every (t, b): rows of the (T * ldb, H) matrix, zero for t = 0 and for the pitch utterances
-    hp = torch.zeros(t_n, ldb, hidden, device=dev, dtype=f32)
-    if t_n > 1:
-        hp[1:, :b] = h_out[:, : t_n - 1].permute(1, 0, 2)
-    hp_t = hp.reshape(n, hidden).t().contiguous()              # (H, T * ldb)
-    if split:
-        pre = gemm_t(hp_t.view(1, hidden, n), n, w_hh.detach()).t().contiguous()
-    else:
-        pre = torch.empty(1, g4, n, device=dev, dtype=f32)
-        gemm(hp_t.data_ptr(), hidden, n, n, w_hh.detach().contiguous(), pre)
-    pre = pre.view(g4, t_n, ldb)
-    pre[:, :, :b] += gates[:t_n].permute(2, 0, 1)             # + input projection and biases
-    cells = torch.zeros(hidden, t_n, ldb, device=dev, dtype=f32)
-    _check(lib.nbasr_lstm_gate_scan(_dev(pre, 'pre'), _dev(cells, 'cells'), hidden, t_n, b, ldb, stream), 'nbasr_lstm_gate_scan')
-    acts = pre                                                 # overwritten in place by the scan
-    dho = torch.zeros(hidden, t_n, ldb, device=dev, dtype=f32)
-    dho[:, :, :b] = dh_out.detach().permute(2, 1, 0)
-    dpre = torch.empty(g4, t_n, ldb, device=dev, dtype=f32)
-    dc = torch.zeros(hidden, ldb, device=dev, dtype=f32)
-    w_hh_t = w_hh.detach().t().contiguous()                    # (H, 4H)
-    # (t = -1: the whole reverse recurrence, frames T-1 .. 0, in one call -- round 6; rounds 2-5 issued the frames from a python loop)
-    _check(lib.nbasr_lstm_backward_step(_dev(dho, 'dho'), _dev(w_hh_t, 'w_hh_t'), _dev(dc, 'dc'), _dev(acts, 'acts'), _dev(cells, 'cells'),
-                                        _dev(dpre, 'dpre'), hidden, t_n, b, ldb, -1, stream), 'nbasr_lstm_backward_step')
-    d2 = dpre.view(g4, n)
-    ldc = round_up4(c + 1)
-    if split:
-        # (dw_ih | db | dw_hh) (4H, C + 1 + H) = dpre (4H, n) . (x | 1 | h_prev) (n, .): ONE GEMM, dpre packed once
-        xh = torch.zeros(t_n, ldb, ldc + hidden, device=dev, dtype=f32)
-        xh[:, :b, :c] = xp[:, :, :t_n].permute(2, 0, 1)
-        xh[:, :b, c] = 1.0
-        xh[:, :, ldc:] = hp
-        wb = gemm_t(xh.view(1, n, ldc + hidden), ldc + hidden, d2).t()
-        dw_ih, db, dw_hh = wb[:, :c].contiguous(), wb[:, c].contiguous(), wb[:, ldc:].contiguous()
-        # dx (C, n) = w_ih^T (C, 4H) . dpre (4H, n), delivered transposed: (n, C)
-        dx = gemm_t(dpre.view(1, g4, n), n, w_ih.detach().t()).view(t_n, ldb, c)[:, :b].permute(1, 2, 0).contiguous()
-        return dx, dw_ih, dw_hh, db
-    # dw_hh (4H, H) = dpre (4H, n) . h_prev (n, H)
-    dw_hh = gemm(hp.data_ptr(), n, hidden, hidden, d2, torch.empty(1, g4, hidden, device=dev, dtype=f32))[0]
-    # (dw_ih | db) (4H, C + 1) = dpre . (x | 1)
-    xt = torch.zeros(t_n, ldb, ldc, device=dev, dtype=f32)
-    xt[:, :b, :c] = xp[:, :, :t_n].permute(2, 0, 1)
-    xt[:, :b, c] = 1.0
-    wb = gemm(xt.data_ptr(), n, c + 1, ldc, d2, torch.empty(1, g4, ldc, device=dev, dtype=f32))[0]
-    dw_ih, db = wb[:, :c].contiguous(), wb[:, c].contiguous()
-    # dx (C, n) = w_ih^T (C, 4H) . dpre (4H, n)
-    dxc = gemm(dpre.data_ptr(), g4, n, n, w_ih.detach().t().contiguous(), torch.empty(1, c, n, device=dev, dtype=f32))[0]
-    dx = dxc.view(c, t_n, ldb)[:, :, :b].permute(2, 0, 1).contiguous()
-    return dx, dw_ih, dw_hh, db
+
+def lstm_gate_scan(pre, cells, batch):
+    """Overwrites pre (4H, T, ldb) with the gate activations; cells (H, T, ldb) <- c_t."""
+    hidden, frames, ldb = cells.shape
+    _check(load_library().nbasr_lstm_gate_scan(_dev(pre, 'pre'), _dev(cells, 'cells'), hidden, frames, batch, ldb, _stream(pre)), 'nbasr_lstm_gate_scan')
+
+
+def lstm_backward_step(dh_out, w_hh_t, dc, acts, cells, dpre, batch, t):
+    hidden, frames, ldb = cells.shape
+    _check(load_library().nbasr_lstm_backward_step(_dev(dh_out, 'dho'), _dev(w_hh_t, 'w_hh_t'), _dev(dc, 'dc'), _dev(acts, 'acts'), _dev(cells, 'cells'),
+                                                   _dev(dpre, 'dpre'), hidden, frames, batch, ldb, t, _stream(dh_out)), 'nbasr_lstm_backward_step')

@@ -8,7 +8,7 @@ import torch
 
 import cases
 from conftest import GOLDEN
-from nb_asr_amd import autograd as nb_autograd, hip, ops
+from nb_asr_amd import autograd as nb_autograd, backward, hip, ops
 from nb_asr_amd.utils import keyed_normal
 
 pytestmark = pytest.mark.gpu
@@ -230,9 +230,9 @@ def test_dense_input_gradient_on_the_split_gemm_matches_the_exact_route(monkeypa
     y[:, :, :t_out] = (torch.randn(b, c_out, t_out, device=DEV) * 8.0).clamp(0.0, 20.0)
     dy = torch.zeros(b, c_out, ld_out, device=DEV)
     dy[:, :, :t_out] = torch.randn(b, c_out, t_out, device=DEV) * 1e-3
-    dx, dw, db = hip.dense_conv1d_backward(x, w, y, dy, t, stride)
+    dx, dw, db = backward.dense_conv1d_backward(x, w, y, dy, t, stride)
     monkeypatch.setenv('NBASR_DENSE_MODE', 'f32')
-    dx_e, dw_e, db_e = hip.dense_conv1d_backward(x, w, y, dy, t, stride)
+    dx_e, dw_e, db_e = backward.dense_conv1d_backward(x, w, y, dy, t, stride)
     assert not torch.equal(dx, dx_e)                                  # (two routes indeed)
     assert torch.equal(dx[:, :, t:], torch.zeros_like(dx[:, :, t:]))
     scale = float(dx_e.abs().max())

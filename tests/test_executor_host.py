@@ -157,3 +157,19 @@ def test_removed_environment_switches_are_announced_once(monkeypatch):
         executor._warn_removed_switches()
         executor._warn_removed_switches()
     assert len(seen) == 1 and 'NBASR_TRAIN_GEMM' in str(seen[0].message) and 'NBASR_DENSE_MODE' in str(seen[0].message)
+
+
+def test_dense_mode_is_read_and_validated_at_call_time(monkeypatch):
+    """hip.dense_mode() is the one reader of NBASR_DENSE_MODE (inference plan, autograd, backward): nothing cached at import, and a
+    misspelt value raises in training as it does when a plan is built."""
+    monkeypatch.delenv('NBASR_DENSE_MODE', raising=False)
+    assert hip.dense_mode() == 'auto' and executor.ForwardPlan('cpu').dense_mode == 'auto'
+    for value in ('auto', 'bf16x3', 'f32'):
+        monkeypatch.setenv('NBASR_DENSE_MODE', value)
+        assert hip.dense_mode() == value and executor.ForwardPlan('cpu').dense_mode == value
+    for value in ('F32', 'fp32'):
+        monkeypatch.setenv('NBASR_DENSE_MODE', value)
+        with pytest.raises(ValueError, match=f'NBASR_DENSE_MODE must be auto, bf16x3 or f32, got {value!r}'):
+            hip.dense_mode()
+        with pytest.raises(ValueError, match='NBASR_DENSE_MODE must be auto, bf16x3 or f32'):
+            executor.ForwardPlan('cpu')
