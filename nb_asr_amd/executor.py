@@ -15,20 +15,21 @@ object: its workspaces only ever grow (a stream of TIMIT batches whose length di
 same memory), and the model is passed to every call, so ``torch.nn.DataParallel`` replicas (shallow copies of
 the module that share the plan pool) each run with their own parameters.
 
-This module keeps what outlives a call: ``ForwardPlan`` (workspaces, derived-weight cache, tile choices, the LSTM recurrence, launch
-tapes, captured graphs, the pipelined tail's streams and buffers) and ``PlanPool``.  The launch sequence of ONE forward -- a dispatch
-loop over ``model.model`` with one step per layer kind, shared by the fp32 and the bf16 storage path, and the state that forward
-carries -- is ``walk.py``; ``node_into`` below is the one node launch both of them (and ``Node.forward``, ``streaming``) go through.
+This module keeps what outlives a call: ``ForwardPlan`` (workspaces, derived-weight cache, the LSTM recurrence, captured graphs, the
+pipelined tail's streams and buffers) and ``PlanPool``.  What a plan merely uses has a module of its own: the tile and kernel-variant
+choices are the free functions of ``tiles.py``; launch tapes -- key, record-or-replay, the one ``invalidate()`` -- are ``tape.py``; the
+ring of recurrence status words is ``seq_status.py``.  The launch sequence of ONE forward -- a dispatch loop over ``model.model`` with
+one step per layer kind, shared by the fp32 and the bf16 storage path, and the state that forward carries -- is ``walk.py``;
+``node_into`` below is the one node launch both of them (and ``Node.forward``, ``streaming``) go through.
 """
-import collections
-import math
 import os
 import threading
 import weakref
 
 import torch
 
-from . import hip
+from . import hip, seq_status, tape
+from .tape import LaunchTape, _structure_epoch          # noqa: F401  (tests build a LaunchTape and read the epoch through this module)
 
 
 def node_into(node, inputs, frames, out, ln0=None, stats=None, linear_ctx=None, gc_variant=0, copies=None):
@@ -119,100 +120,6 @@ class GroupLogits(PendingLogits):
         return super().result()
 
 
-def _load_gc_table():
-    import json
-    import pathlib
-    path = pathlib.Path(__file__).with_name('gc_variant_table.json')
-    return json.loads(path.read_text()) if path.exists() else {}
-
-
-_GC_TABLE = _load_gc_table()
-
-
-def _load_dense_tile_table():
-    """Measured us per launch of the image-path dense convolution per (row tile, frame tile): nb_asr_amd/dense_tile_table.json
-    (tools/ubench/dense_tiles.py -> tools/make_dense_tile_table.py), {(c_in, c_out, stride, frames_out): {batch: {(rows, frames): us}}}."""
-    import json
-    import pathlib
-    path = pathlib.Path(__file__).with_name('dense_tile_table.json')
-    if not path.exists():
-        return {}
-    raw = json.loads(path.read_text())['table']
-    return {tuple(int(v) for v in k.split(',')): {int(b): {tuple(int(v) for v in t.split('x')): us for t, us in row.items()} for b, row in by_b.items()}
-            for k, by_b in raw.items()}
-
-
-_DENSE_TILES = _load_dense_tile_table()
-
-
-# Any submodule or parameter (re-)registered on any module bumps this counter: a launch tape recorded before is not replayed
-# afterwards (a layer swapped inside a model that has already run must be seen by the next forward).
-_structure_epoch = [0]
-
-
-def _bump_structure_epoch(*_args):
-    _structure_epoch[0] += 1
-
-
-torch.nn.modules.module.register_module_module_registration_hook(_bump_structure_epoch)
-torch.nn.modules.module.register_module_parameter_registration_hook(_bump_structure_epoch)
-
-
-class LaunchTape:
-    """The enqueueing C-ABI calls of ONE forward, recorded once and replayed for every later batch with the same key
-    (shape, dtype, streams, parameter addresses and versions): the plan's workspaces and the derived weight copies sit
-    at fixed addresses, so the only arguments that change are the caller's input pointer and the freshly allocated
-    logits, which are patched into the recorded argument lists.  Host-side steps that belong to the sequence (event
-    record / wait between the main and the side stream, the logits allocation) are recorded as callables.
-
-    Why: a forward is ~380 launches, ~130 of them issued from python at ~12 us each; at 8 utterances per GPU (the
-    strong-scaling split of the benchmark batch) that host time, 2.4 ms, exceeds the device time.  A replay issues the same
-    calls in ~0.4 ms (tools/ubench/host_issue.py)."""
-
-    def __init__(self, entries, x_ptr, pipelined, pipe, group=None):
-        self.entries, self.pipelined, self.pipe, self.group = entries, pipelined, pipe, group
-        self.x_slots = []
-        producers = [(i, e) for i, e in enumerate(entries) if e[0] is None and e[2] is not None]
-        for i, e in enumerate(entries):
-            if e[0] is None:
-                continue
-            for j, a in enumerate(e[1]):
-                if type(a) is not int:
-                    continue
-                if a == x_ptr:
-                    self.x_slots.append((i, j))
-                for pi, pe in producers:
-                    if pi < i and a == pe[2]:
-                        pe[3].append((i, j))
-        self.launches = sum(1 for e in entries if e[0] is not None)
-
-    def replay(self, plan, x):
-        entries = self.entries
-        if not self.pipe:
-            plan.wait_tails()
-        px = x.data_ptr()
-        for i, j in self.x_slots:
-            entries[i][1][j] = px
-        for e in entries:
-            fn = e[0]
-            if fn is None:
-                t = e[1]()
-                if e[3]:
-                    p = t.data_ptr()
-                    for i, j in e[3]:
-                        entries[i][1][j] = p
-            else:
-                rc = fn(*e[1])
-                if rc:
-                    hip._check(rc, fn.__name__)
-        logits, plan._tape_logits = plan._tape_logits, None
-        if self.group is not None:
-            return plan._group_member(self.group, logits)
-        if self.pipelined:
-            return PendingLogits(logits, plan.tail_done[plan._turn] if self.pipe else None)
-        return logits
-
-
 # Environment switches of earlier rounds that no longer exist: a script that still sets one gets ONE warning instead of silence (ADVICE r3)
 _REMOVED_SWITCHES = {
     'NBASR_TRAIN_GEMM': 'folded into NBASR_DENSE_MODE (f32 = every GEMM on the exact-fp32 MFMA)',
@@ -254,9 +161,6 @@ class ForwardPlan:
         self.linear_mode = os.environ.get('NBASR_LINEAR_MODE', 'f16x2')
         if self.linear_mode not in ('f16x2', 'f32'):
             raise ValueError(f'NBASR_LINEAR_MODE must be f16x2 or f32, got {self.linear_mode!r}')
-        # (round 3: the A/B switches of rounds 1-2 whose alternatives lost everywhere are gone -- NBASR_IMAGE_MODE, NBASR_ROW_TILE,
-        # NBASR_LN_MODE, NBASR_EPILOGUE_STATS, NBASR_LSTM_UNPACKED, NBASR_GC_TABLE, NBASR_GC_BF16_VARIANT, NBASR_GC_BF16_MFMA; what is
-        # left: NBASR_DENSE_MODE (hip.dense_mode(): also autograd.py, backward.py), NBASR_LINEAR_MODE, NBASR_CELL_FUSION, NBASR_GC_F32_VARIANT, NBASR_LSTM_SEQ, NBASR_TAPE, NBASR_CONV_STATS)
         self.dense_schemes = {}      # block -> scheme used by the last run (read by bench.py)
         self.dense_row_tiles = {}    # block -> rows per workgroup of the image-path GEMM in the last run
         self.dense_frame_tiles = {}  # block -> frames per workgroup (256, or 128 where the measured table says so)
@@ -281,17 +185,11 @@ class ForwardPlan:
             raise ValueError(f"NBASR_TAIL={self.tail_mode!r}: expected 'auto', 'side' or 'main'")
         self._group_handles = []      # handles of the tail group being enqueued (_group_member)
         self._released_on, self._released_event = None, None   # PlanPool: the stream the last forward was enqueued on, an event behind it
-        self._seq_host, self._seq_pending = None, None      # pinned ring of status words / deque of (event behind the copy, slot) (check_seq)
-        self._seq_slot, self._seq_failed = 0, False
-        self._seq_outcome = {}       # ring slot -> whether that launch failed, once its word has been read (check_seq_slot)
-        self._seq_lock = threading.Lock()    # PendingLogits.result() may run on another thread than the one enqueueing through the plan
+        self.seq_status = seq_status.SeqStatusRing()     # the status words of the one-launch recurrences (check_seq, check_seq_slot)
         self._seq_last = None        # (event, slot) of the status copy the forward being enqueued has just added
         # statistics of a downsample convolution's output from its own epilogue (round 5); NBASR_CONV_STATS=0: a pass over the output
         self.conv_stats = os.environ.get('NBASR_CONV_STATS', '1') != '0'
         self._seq_flags = hip.LSTM_SEQ_INJECT_FAULT if os.environ.get('NBASR_LSTM_SEQ_FAULT') == '1' else 0     # tests: force a timeout
-        # fp32 node kernel variant per launch from the measured table (_gc_variant); NBASR_GC_F32_VARIANT=<bits> forces one (0: the
-        # default kernel everywhere)
-        self.gc_table = _GC_TABLE
         self._bufs = {}              # name -> flat tensor; grow-only (see _buf)
         self.grow_count = 0          # number of (re)allocations so far (tests: a smaller batch must not allocate)
         # pipelined mode (forward_async): the latency-bound LSTM + head of batch i run on a side stream while the main
@@ -300,14 +198,14 @@ class ForwardPlan:
         self._graphs = {}            # (batch, frames) -> (graph, parameter signature, x_static, y_static)
         self.tail_done = [None, None]
         self._turn = 0
-        # launch tapes (LaunchTape): NBASR_TAPE=0 issues every forward through the python launch sequence
+        # launch tapes (tape.py): NBASR_TAPE=0 issues every forward through the python launch sequence
         self.tape_mode = os.environ.get('NBASR_TAPE', '1') != '0'
-        self._tapes, self._tape_seen = {}, {}
-        self._recording = None       # the entries list while a tape is being recorded
-        self._mutations = 0          # workspace growths + derived-weight rebuilds (either one invalidates every tape)
-        self._tape_logits = None
-        self._param_slots = None     # (weakref(model), [(module._parameters, name), ...])
-        self.tape_replays = 0
+        self.tapes = tape.Tapes()            # (tests read and set its state through _tapes, tape_replays and _recording below)
+        self._tape_logits = None     # the logits of the forward being enqueued (_new_logits): what a replay hands out
+
+    _tapes = property(lambda self: self.tapes.tapes)
+    tape_replays = property(lambda self: self.tapes.replays)
+    _recording = property(lambda self: self.tapes.recording, lambda self, entries: setattr(self.tapes, 'recording', entries))
 
     # ---- grow-only workspaces ---------------------------------------------------------------------------------------
     def _buf(self, name, numel, dtype=torch.float32):
@@ -317,8 +215,7 @@ class ForwardPlan:
         if t is None or t.numel() < numel or t.dtype != dtype:
             self.wait_tails()
             self._graphs.clear()
-            self._tapes.clear()
-            self._mutations += 1
+            self.tapes.invalidate()
             t = self._bufs[name] = torch.empty(max(int(numel), 4), device=self.device, dtype=dtype)
             if self.side_stream is not None:
                 t.record_stream(self.side_stream)
@@ -345,7 +242,7 @@ class ForwardPlan:
                 if mode == 'xcd' or (mode == 'auto' and not pipe):
                     out = hip.lstm_recurrence_xcd(gates, self._packed_whh16(w_hh), self.cell_ws, self.h_out, ws, self._seq_flags)
                     if not capturing:          # (a captured graph holds the launch, not the host-side read-back of its status word)
-                        self._host(lambda: self._seq_status_readback(ws))
+                        self._host(lambda: self._seq_launched(ws))
                     return out
                 return hip.lstm_recurrence_frames16(gates, self._packed_whh16(w_hh), self.cell_ws, self.h_out, ws)
         packed_hh = self._packed_whh(w_hh)
@@ -361,68 +258,33 @@ class ForwardPlan:
                 if e.code != hip.HIP_ERROR_COOPERATIVE_LAUNCH_TOO_LARGE:
                     raise
                 self.lstm_seq_mode = '0'
-                self._tapes.clear()
-                self._mutations += 1          # a tape being recorded right now holds the refused launch: it must not be kept
+                self.tapes.invalidate()       # a tape being recorded right now holds the refused launch: it must not be kept
                 return hip.lstm_recurrence_packed(gates, packed_hh, self.cell_ws, self.h_out)
-            self._host(lambda: self._seq_status_readback(ws))
+            self._host(lambda: self._seq_launched(ws))
             return out
         return hip.lstm_recurrence_packed(gates, packed_hh, self.cell_ws, self.h_out)
 
-    def _seq_status_readback(self, ws):
-        """Behind every one-launch recurrence: its status word travels to pinned host memory, stream-ordered and without a host
-        synchronisation; `check_seq` looks at it once the copy has landed (ADVICE r3 / VERDICT r3 next 6: the word used to be read by
-        nobody, and a grid that lost its compute units to another process returned NaN logits without an error)."""
-        # One pinned word PER LAUNCH (a ring): a caller may enqueue many forwards before anything is looked at, and the next launch
-        # clears the device-side word -- a single host word would let a later, healthy forward overwrite an earlier one's timeout.
-        if self._seq_host is None:
-            self._seq_host = torch.zeros(self._SEQ_RING, dtype=torch.int32).pin_memory()
-            self._seq_pending = collections.deque()
-        with self._seq_lock:
-            if len(self._seq_pending) >= self._SEQ_RING:      # the slot about to be re-used still holds an unread word: read it first
-                ev, slot = self._seq_pending.popleft()
-                ev.synchronize()
-                self._seq_note(slot)
-            slot = self._seq_slot
-            self._seq_outcome.pop(slot, None)                 # (a new launch takes the slot: its old verdict is history)
-            self._seq_slot = (slot + 1) % self._SEQ_RING
-            self._seq_host[slot: slot + 1].copy_(ws.view(torch.int32)[:1], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.device))
-            self._seq_pending.append((ev, slot))
-            self._seq_last = (ev, slot)
-
-    _SEQ_RING = 256
-
-    def _seq_note(self, slot):
-        """The verdict of the launch behind ring slot ``slot`` (its status copy has landed): latched for the next forward
-        (``_seq_failed``) AND remembered per slot, so that the handle of exactly that forward still raises from its ``result()`` when
-        ``check_seq`` got to the word first (it used to return NaN logits silently then)."""
-        failed = int(self._seq_host[slot]) != 0
-        self._seq_outcome[slot] = failed
-        self._seq_failed |= failed
+    def _seq_launched(self, ws):
+        """Host step behind every one-launch recurrence (recorded into a tape with it): its status word sets out for the ring."""
+        self._seq_last = self.seq_status.launched(ws, self.device)
 
     def _demote(self):
-        """After a resident recurrence reported a timeout: one launch per frame from now on, in the SAME arithmetic as the form that failed."""
+        """After a resident recurrence reported a timeout: one launch per frame from now on, in the SAME arithmetic as the form that failed.
+        May run on the thread that reads a result while another one records a tape through this plan: that tape holds the resident launch
+        and the tape key does not hold ``lstm_seq_mode``, so it must not be kept either."""
         self.lstm_seq_mode = '0' if self.lstm_seq_mode == '1' else 'frames'
-        self._tapes.clear()
+        self.tapes.invalidate()
+
+    def seq_pending(self):
+        """Whether a one-launch recurrence enqueued through this plan still awaits a look at its status word."""
+        return bool(self.seq_status.pending)
 
     def check_seq(self, wait=False):
         """Raise if a one-launch recurrence enqueued through this plan timed out (that forward's logits hold NaN rows); the
         one-launch form is switched off for this plan then, so the caller's retry runs the per-frame launches.  ``wait``: block until
         that launch has finished (tests, `ASRModel.check`); otherwise only a finished launch is looked at -- called at the start of
         every forward, so a failure surfaces at the next call at the latest."""
-        pending = self._seq_pending
-        with self._seq_lock:
-            while pending:
-                ev, slot = pending[0]
-                if wait:
-                    ev.synchronize()
-                elif not ev.query():
-                    break
-                pending.popleft()
-                self._seq_note(slot)
-            failed, self._seq_failed = self._seq_failed, False
-        if failed:
+        if self.seq_status.poll(wait):
             self._demote()
             raise hip.HipError('the one-launch LSTM recurrence of an EARLIER forward timed out waiting for its peer workgroups (the grid was '
                                'not co-resident: compute units taken by another process or stream); that forward\'s logits are invalid. '
@@ -431,17 +293,7 @@ class ForwardPlan:
     def check_seq_slot(self, ev, slot):
         """Wait for ONE one-launch recurrence (the status copy behind it) and raise if it timed out: what ``PendingLogits.result()``
         does for the forward it belongs to."""
-        ev.synchronize()
-        with self._seq_lock:
-            try:
-                self._seq_pending.remove((ev, slot))          # reported here, not again at the next forward
-                failed = int(self._seq_host[slot]) != 0
-            except ValueError:
-                # check_seq (the next forward's poll) or the ring wrap has consumed the word already: its verdict was recorded per slot
-                failed = bool(self._seq_outcome.pop(slot, False))
-                if failed:
-                    self._seq_failed = False                  # reported here, by the forward it belongs to
-        if failed:
+        if self.seq_status.verdict(ev, slot):
             self._demote()
             raise hip.HipError('the one-launch LSTM recurrence of THIS forward timed out waiting for its peer workgroups (the grid was not '
                                'co-resident: compute units taken by another process or stream); its logits are invalid. The plan now '
@@ -460,7 +312,7 @@ class ForwardPlan:
         """Called before the plan is dropped: later allocations on the current stream may re-use its memory."""
         self.wait_tails()
         self._graphs.clear()
-        self._tapes.clear()
+        self.tapes.invalidate()
         self._bufs.clear()
         self.side_stream = None                     # (streams.py remembers it for the main stream: a plan built again gets the same one)
 
@@ -520,75 +372,13 @@ class ForwardPlan:
                 built.record_stream(self.side_stream)
             hit = (weakref.ref(param), param._version, built)
             self._packed[key] = hit
-            self._tapes.clear()
-            self._mutations += 1
+            self.tapes.invalidate()
         return hit[2]
 
     def _packed_weights(self, layer, scheme, row_tile=128):
         """Split/re-laid-out copy of a downsample conv's weights."""
         w = layer.conv.weight
         return self._cached(w, (scheme, row_tile, layer.strides), lambda: hip.pack_dense_weights(w.detach(), layer.strides, scheme, row_tile))
-
-    def _row_tile(self, c_out, frames_out, allow_64=True):
-        """Rows per workgroup of the image-path GEMM: 128, or 160 where that means less work in whole rounds of workgroups
-        (a tile's cost is proportional to its rows; 256 CUs run one workgroup each).  At the benchmark shape: 160 for
-        C_out = 800 (5 full row tiles instead of 7 with the last a quarter full) and 1200 (512 workgroups instead of 640)."""
-        n_nt = (hip.round_up4(frames_out) + 255) // 256
-
-        def cost(rows):
-            wgs = -(-c_out // rows) * n_nt * self.batch
-            return -(-wgs // 256) * rows
-        rows = 160 if cost(160) < cost(128) else 128
-        # smaller tiles where a small batch leaves CUs without a workgroup (8 utterances: 128 or 80 workgroups for convs 2 and 3).  A
-        # smaller tile does less per operand byte staged, so it has to win by a margin: 96 rows (round 4: 13 x 16 = 208 workgroups in ONE
-        # round for conv 3 at 16 utterances) by a tenth, 64 rows by a quarter (measured +4 % at 8 utterances, nothing to gain at 32)
-        score = float(cost(rows))
-        if allow_64:
-            for r, margin in ((96, 1.1), (64, 1.25)):
-                if margin * cost(r) < score:
-                    rows, score = r, margin * cost(r)
-        return rows
-
-    def _bf16_tile(self, c_out, frames_out, pipe=False):
-        """(rows, frames) per workgroup of the one-term bf16 GEMM: rows 128 / 160, frames 256 / 512 (results are bit-identical, the choice
-        is speed only).  That flavour is bound by LDS reads; a 512-frame tile re-uses a weight fragment 8 times instead of 4 and runs
-        its K-steps ~10 % faster per unit of work (measured at 32 x 1600: conv 2 312 -> 283 us, conv 3 237 -> 213) -- where the frames
-        and the workgroup count still fill whole tiles and rounds (conv 1, 1600 frames = 3.1 tiles of 512: 357 -> 362).  Cost = rounds
-        of 256 workgroups x tile area x that factor.  In a PIPELINED forward the 256-frame tiles stay: the wide tiles' workgroups (237-245
-        registers, twice as long-lived) leave the per-frame launches of the previous batch's LSTM tail waiting for a compute unit --
-        dense convs 0.983 -> 0.924 ms per forward but 9 620 -> 9 190 utterances/s (three alternating same-box runs each)."""
-        forced = os.environ.get('NBASR_BF16_FTILE')
-        best = None
-        for rows in (128, 160):
-            for ftile in ((int(forced),) if forced else (256,) if pipe else (256, 512)):
-                wgs = -(-c_out // rows) * -(-hip.row_pitch(frames_out, torch.bfloat16) // ftile) * self.batch
-                cost = -(-wgs // 256) * rows * ftile * (0.9 if ftile == 512 else 1.0)
-                if best is None or cost < best[0]:
-                    best = (cost, rows, ftile)
-        return best[1], best[2]
-
-    def _dense_tile(self, layer, frames_out):
-        """(row tile, frame tile) of the image-path fp16 GEMM for this launch.  Every tiling computes the same sums in the same order
-        (results are bit-identical), so the choice is speed only: `_row_tile`'s whole-rounds model, overruled by the measured table
-        (dense_tile_table.json: every tiling at 4 ... 64 utterances x 1000 frames) where that knows the shape and a tiling beat the
-        model's choice by more than 3 % -- 128-frame tiles and 64-row tiles at small batches (one round of workgroups: conv 3 at 8
-        utterances 185 -> 168 us), 64-row tiles for conv 0 at every batch (two workgroups per CU: its ten K-steps are mostly prologue
-        and epilogue)."""
-        conv = layer.conv
-        rows = self._row_tile(conv.out_channels, frames_out)
-        best = (rows, 256)
-        for (c_in, c_out, stride, t_ref), by_batch in _DENSE_TILES.items():
-            if (c_in, c_out, stride) != (conv.in_channels, conv.out_channels, layer.strides) or not 0.75 * t_ref <= frames_out <= 1.34 * t_ref:
-                continue
-            b_ref = min(by_batch, key=lambda b: abs(math.log2(max(self.batch, 1) / b)))
-            if not 0.7 * b_ref <= self.batch <= 1.42 * b_ref:
-                break
-            row = by_batch[b_ref]
-            cand = min(row, key=row.get)
-            if row[cand] < 0.97 * row.get(best, float('inf')):
-                best = cand
-            break
-        return best
 
     def _packed_linear(self, linear):
         """Packed (fp16 split) copy of an nn.Linear-like weight (c_out, c_in), rebuilt whenever the parameter changes."""
@@ -634,36 +424,6 @@ class ForwardPlan:
         """Workspace for the statistics partials a dense convolution emits from its epilogue (one row pair per 16 channels)."""
         n = hip.dense_stats_part_floats(self.batch, c_out, ld_out)
         return self._buf('dense_part', n)[:n]
-
-    def _gc_variant(self, view, node=None, ln0=None, stats=None, n_inputs=0):
-        """Kernel variant of the fp32 grouped-conv node op for this launch (speed only: every variant computes the same sums in the
-        same order, results are bit-identical).  NBASR_GC_F32_VARIANT=<int> forces one (diagnostics; needs ld % 8 == 0 for the
-        8-frame variants; the output-split ones are never forced onto a statistics launch, which they do not have).
-
-        Default: looked up in gc_variant_table.json, which tools/make_gc_variant_table.py derives from same-process A/B timings of
-        the variants {default, output split, pipelined buffer loads, both, LDS ring, persistent LDS ring} per (taps, dilation,
-        channels per group, flavour, size class) on an MI355X (tools/ubench/ab_gc_variants.py, profiles/r03_gc_variants/)."""
-        forced = os.environ.get('NBASR_GC_F32_VARIANT')
-        if forced is not None:
-            v = int(forced)
-            return (v & ~hip.GC_OSPLIT if v & hip.GC_PIPE else 0) if (v & hip.GC_OSPLIT and (stats is not None or node is None)) else v
-        if node is None or not self.gc_table:
-            return 0
-        op = node.op
-        groups = getattr(op, 'groups', 0)
-        if not groups:
-            return 0
-        b, c, ld = view.shape
-        waves_per_simd = b * groups * (-(-(ld // 4) // 64)) / 1024.0
-        on_x = ln0 is not None and n_inputs == 1
-        has_skips = any(type(br).__name__ == 'Identity' for br in node.branch_ops)
-        flavour = ('lnx+skip' if has_skips else 'lnx') if on_x else ('skip' if has_skips else 'plain')
-        head = f"{op.kernel_size},{op.dilation},{c // groups},"
-        tail = f",{'small' if waves_per_simd < 4.0 else 'large'}{',stats' if stats is not None else ''}"
-        v = self.gc_table.get(head + flavour + tail)
-        if v is None and on_x:                           # (tables older than round 3 have one LayerNorm-on-load class)
-            v = self.gc_table.get(head + 'lnx' + tail)
-        return v or 0
 
     def _view(self, idx, channels, frames, dtype=torch.float32):
         ld = hip.row_pitch(frames, dtype)
@@ -750,8 +510,9 @@ class ForwardPlan:
         """Run a host-side step of the launch sequence now and, while a tape is being recorded, note it for every replay.
         ``produces``: the step returns a freshly allocated tensor whose address later launches take (patched on replay)."""
         out = step()
-        if self._recording is not None:
-            self._recording.append([None, step, out.data_ptr() if produces else None, []])
+        recording = self.tapes.recording
+        if recording is not None:
+            recording.append([None, step, out.data_ptr() if produces else None, []])
         return out
 
     def _to_side_stream(self):
@@ -781,43 +542,6 @@ class ForwardPlan:
             return t
         return self._host(alloc, produces=True)
 
-    _TAPE_ENV = ('NBASR_GC_F32_VARIANT',)       # (NBASR_LSTM_SEQ and the other plan switches are read once, when the plan is built)
-
-    def _tape_key(self, model, x, pipelined, group=None):
-        """Everything the recorded launch sequence depends on; None: this call cannot use a tape."""
-        if getattr(model, '_is_replica', False) or x.numel() == 0:    # DataParallel replica: its weights are fresh tensors every step
-            return None
-        slots, epoch = self._param_slots, _structure_epoch[0]
-        if slots is None or slots[0]() is not model or slots[2] != epoch:
-            found = [(m._parameters, n) for m in model.modules() for n, p in m._parameters.items() if p is not None]
-            slots = self._param_slots = (weakref.ref(model), found, epoch)
-        params = tuple([(d[n].data_ptr(), d[n]._version) for d, n in slots[1]])
-        pipe = bool(pipelined) and model.use_rnn and self._tail_on_side_stream(x.shape[0])
-        slot = -1 if not pipe else (self._turn ^ 1) if (group is None or group[0] == 0) else self._turn      # (a group's first forward rotates the slot)
-        return (x.dtype, tuple(x.shape), x.data_ptr() % 16 == 0, bool(pipelined), slot, group,
-                torch.cuda.current_stream(self.device).cuda_stream, tuple(os.environ.get(k) for k in self._TAPE_ENV),
-                epoch, tuple(map(id, model.model)), params, self._structure_fingerprint(model))
-
-    @staticmethod
-    def _structure_fingerprint(model):
-        """The PLAIN attributes the launch sequence reads on every call and that no registration hook sees:
-        ``node.branch_ops`` is a python list, ``cell.use_norm`` / ``op.dilation`` / ``norm.eps`` / ``model.use_rnn`` are plain
-        attributes -- mutating one after a tape exists must not replay the old sequence."""
-        fp = [model.use_rnn, model.training, getattr(model, 'dropout_rate', 0.0)]
-        for layer in model.model:
-            nodes = getattr(layer, 'nodes', None)
-            if nodes is not None:
-                fp.append(layer.use_norm)
-                fp.append(layer.norm_layer.eps if layer.use_norm else None)
-                for node in nodes:
-                    op = node.op
-                    fp.append((type(op), getattr(op, 'kernel_size', 0), getattr(op, 'dilation', 0), getattr(op, 'groups', 0),
-                               tuple(map(type, node.branch_ops))))
-            else:
-                fp.append((type(layer), getattr(layer, 'eps', None), getattr(layer, 'kernel_size', 0), getattr(layer, 'strides', 0),
-                           getattr(layer, 'groups', 0), getattr(layer, 'p', None)))
-        return tuple(fp)
-
     def run(self, model, x, taps=None, pipelined=False, _capturing=False, group=None):
         """``_enqueue`` + the hand-over of a one-launch recurrence's status slot to the handle a pipelined forward returns.
         ``group`` = (g, n): this pipelined forward is the g-th of a TAIL GROUP of n forwards of the same shape enqueued back to back
@@ -835,7 +559,7 @@ class ForwardPlan:
         a ``PendingLogits`` is returned."""
         if x.device != self.device:
             raise hip.HipError(f'input on {x.device}, plan on {self.device}')
-        if not _capturing and self._seq_pending and not torch.cuda.is_current_stream_capturing():
+        if not _capturing and self.seq_status.pending and not torch.cuda.is_current_stream_capturing():
             self.check_seq()                           # (an event query is not a capturable operation)
         wdtype = model.model[0].conv.weight.dtype          # (not model.parameters(): a DataParallel replica has none)
         if x.dtype != wdtype:
@@ -846,37 +570,10 @@ class ForwardPlan:
         x = x.detach().contiguous()
         group = self._group_or_none(model, x, taps, pipelined, _capturing, group)
         from . import walk
-        body = lambda m, xx, tp, pl, cp: walk.run(self, m, xx, tp, pl, cp, group)          # noqa: E731
         key = None
         if self.tape_mode and taps is None and not _capturing and self.timer is None:
-            key = self._tape_key(model, x, pipelined, group)
-        if key is None:
-            return body(model, x, taps, pipelined, _capturing)
-        tape = self._tapes.get(key)
-        if tape is not None:
-            self.tape_replays += 1
-            return tape.replay(self, x)
-        if len(self._tape_seen) > 256:
-            self._tape_seen.clear()
-        seen = self._tape_seen[key] = self._tape_seen.get(key, 0) + 1
-        if seen < 2:
-            # first sight of this key: workspaces may grow and derived weights may be built -- not a sequence worth keeping
-            return body(model, x, taps, pipelined, _capturing)
-        entries, before = [], self._mutations
-        self._recording = entries
-        hip.start_tape(entries)
-        try:
-            out = body(model, x, taps, pipelined, _capturing)
-        finally:
-            hip.stop_tape()
-            self._recording = None
-        if self._mutations == before:
-            if len(self._tapes) >= 48:               # (a tail group of 8 on two slots: 16 tapes of one shape)
-                self._tapes.clear()
-            self._tapes[key] = LaunchTape(entries, x.data_ptr(), bool(pipelined),
-                                          bool(pipelined) and model.use_rnn and self._tail_on_side_stream(x.shape[0]), group)
-        self._tape_logits = None
-        return out
+            key = tape.tape_key(self, model, x, pipelined, group)
+        return self.tapes.run(self, key, model, x, pipelined, group, lambda: walk.run(self, model, x, taps, pipelined, _capturing, group))
 
     def _group_or_none(self, model, x, taps, pipelined, capturing, group):
         """The tail group this forward can really run in: fp32, a pipelined tail on the side stream, the fp16-pair per-frame recurrence
@@ -972,7 +669,7 @@ class PlanPool:
         device = torch.device(device)
         with self._lock:
             for plan in self._idle.get(device.index, ()):
-                if plan._seq_pending:
+                if plan.seq_pending():
                     plan.check_seq()
 
     def values(self):

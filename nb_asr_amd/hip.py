@@ -158,7 +158,7 @@ _tls = threading.local()
 
 
 class _TapingLibrary:
-    """Stand-in for the loaded library while a ``ForwardPlan`` records a launch tape (executor.LaunchTape): every entry
+    """Stand-in for the loaded library while a ``ForwardPlan`` records a launch tape (tape.LaunchTape): every entry
     point that takes a stream -- i.e. enqueues work -- is executed AND appended to ``entries`` as ``[function, [args]]``;
     host-only queries (sizes, error text, version) pass straight through."""
 

@@ -1,6 +1,7 @@
 """The launch sequence of one forward: a walk over ``model.model`` that calls one step per layer kind.
 
-``executor.ForwardPlan`` owns what outlives a call -- workspaces, derived weight copies, tile choices, the recurrence, tapes, graphs.  A
+``executor.ForwardPlan`` owns what outlives a call -- workspaces, derived weight copies, the recurrence, tapes, graphs; the tile and kernel-variant
+choices are the free functions of ``tiles.py``.  A
 ``Walk`` is what ONE forward knows about the activation it is carrying: where it lives, whether a LayerNorm is still pending on it, what
 by-product the last producer left (a range bound or an operand image from a LayerNorm, statistics partials from a dense convolution), which
 block it is in, and whether the tail has moved to the side stream.  It dies with the call, so nothing of an aborted forward reaches the next one.
@@ -13,7 +14,7 @@ before it hands a closure to ``plan._timed``: nothing a closure sees is re-bound
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, tiles
 from .executor import PendingLogits, node_into
 from .ops import PadConvRelu, Linear, Identity
 
@@ -280,7 +281,7 @@ class WalkF32(Walk):
         return param.detach()
 
     def gc_variant(self, view, node, ln0, stats, n_inputs):
-        return self.plan._gc_variant(view, node, ln0, stats, n_inputs)
+        return tiles.gc_variant(tiles._GC_TABLE, view.shape, node, ln0, stats, n_inputs)
 
     def defers(self, nxt, after):
         # the LSTM's input projection pre-splits its operand in a streaming pass that applies a pending LayerNorm while loading
@@ -308,7 +309,7 @@ class WalkF32(Walk):
             # pass over the input, then the same DMA-only GEMM as convs 1-3
             b, c, ld = src.shape
             image = plan._buf('input_image', max(hip.load_library().nbasr_split_image_bytes(b, c, ld), 16), torch.uint8)
-            rows, ftile = plan._dense_tile(layer, t_out)
+            rows, ftile = tiles.dense_tile(plan.batch, conv.in_channels, conv.out_channels, layer.strides, t_out)
             plan.dense_row_tiles[blk], plan.dense_frame_tiles[blk] = rows, ftile
             plan.dense_schemes[blk] = 'f16x2-image'
             w16 = plan._packed_weights(layer, 'f16x2', rows)
@@ -320,7 +321,7 @@ class WalkF32(Walk):
             image, bound = self.image
             plan.dense_schemes[blk] = 'f16x2-image'
             b, c, ld = src.shape
-            rows, ftile = plan._dense_tile(layer, (frames + layer.strides - 1) // layer.strides)
+            rows, ftile = tiles.dense_tile(plan.batch, conv.in_channels, conv.out_channels, layer.strides, (frames + layer.strides - 1) // layer.strides)
             plan.dense_row_tiles[blk], plan.dense_frame_tiles[blk] = rows, ftile
             part = partials()
             w16 = plan._packed_weights(layer, 'f16x2', rows)
@@ -445,7 +446,7 @@ class WalkBf16(Walk):
         if self.pending is not None:
             raise RuntimeError('a dense convolution cannot take a deferred LayerNorm in the bf16 path')
         image = self.image if self.image is not None else self.image_of()
-        rows, ftile = plan._bf16_tile(conv.out_channels, t_out, self.pipe)
+        rows, ftile = tiles.bf16_tile(plan.batch, conv.out_channels, t_out, self.pipe)
         plan.dense_row_tiles[blk], plan.dense_frame_tiles[blk] = rows, ftile
         w = conv.weight
         packed = plan._cached(w, ('bf16', rows, layer.strides), lambda: hip.pack_dense_weights_bf16(plan._f32(w), layer.strides, rows))

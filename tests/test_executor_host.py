@@ -8,7 +8,7 @@ import torch.nn as nn
 
 import cases
 import nb_asr_amd as nb
-from nb_asr_amd import executor, hip
+from nb_asr_amd import executor, hip, tiles
 
 
 class _Ptr:
@@ -80,9 +80,9 @@ def test_launch_tape_reports_a_failing_call(monkeypatch):
 
 
 def test_variant_table_is_complete_and_well_formed():
-    table = json.loads(pathlib.Path(executor.__file__).with_name('gc_variant_table.json').read_text())
+    table = json.loads(pathlib.Path(tiles.__file__).with_name('gc_variant_table.json').read_text())
     # (taps, dilation) x channels per group x {4 flavours + 2 statistics flavours} x {small, large}
-    assert table == executor._GC_TABLE and len(table) == 4 * 4 * (4 + 2) * 2
+    assert table == tiles._GC_TABLE and len(table) == 4 * 4 * (4 + 2) * 2
     no_split = (0, hip.GC_PIPE, hip.GC_RING)
     for key, v in table.items():
         parts = key.split(',')
@@ -100,7 +100,7 @@ def test_variant_table_is_complete_and_well_formed():
 
 
 def test_variant_choice_per_launch(monkeypatch):
-    plan = executor.ForwardPlan('cpu')
+    pick = lambda view, *a: tiles.gc_variant(tiles._GC_TABLE, view.shape, *a)          # noqa: E731
     model = nb.get_model(cases.ARCH_D, use_rnn=True, dropout_rate=0.0)
     cell = next(m for m in model.model if type(m).__name__ == 'SearchCell' and m.filters == 1200)
     node = cell.nodes[0]                                           # conv7d2 or similar with 12 channels per group
@@ -112,18 +112,18 @@ def test_variant_choice_per_launch(monkeypatch):
     has_skip = any(type(br).__name__ == 'Identity' for br in node.branch_ops)
     flavour = 'skip' if has_skip else 'plain'
     for b, frames, size in ((64, 250, 'large'), (8, 250, 'small'), (2, 40, 'small')):
-        want = executor._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{flavour},{size}']
-        assert plan._gc_variant(view(b, frames), node, None, None, 2) == want
-        assert plan._gc_variant(view(b, frames), node, None, ('stats',), 2) == executor._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{flavour},{size},stats']
+        want = tiles._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{flavour},{size}']
+        assert pick(view(b, frames), node, None, None, 2) == want
+        assert pick(view(b, frames), node, None, ('stats',), 2) == tiles._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{flavour},{size},stats']
     ln0 = ('stats', 'gamma', 'beta')
-    assert plan._gc_variant(view(64, 250), node, ln0, None, 1) == executor._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{"lnx+skip" if has_skip else "lnx"},large']
-    assert plan._gc_variant(view(64, 250), None) == 0                                   # no node: the default kernel
+    assert pick(view(64, 250), node, ln0, None, 1) == tiles._GC_TABLE[f'{op.kernel_size},{op.dilation},{cg},{"lnx+skip" if has_skip else "lnx"},large']
+    assert pick(view(64, 250), None) == 0                                   # no node: the default kernel
     monkeypatch.setenv('NBASR_GC_F32_VARIANT', str(hip.GC_PIPE | hip.GC_OSPLIT))
-    assert plan._gc_variant(view(64, 250), node, None, None, 2) == hip.GC_PIPE | hip.GC_OSPLIT
-    assert plan._gc_variant(view(64, 250), node, None, ('stats',), 2) == hip.GC_PIPE       # the split is never forced onto a statistics launch
+    assert pick(view(64, 250), node, None, None, 2) == hip.GC_PIPE | hip.GC_OSPLIT
+    assert pick(view(64, 250), node, None, ('stats',), 2) == hip.GC_PIPE       # the split is never forced onto a statistics launch
     monkeypatch.delenv('NBASR_GC_F32_VARIANT')
     monkeypatch.setenv('NBASR_GC_F32_VARIANT', '0')                                     # the default kernel everywhere
-    assert executor.ForwardPlan('cpu')._gc_variant(view(64, 250), node, None, None, 2) == 0
+    assert pick(view(64, 250), node, None, None, 2) == 0
 
 
 def test_structure_epoch_counts_registrations():
@@ -173,3 +173,119 @@ def test_dense_mode_is_read_and_validated_at_call_time(monkeypatch):
             hip.dense_mode()
         with pytest.raises(ValueError, match='NBASR_DENSE_MODE must be auto, bf16x3 or f32'):
             executor.ForwardPlan('cpu')
+
+
+class _Model:
+    use_rnn = False
+
+
+@pytest.mark.parametrize('mutation', ['demote', 'buf', 'cached', None])
+def test_a_mutation_while_recording_drops_the_tape(mutation):
+    """One ``invalidate()`` for everything that makes a recorded sequence stale.  A plan demoted halfway through a recording -- by
+    ``PendingLogits.result()`` on another thread, say -- used to clear the stored tapes only: the tape being recorded was stored after the
+    clear and replayed the resident launch the plan had just been demoted from (the tape key does not hold ``lstm_seq_mode``)."""
+    plan = executor.ForwardPlan('cpu')
+    tapes, param = plan.tapes, torch.zeros(3)
+    plan._cached(param, 'copy', param.clone)
+    calls = []
+
+    def body():
+        calls.append(tapes.recording is not None)
+        if len(calls) == 2:                               # second sight of the key: this call is being recorded
+            if mutation == 'demote':
+                plan._demote()
+            elif mutation == 'buf':
+                plan._buf('grown', 1000)
+            elif mutation == 'cached':
+                param.add_(1.0)                           # (version counter: the derived copy is rebuilt)
+                plan._cached(param, 'copy', param.clone)
+        return 'out'
+    run = lambda: tapes.run(plan, 'key', _Model(), _Ptr(0x1000), False, None, body)      # noqa: E731
+    assert run() == 'out' and calls == [False] and not tapes.tapes                      # first sight: python, nothing kept
+    assert run() == 'out' and calls == [False, True] and tapes.recording is None
+    if mutation is None:                                  # the control: an undisturbed recording is kept and replayed
+        assert list(tapes.tapes) == ['key'] and tapes.replays == 0
+        plan._tape_logits = 'replayed'
+        assert run() == 'replayed' and len(calls) == 2 and tapes.replays == 1
+        return
+    assert not tapes.tapes                                # no tape is stored for that key
+    assert run() == 'out' and calls == [False, True, True] and tapes.replays == 0       # the next call records again, not replays
+    assert list(tapes.tapes) == ['key']
+    if mutation == 'demote':
+        assert plan.lstm_seq_mode == 'frames'
+
+
+class _Event:
+    def __init__(self, done=True):
+        self.done, self.waited = done, 0
+
+    def query(self):
+        return self.done
+
+    def synchronize(self):
+        self.waited += 1
+        self.done = True
+
+
+class _StandInRing(executor.seq_status.SeqStatusRing):
+    """The ring with a list for the pinned tensor and ``_Event`` for the events: ``launched(word)`` lands ``word`` in its slot at once."""
+
+    def __init__(self):
+        super().__init__()
+        self.host = [0] * self.SIZE
+
+    def _copy(self, word, slot, device):
+        self.host[slot] = word
+        return _Event(done=word != 'in flight')
+
+
+def _plan_with_stand_in_ring():
+    plan = executor.ForwardPlan('cpu')
+    plan.seq_status = _StandInRing()
+    return plan, plan.seq_status
+
+
+def test_status_ring_wraps_and_reads_the_evicted_slot_first():
+    plan, ring = _plan_with_stand_in_ring()
+    first_ev, first_slot = ring.launched(1, None)         # a failed launch nobody looks at ...
+    first_ev.done = False
+    handles = [ring.launched(0, None) for _ in range(ring.SIZE - 1)]
+    assert [slot for _, slot in handles] == list(range(1, ring.SIZE)) and len(ring.pending) == ring.SIZE and first_ev.waited == 0
+    ev, slot = ring.launched(0, None)                     # ... until the ring wraps: its word is read before the slot is taken again
+    assert slot == first_slot == 0 and first_ev.waited == 1 and len(ring.pending) == ring.SIZE and ring.host[0] == 0
+    assert plan.seq_pending()
+    with pytest.raises(hip.HipError, match='EARLIER forward'):
+        plan.check_seq()
+    assert plan.lstm_seq_mode == 'frames' and not plan.seq_pending()
+    plan.check_seq(wait=True)                             # reported once
+    plan.check_seq_slot(ev, slot)                         # the slot's new launch is healthy: the evicted verdict is history
+
+
+def test_a_failure_the_poll_consumed_is_still_raised_by_its_own_handle_once():
+    plan, ring = _plan_with_stand_in_ring()
+    ok = ring.launched(0, None)
+    bad = ring.launched(7, None)
+    late = ring.launched('in flight', None)
+    with pytest.raises(hip.HipError, match='EARLIER forward'):
+        plan.check_seq()                                  # the non-waiting poll reads the two finished launches
+    assert list(ring.pending) == [late] and late[0].waited == 0 and plan.lstm_seq_mode == 'frames'
+    with pytest.raises(hip.HipError, match='THIS forward'):
+        plan.check_seq_slot(*bad)
+    plan.check_seq_slot(*ok)
+    plan.check_seq()                                      # not again
+    plan.check_seq_slot(*bad)                             # nor by the handle
+    ring.host[late[1]] = 0
+    plan.check_seq(wait=True)
+    assert late[0].waited == 1 and not plan.seq_pending()
+
+
+def test_a_failure_first_seen_by_its_handle_is_not_reported_again():
+    plan, ring = _plan_with_stand_in_ring()
+    bad = ring.launched(1, None)
+    ok = ring.launched(0, None)
+    with pytest.raises(hip.HipError, match='THIS forward'):
+        plan.check_seq_slot(*bad)
+    assert list(ring.pending) == [ok] and plan.lstm_seq_mode == 'frames'
+    plan.check_seq()
+    plan.check_seq(wait=True)
+    assert not plan.seq_pending()

@@ -135,9 +135,9 @@ def test_keyed_generators_are_platform_stable(known):
 def test_row_tile_rule_counts_rounds_of_workgroups():
     """Image-path GEMM: 160-row tiles exactly where they mean fewer (rows x rounds of 256 workgroups) than 128-row tiles."""
     import types
-    from nb_asr_amd.executor import ForwardPlan
+    from nb_asr_amd import tiles
     plan = types.SimpleNamespace(batch=64)
-    pick = lambda c, t: ForwardPlan._row_tile(plan, c, t)                      # noqa: E731
+    pick = lambda c, t: tiles.row_tile(plan.batch, c, t)                       # noqa: E731
     assert [pick(800, 1000), pick(1000, 500), pick(1200, 250)] == [160, 128, 160]     # the benchmark shape: convs 1 and 3
     plan.batch = 32
     assert [pick(800, 1000), pick(1000, 500), pick(1200, 250)] == [160, 128, 160]
@@ -147,4 +147,4 @@ def test_row_tile_rule_counts_rounds_of_workgroups():
     assert [pick(600, 1000), pick(800, 1000), pick(1000, 500), pick(1200, 250)] == [160, 128, 128, 96]  # (round 4) conv 3: 13 x 16 = 208 workgroups, one round
     plan.batch = 2
     assert [pick(800, 1000), pick(1000, 500), pick(1200, 250)] == [64, 64, 64]        # a single round whatever the tile: the smallest
-    assert ForwardPlan._row_tile(plan, 1200, 250, allow_64=False) == 128               # (the bf16 GEMM has no 64-row instance)
+    assert tiles.row_tile(plan.batch, 1200, 250, allow_64=False) == 128               # (the bf16 GEMM has no 64-row instance)

@@ -283,26 +283,7 @@ def test_dense_scheme_selection():
     assert plan.dense_schemes == {0: 'f16x2-image', 1: 'f16x2-image', 2: 'f16x2-image', 3: 'f16x2-image'}
     assert set(plan.dense_row_tiles) == {0, 1, 2, 3} and set(plan.dense_row_tiles.values()) <= {64, 96, 128, 160}
     assert set(plan.dense_frame_tiles) == {0, 1, 2, 3} and set(plan.dense_frame_tiles.values()) <= {128, 256}
-    assert plan._row_tile(800, 1000) == 64 and plan._row_tile(1200, 250) == 64            # 2 utterances: under one round, so the smallest tiles
-    plan.batch = 64
-    assert plan._row_tile(800, 1000) == 160 and plan._row_tile(1000, 500) == 128 and plan._row_tile(1200, 250) == 160 and plan._row_tile(600, 1000) == 128
-    plan.batch = 8
-    assert plan._row_tile(1000, 500) == 64 and plan._row_tile(1200, 250) == 64 and plan._row_tile(800, 1000) == 128
-    # round 5: the measured table (dense_tile_table.json) overrules the whole-rounds model where it knows the shape: 128-frame tiles for the
-    # stride-2 convs of a small batch, 64-row tiles (two workgroups per CU) for conv 0; shapes it does not know keep the model's choice
-    c0, c2, c3 = model.model[0], [l for l in model.model if getattr(l, 'strides', 0) == 2][0], [l for l in model.model if getattr(l, 'strides', 0) == 2][1]
-    from nb_asr_amd.executor import _DENSE_TILES
-
-    def within_3_percent_of_the_tables_best(layer, frames_out, key):
-        row = _DENSE_TILES[key][plan.batch]
-        return row[plan._dense_tile(layer, frames_out)] <= min(row.values()) / 0.97
-    assert plan._dense_tile(c3, 250) == (64, 128) and plan._dense_tile(c3, 77) == (plan._row_tile(1200, 77), 256)
-    assert within_3_percent_of_the_tables_best(c2, 500, (800, 1000, 2, 500)) and within_3_percent_of_the_tables_best(c0, 1000, (80, 600, 1, 1000))
-    plan.batch = 64
-    assert plan._dense_tile(c0, 1000) == (64, 256) and plan._dense_tile(c2, 500) == (128, 256) and plan._dense_tile(c3, 250) == (160, 256)
-    assert within_3_percent_of_the_tables_best([l for l in model.model if getattr(l, 'strides', 0) == 1 and hasattr(l, 'conv') and l.conv.in_channels == 600][0],
-                                               1000, (600, 800, 1, 1000))
-    plan.batch = 2
+    # (what the choosers pick at 2, 8 and 64 utterances needs no device: tests/test_tiles_host.py)
     os.environ['NBASR_DENSE_MODE'] = 'bf16x3'
     try:
         model._plans.clear()
@@ -825,19 +806,18 @@ def test_exact_fp32_mode_on_the_noisy_cases(model_fx, case):
 def test_node_kernel_variants_are_chosen_and_change_nothing(monkeypatch):
     """The executor picks the fp32 node kernel's variant per launch from the measured table (output split and / or pipelined
     buffer loads, LDS ring); NBASR_GC_F32_VARIANT=0 keeps the default kernel everywhere.  Same sums in the same order: bit-identical logits."""
-    from nb_asr_amd import hip
-    from nb_asr_amd.executor import ForwardPlan
+    from nb_asr_amd import hip, tiles
     monkeypatch.setenv('NBASR_CELL_FUSION', '0')            # (with fused cells -- the default -- a conv-only cell is one launch, not three node launches)
     m = build(cases.ARCH_D, True, 'lively')
     x = keyed_input(3, 210, seed=8).to(DEV)
     chosen = []
-    original = ForwardPlan._gc_variant
+    original = tiles.gc_variant
 
-    def spy(self, *a, **k):
-        v = original(self, *a, **k)
-        chosen.append((v, a[3] is not None if len(a) > 3 else False))
+    def spy(table, shape, *a, **k):
+        v = original(table, shape, *a, **k)
+        chosen.append((v, a[2] is not None if len(a) > 2 else False))
         return v
-    monkeypatch.setattr(ForwardPlan, '_gc_variant', spy)
+    monkeypatch.setattr(tiles, 'gc_variant', spy)
     with torch.no_grad():
         y1 = m(x).clone()
     picked = {v for v, _ in chosen}

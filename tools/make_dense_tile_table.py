@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/ubench/dense_tiles.py output (one or more batches) -> nb_asr_amd/dense_tile_table.json: measured us per launch of the image-path dense
-convolution for every (row tile, frame tile), keyed by "c_in,c_out,stride,frames_out" and batch.  executor._dense_tile reads it.
+convolution for every (row tile, frame tile), keyed by "c_in,c_out,stride,frames_out" and batch.  tiles.dense_tile reads it.
 
 usage: python tools/make_dense_tile_table.py gpurun_out/.../dense_tiles.txt > nb_asr_amd/dense_tile_table.json"""
 import collections

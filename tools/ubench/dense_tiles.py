@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the image-path dense convolution (fp16 split) at every (row tile, frame tile) for the four downsample convs at one batch size:
-the table behind executor._dense_tile.  Outputs of every tiling are asserted bit-equal (the K order of an output does not depend on it).
+the table behind tiles.dense_tile.  Outputs of every tiling are asserted bit-equal (the K order of an output does not depend on it).
 
 usage: python tools/ubench/dense_tiles.py [--batch 8] [--frames 1000] [--iters 15]
 """
