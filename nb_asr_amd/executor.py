@@ -42,7 +42,7 @@ def node_into(node, inputs, frames, out, ln0=None, stats=None, linear_ctx=None, 
     matrix cores (packed weights, pre-split activations); None = the exact-fp32 MFMA GEMM.
     ``copies``: the ForwardPlan of a forward on bf16 rows.  Its parameters are bfloat16 tensors while the kernels read fp32 weights, so
     they come from the plan's derived copies: fp32 values, the [group][ci][tap][co] order for a GC_WPERM variant, the one-term bf16
-    operand image of a `linear` op (one bf16 MFMA per product, gemm_pointwise_bf16.hip)."""
+    operand image of a `linear` op (one bf16 MFMA per product, gemm_pointwise.hip)."""
     from .ops import PadConvRelu, Linear, Zero, Identity
     f32 = copies._f32 if copies is not None else torch.Tensor.detach
     if len(inputs) != len(node.branch_ops):

@@ -285,7 +285,7 @@ class WalkF32(Walk):
 
     def defers(self, nxt, after):
         # the LSTM's input projection pre-splits its operand in a streaming pass that applies a pending LayerNorm while loading
-        # (gemm_pointwise_split.hip), and it runs on the MAIN stream in both modes: the cell in front of it defers its LayerNorm like a
+        # (gemm_pointwise.hip, PwF16x2), and it runs on the MAIN stream in both modes: the cell in front of it defers its LayerNorm like a
         # cell in front of a grouped conv does -- no materialised copy of the encoder output
         return cheap_consumer(nxt) or (isinstance(after, nn.LSTM) and self.plan.linear_mode == 'f16x2')
 
