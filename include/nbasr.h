@@ -431,6 +431,31 @@ int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths,
 int nbasr_ctc_beam_stream_finish(const void* state, int* beams, float* scores, int* beam_lens, int ld_beams, int batch, int beam_width,
                                  int pool_nodes, nbasr_stream_t stream);
 
+/* ---- per-token time steps (ctcdecode's fourth output; nb_asr_amd/ctc.py beam_decode(return_timesteps=True), BeamSearchStream(
+ * timesteps=True)) -- the same searches, bit for bit, that also report for every token the frame at which its class had the largest
+ * log-probability among the frames that extended into its node (ctcdecode's PathTrie::get_path_trie; the rule is DESIGN.md 9 "Beam
+ * decode"): a new prefix's node starts at the frame that created it; while the prefix and its parent string are both live, a frame with a
+ * strictly larger (unpruned) log-probability of the prefix's last class moves the node there.  Frames are the utterance's own, 0-based.
+ * nbasr_ctc_beam_search_timed: nbasr_ctc_beam_search plus timesteps(batch, beam_width, frames) int32, 0 beyond beam_lens; ws of
+ *   nbasr_ctc_beam_timed_workspace_bytes.
+ * nbasr_ctc_beam_stream_timed_*: the streaming search over a state of its own layout, nbasr_ctc_beam_stream_timed_state_bytes (the pool is
+ *   still last in each record, its nodes are 16 bytes; the record also counts the utterance's frames over all steps since the init, an
+ *   ended utterance stops counting); ws as nbasr_ctc_beam_stream_workspace_bytes.  A state belongs to the family that initialised it.
+ *   _step also gives committed_frames / partial_frames(batch, pool_nodes), aligned with committed / partial; a committed token's frame is
+ *   final.  _finish also gives timesteps(batch, beam_width, ld_beams), aligned with the suffixes. */
+size_t nbasr_ctc_beam_timed_workspace_bytes(int batch, int frames, int classes, int beam_width);
+int nbasr_ctc_beam_search_timed(const float* log_probs, const int* lengths, void* ws, int* beams, float* scores, int* timesteps,
+                                int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
+                                nbasr_stream_t stream);
+size_t nbasr_ctc_beam_stream_timed_state_bytes(int batch, int beam_width, int pool_nodes);
+int nbasr_ctc_beam_stream_timed_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_timed_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+                                     int* committed_frames, int* committed_counts, int* partial, int* partial_frames, int* partial_counts,
+                                     int* usage, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
+                                     int pool_nodes, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_timed_finish(const void* state, int* beams, float* scores, int* timesteps, int* beam_lens, int ld_beams,
+                                       int batch, int beam_width, int pool_nodes, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

@@ -16,6 +16,13 @@
 // the trie of ctcdecode provides; a re-created prefix must meet its still-live extensions again), the token strings
 // themselves are (parent node, class) pairs in a per-utterance pool in global memory, walked backwards once at the end.
 // All arithmetic is fp32 with ctcdecode's finite "-infinity" (-FLT_MAX).  The utterances of a batch run on different CUs.
+//
+// Per-token time steps (ctcdecode's fourth output; the TIMED instantiations, nbasr_ctc_beam_*_timed*): every token node carries a
+// record (frame, best) after ctcdecode's PathTrie::get_path_trie -- the frame at which the node's class had the largest log-probability
+// among the frames that extended into it.  A node is created with (t, lp_t[c]); at frame t a live prefix whose parent string is live
+// too moves its own node's record to (t, lp_t[c]) when lp_t[c] is larger (strictly: the earliest frame wins).  The lane of a live
+// prefix keeps `best` in a register, the frame lives in the pool: a timed node is two int2, (parent, class) then (frame, best).  The
+// untimed instantiations compile to the code they were before the flag existed.
 #include "common.h"
 
 #include <cfloat>
@@ -147,11 +154,13 @@ struct BeamLanes {
     unsigned long long p_hash, p_phash;
     unsigned merged;                                // class lane c: bit i set = (live prefix i + class c) is itself a live prefix
     int n_live, n_nodes;
+    float p_best;                                   // TIMED only: `best` of this prefix's own node
 };
 
 __device__ __forceinline__ void beam_lane_reset(BeamLanes& s)
 {
     s.p_b = s.p_nb = s.p_score = NEG; s.p_last = -1; s.p_node = 0; s.p_len = 0; s.p_mp = -1; s.p_hash = 0ull; s.p_phash = ~0ull;
+    s.p_best = NEG;
 }
 
 // class lanes: the extensions that are live prefixes themselves (from p_mp and p_last of the live prefixes)
@@ -167,9 +176,14 @@ __device__ __forceinline__ unsigned merged_mask(int p_mp, int p_last, int n_live
 
 // One frame of the prefix beam search: `lp` = log-probability of class `lane` in this frame (pruned: -FLT_MAX).  New prefixes get
 // pool nodes n_nodes, n_nodes + 1, ... in rank order (at most `width` per frame).  The whole-utterance kernel and the resumable
-// one both run exactly this, so the two cannot drift apart.
-__device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __restrict__ pool, int classes, int width, int blank, int lane)
+// one both run exactly this, so the two cannot drift apart.  TIMED: `t` is the utterance's frame index, pool nodes are NODE_INT2<true> int2
+// wide and carry their (frame, best) record; the owning lane writes a record when it creates a node or improves its own.
+template <bool TIMED> constexpr int NODE_INT2 = TIMED ? 2 : 1;
+
+template <bool TIMED>
+__device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __restrict__ pool, int classes, int width, int blank, int lane, int t)
 {
+    constexpr int NS = NODE_INT2<TIMED>;
     float p_b = st.p_b, p_nb = st.p_nb, p_score = st.p_score;
     int p_last = st.p_last, p_node = st.p_node, p_len = st.p_len, p_mp = st.p_mp;
     unsigned long long p_hash = st.p_hash, p_phash = st.p_phash;
@@ -194,6 +208,13 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
         }
         n_score = log_sum_exp(n_b, n_nb);
         live_key = beam_key(n_score, p_last + 1, width * BEAM_CLASSES + lane);
+    }
+    // ---- TIMED: a live prefix whose parent string is live too was extended into by this frame (whether or not the parent can contribute
+    //      probability, as ctcdecode's get_path_trie runs before log_p): a larger log-probability of its class moves its node's record here
+    float p_best = TIMED ? st.p_best : 0.f;
+    if (TIMED && lane < n_live && p_mp >= 0 && lp_last > NEG && lp_last > p_best) {
+        p_best = lp_last;
+        pool[p_node * NS + 1] = make_int2(t, __float_as_int(lp_last));
     }
 
     // The candidates (live prefix i + class c) are spread over the lanes by ROTATING the per-class values (log-probability,
@@ -254,24 +275,29 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
     const float s_b = __shfl(p_b, src), s_score = __shfl(p_score, src);
     const int s_last = __shfl(p_last, src), s_node = __shfl(p_node, src), s_len = __shfl(p_len, src);
     const unsigned long long s_hash = shfl64(p_hash, src), s_phash = shfl64(p_phash, src);
+    const float s_best = TIMED ? __shfl(p_best, src) : 0.f;
     const float lp_col = __shfl(lpk, mine_valid && !survivor ? col : 0);
     if (mine_valid && survivor) {
         p_b = s_b_new; p_nb = s_nb_new; p_score = s_score_new;
         p_last = s_last; p_node = s_node; p_len = s_len; p_hash = s_hash; p_phash = s_phash;
+        p_best = s_best;
     } else if (mine_valid) {
         const float v = (col == s_last) ? (s_b > NEG ? lp_col + s_b : NEG) : lp_col + s_score;
         p_b = NEG; p_nb = v; p_score = v;
         p_last = col; p_len = s_len + 1; p_phash = s_hash; p_hash = extend_hash(s_hash, col);
         p_node = -1 - s_node;                                       // parent's node, until this prefix gets its own
+        p_best = lp_col;                                            // a new prefix, or a re-created one: a fresh record
     } else {
         p_b = p_nb = p_score = NEG; p_last = -1; p_node = 0; p_len = 0; p_hash = 0ull; p_phash = ~0ull;
+        p_best = NEG;
     }
     // new pool nodes in rank order
     const bool is_new = mine_valid && p_node < 0;
     const unsigned long long new_mask = __ballot(is_new);
     if (is_new) {
         const int id = n_nodes + __popcll(new_mask & ((1ull << lane) - 1ull));
-        pool[id] = make_int2(-1 - p_node, p_last);
+        pool[id * NS] = make_int2(-1 - p_node, p_last);
+        if (TIMED) pool[id * NS + 1] = make_int2(t, __float_as_int(p_best));
         p_node = id;
     }
     n_nodes += __popcll(new_mask);
@@ -287,15 +313,20 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
     st.p_last = p_last; st.p_node = p_node; st.p_len = p_len; st.p_mp = p_mp;
     st.p_hash = p_hash; st.p_phash = p_phash;
     st.merged = merged; st.n_live = n_live; st.n_nodes = n_nodes;
+    if (TIMED) st.p_best = p_best;
 }
 
+// TIMED: timesteps(batch, width, frames) = the frame of every token's record, 0 beyond the beam's length.  (What the timed instantiations
+// take in addition comes last in every kernel's arguments: the untimed ones read theirs where they always did.)
+template <bool TIMED>
 __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ lengths, int2* __restrict__ pool_all, int* __restrict__ beams,
-    float* __restrict__ scores, int* __restrict__ beam_lens, int frames, int classes, int width, int blank)
+    float* __restrict__ scores, int* __restrict__ beam_lens, int frames, int classes, int width, int blank, int* __restrict__ timesteps)
 {
+    constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
     const int len = lengths ? min(max(lengths[b], 0), frames) : frames;
-    int2* __restrict__ pool = pool_all + static_cast<size_t>(b) * (static_cast<size_t>(frames) * width + 1);
+    int2* __restrict__ pool = pool_all + static_cast<size_t>(b) * (static_cast<size_t>(frames) * width + 1) * NS;
     const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
 
     // the empty prefix: P(blank-ending) = 1, hash 0, pool node 0
@@ -310,24 +341,27 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     for (int t = 0; t < len; ++t) {
         const float lp = lp_next;                                                                       // class `lane` of frame t
         if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];  // in flight during this frame
-        beam_frame(st, lp, pool, classes, width, blank, lane);
+        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t);
     }
 
     // results, best first (the selection of the last frame already ordered them; a zero-length utterance has the empty prefix)
     __syncthreads();                                                   // pool entries written by other lanes
     if (lane < width) {
         int* out = beams + (static_cast<size_t>(b) * width + lane) * frames;
+        int* out_t = TIMED ? timesteps + (static_cast<size_t>(b) * width + lane) * frames : nullptr;
         const bool live = lane < st.n_live;
         const int n = live ? st.p_len : 0;
         if (live) {
             int node = st.p_node;
             for (int k = n - 1; k >= 0; --k) {
-                const int2 e = pool[node];
+                const int2 e = pool[node * NS];
                 out[k] = e.y;
+                if (TIMED) out_t[k] = pool[node * NS + 1].x;
                 node = e.x;
             }
         }
         for (int k = n; k < frames; ++k) out[k] = 0;
+        if (TIMED) for (int k = n; k < frames; ++k) out_t[k] = 0;
         scores[static_cast<size_t>(b) * width + lane] = live ? -st.p_score : FLT_MAX;     // ctcdecode returns -log P
         beam_lens[static_cast<size_t>(b) * width + lane] = n;
     }
@@ -343,12 +377,18 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
 // State of one utterance, `beam_stream_record_bytes` bytes at a multiple of 8: a header of 16 ints (n_live, n_nodes, committed
 // tokens, ended), then p_hash[width], p_phash[width] (u64), p_b, p_nb, p_score (f32) and p_last, p_node, p_len, p_mp (i32) per lane,
 // then the pool (pool_nodes int2).  The pool comes last, so a larger pool keeps the layout of the smaller one's prefix.
-enum { BS_N_LIVE = 0, BS_N_NODES = 1, BS_COMMITTED = 2, BS_ENDED = 3, BS_HEADER_INTS = 16 };
+// The timed state (nbasr_ctc_beam_stream_timed_*) is a layout of its own: the header also counts the utterance's frames so far, the
+// lanes end with p_best (f32), and the pool's nodes are two int2 wide -- one wider node rather than a second array, so the pool is
+// still the record's tail.
+enum { BS_N_LIVE = 0, BS_N_NODES = 1, BS_COMMITTED = 2, BS_ENDED = 3, BS_FRAMES = 4, BS_HEADER_INTS = 16 };
 
-__host__ __device__ constexpr size_t beam_stream_lanes_bytes(int width) { return (16 * static_cast<size_t>(width) + 28 * static_cast<size_t>(width) + 7) & ~size_t(7); }
-__host__ __device__ constexpr size_t beam_stream_record_bytes(int width, int pool_nodes)
+__host__ __device__ constexpr size_t beam_stream_lanes_bytes(int width, bool timed = false)
 {
-    return BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width) + static_cast<size_t>(pool_nodes) * sizeof(int2);
+    return (16 * static_cast<size_t>(width) + (timed ? 32 : 28) * static_cast<size_t>(width) + 7) & ~size_t(7);
+}
+__host__ __device__ constexpr size_t beam_stream_record_bytes(int width, int pool_nodes, bool timed = false)
+{
+    return BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width, timed) + static_cast<size_t>(pool_nodes) * (timed ? 2 : 1) * sizeof(int2);
 }
 
 struct BeamStreamRecord {
@@ -356,12 +396,13 @@ struct BeamStreamRecord {
     unsigned long long *hash, *phash;
     float *pb, *pnb, *pscore;
     int *last, *node, *len, *mp;
+    float* best;                                    // timed state only
     int2* pool;
 };
 
-__device__ __forceinline__ BeamStreamRecord beam_stream_record(char* state, int b, int width, int pool_nodes)
+__device__ __forceinline__ BeamStreamRecord beam_stream_record(char* state, int b, int width, int pool_nodes, bool timed = false)
 {
-    char* r = state + static_cast<size_t>(b) * beam_stream_record_bytes(width, pool_nodes);
+    char* r = state + static_cast<size_t>(b) * beam_stream_record_bytes(width, pool_nodes, timed);
     BeamStreamRecord rec;
     rec.hdr = reinterpret_cast<int*>(r);
     rec.hash = reinterpret_cast<unsigned long long*>(r + BS_HEADER_INTS * 4);
@@ -373,27 +414,31 @@ __device__ __forceinline__ BeamStreamRecord beam_stream_record(char* state, int 
     rec.node = rec.last + width;
     rec.len = rec.node + width;
     rec.mp = rec.len + width;
-    rec.pool = reinterpret_cast<int2*>(r + BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width));
+    rec.best = reinterpret_cast<float*>(rec.mp + width);
+    rec.pool = reinterpret_cast<int2*>(r + BS_HEADER_INTS * 4 + beam_stream_lanes_bytes(width, timed));
     return rec;
 }
 
+template <bool TIMED>
 __device__ __forceinline__ void beam_stream_store(const BeamStreamRecord& rec, const BeamLanes& st, int lane, int width)
 {
     if (lane < width) {
         rec.hash[lane] = st.p_hash; rec.phash[lane] = st.p_phash;
         rec.pb[lane] = st.p_b; rec.pnb[lane] = st.p_nb; rec.pscore[lane] = st.p_score;
         rec.last[lane] = st.p_last; rec.node[lane] = st.p_node; rec.len[lane] = st.p_len; rec.mp[lane] = st.p_mp;
+        if (TIMED) rec.best[lane] = st.p_best;
     }
 }
 
+template <bool TIMED>
 __global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restrict__ state, int width, int pool_nodes)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes);
+    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes, TIMED);
     BeamLanes st;
     beam_lane_reset(st);
     if (lane == 0) st.p_b = st.p_score = 0.f;                         // the empty prefix: P(blank-ending) = 1, hash 0, node 0
-    beam_stream_store(rec, st, lane, width);
+    beam_stream_store<TIMED>(rec, st, lane, width);
     if (lane < BS_HEADER_INTS) rec.hdr[lane] = lane == BS_N_LIVE || lane == BS_N_NODES ? 1 : 0;
     if (lane == 0) rec.pool[0] = make_int2(-1, -1);
 }
@@ -401,14 +446,20 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restri
 // One chunk of frames for every utterance (one wavefront each).  `ids`: pool_nodes ints of scratch per utterance (the renumbering).
 // committed / partial: rows of pool_nodes ints (the host keeps usage + width * n + 1 <= pool_nodes, which bounds both counts).
 // usage[b] = pool nodes in use afterwards, or -1: the chunk could overflow the pool, nothing was done.
+// TIMED: committed_frames / partial_frames, rows like committed / partial, hold each written token's frame (counted per utterance from the
+// init, over the frames of all steps that counted for it); the records move with their nodes through the compaction.
+template <bool TIMED>
 __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ chunk_lengths, char* __restrict__ state, int* __restrict__ ids_all,
     int* __restrict__ committed, int* __restrict__ committed_counts, int* __restrict__ partial, int* __restrict__ partial_counts,
-    int* __restrict__ usage, int frames, int classes, int width, int blank, int pool_nodes)
+    int* __restrict__ usage, int frames, int classes, int width, int blank, int pool_nodes, int* __restrict__ committed_frames,
+    int* __restrict__ partial_frames)
 {
+    constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes);
+    const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes, TIMED);
     int2* __restrict__ pool = rec.pool;
+    const int t0 = TIMED ? rec.hdr[BS_FRAMES] : 0;
     const int n_live0 = rec.hdr[BS_N_LIVE], n_nodes0 = rec.hdr[BS_N_NODES], c_old = rec.hdr[BS_COMMITTED], ended = rec.hdr[BS_ENDED];
     const int cl = chunk_lengths ? chunk_lengths[b] : frames;
     const int len = ended ? 0 : min(max(cl, 0), frames);
@@ -425,6 +476,7 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
         st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
         st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
         st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
+        if (TIMED) st.p_best = rec.best[lane];
     }
     st.n_live = n_live0; st.n_nodes = n_nodes0;
     st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
@@ -433,7 +485,7 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     for (int t = 0; t < len; ++t) {
         const float lp = lp_next;
         if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];
-        beam_frame(st, lp, pool, classes, width, blank, lane);
+        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t0 + t);
     }
     __syncthreads();                                                   // pool entries written by other lanes
 
@@ -445,11 +497,11 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     for (int i = 0; i < n_live; ++i) d_min = min(d_min, rl(st.p_len, i));
     d_min -= c_old;                                                    // >= 0: every live prefix extends the committed one
     int node = live ? st.p_node : 0;
-    for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node].x;
+    for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node * NS].x;
     int lcp = d_min;
     for (int k = d_min; k >= 1; --k) {
         if (__ballot(live && node != rl(node, 0)) == 0ull) break;
-        const int2 e = live ? pool[node] : make_int2(0, 0);
+        const int2 e = live ? pool[node * NS] : make_int2(0, 0);
         if (__ballot(live && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;
         node = e.x;
     }
@@ -463,15 +515,22 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     __syncthreads();
     int* __restrict__ out_c = committed + static_cast<size_t>(b) * pool_nodes;
     int* __restrict__ out_p = partial + static_cast<size_t>(b) * pool_nodes;
+    int* __restrict__ out_cf = TIMED ? committed_frames + static_cast<size_t>(b) * pool_nodes : nullptr;
+    int* __restrict__ out_pf = TIMED ? partial_frames + static_cast<size_t>(b) * pool_nodes : nullptr;
     {
         const int stop = lane == 0 ? c_old : c_new;
         int k = live ? st.p_len : stop, nd = st.p_node;            // k: depth of node nd
         while (k > stop) {
-            const int2 e = pool[nd];
+            const int2 e = pool[nd * NS];
             if (k > c_new) ids[nd] = 1;
             if (lane == 0) {
                 if (k > c_new) out_p[k - 1 - c_new] = e.y;
                 else out_c[k - 1 - c_old] = e.y;
+                if (TIMED) {
+                    const int frame = pool[nd * NS + 1].x;
+                    if (k > c_new) out_pf[k - 1 - c_new] = frame;
+                    else out_cf[k - 1 - c_old] = frame;
+                }
             }
             nd = e.x;
             --k;
@@ -490,21 +549,25 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     __syncthreads();
     // ---- move the kept nodes down, in place: a chunk of 64 reads its entries before it stores (the store data depends on them),
     //      and it stores only at ids <= its own indices.  The parent of a kept node is kept too, or it is the committed prefix (id 0).
+    //      TIMED: the record half of a node moves the same way (its stores touch record halves only, and depend on its own loads).
     for (int i0 = 0; i0 < n_nodes; i0 += 64) {
         const int i = i0 + lane;
         const int id = i < n_nodes ? ids[i] : 0;
-        int2 e = make_int2(0, 0);
+        int2 e = make_int2(0, 0), f = make_int2(0, 0);
         if (id) {
-            e = pool[i];
+            e = pool[i * NS];
             e.x = ids[e.x];
+            if (TIMED) f = pool[i * NS + 1];
         }
-        if (id) pool[id] = e;
+        if (id) pool[id * NS] = e;
+        if (TIMED && id) pool[id * NS + 1] = f;
     }
     if (live) st.p_node = st.p_len > c_new ? ids[st.p_node] : 0;
 
     // ---- store the state
-    beam_stream_store(rec, st, lane, width);
+    beam_stream_store<TIMED>(rec, st, lane, width);
     if (lane == 0) {
+        if (TIMED) rec.hdr[BS_FRAMES] = t0 + len;
         rec.hdr[BS_N_LIVE] = n_live;
         rec.hdr[BS_N_NODES] = 1 + kept;
         rec.hdr[BS_COMMITTED] = c_new;
@@ -516,27 +579,32 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
 }
 
 // The live prefixes' uncommitted suffixes, best first: beams(batch, width, ld) padded with 0, scores = -log P (FLT_MAX beyond
-// n_live), beam_lens = suffix length (-1 beyond n_live).  Reads the state only.
+// n_live), beam_lens = suffix length (-1 beyond n_live).  Reads the state only.  TIMED: timesteps(batch, width, ld) = the suffix tokens' frames.
+template <bool TIMED>
 __global__ __launch_bounds__(64) void ctc_beam_stream_finish_kernel(const char* __restrict__ state, int* __restrict__ beams,
                                                                     float* __restrict__ scores, int* __restrict__ beam_lens, int ld,
-                                                                    int width, int pool_nodes)
+                                                                    int width, int pool_nodes, int* __restrict__ timesteps)
 {
+    constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
-    const BeamStreamRecord rec = beam_stream_record(const_cast<char*>(state), b, width, pool_nodes);
+    const BeamStreamRecord rec = beam_stream_record(const_cast<char*>(state), b, width, pool_nodes, TIMED);
     if (lane >= width) return;
     const int n_live = rec.hdr[BS_N_LIVE], c = rec.hdr[BS_COMMITTED];
     const bool live = lane < n_live;
     const int n = live ? rec.len[lane] - c : 0;
     int* out = beams + (static_cast<size_t>(b) * width + lane) * ld;
+    int* out_t = TIMED ? timesteps + (static_cast<size_t>(b) * width + lane) * ld : nullptr;
     if (live) {
         int node = rec.node[lane];
         for (int k = n - 1; k >= 0; --k) {
-            const int2 e = rec.pool[node];
+            const int2 e = rec.pool[node * NS];
             if (k < ld) out[k] = e.y;
+            if (TIMED && k < ld) out_t[k] = rec.pool[node * NS + 1].x;
             node = e.x;
         }
     }
     for (int k = n; k < ld; ++k) out[k] = 0;
+    if (TIMED) for (int k = n; k < ld; ++k) out_t[k] = 0;
     scores[static_cast<size_t>(b) * width + lane] = live ? -rec.pscore[lane] : FLT_MAX;
     beam_lens[static_cast<size_t>(b) * width + lane] = live ? n : -1;
 }
@@ -805,47 +873,88 @@ __global__ __launch_bounds__(256) void token_errors_kernel(
 
 using namespace nbasr;
 
-static size_t beam_pool_bytes(int batch, int frames, int beam_width)
+static size_t beam_pool_bytes(int batch, int frames, int beam_width, bool timed)
 {
-    return static_cast<size_t>(batch) * (static_cast<size_t>(frames) * beam_width + 1) * sizeof(int2);
+    return static_cast<size_t>(batch) * (static_cast<size_t>(frames) * beam_width + 1) * (timed ? 2 : 1) * sizeof(int2);
+}
+
+static size_t beam_workspace_bytes(int batch, int frames, int classes, int beam_width, bool timed)
+{
+    if (batch <= 0 || frames < 0 || classes <= 0 || beam_width <= 0) return 0;
+    return beam_pool_bytes(batch, frames, beam_width, timed) + static_cast<size_t>(batch) * frames * classes * sizeof(float);
 }
 
 extern "C" size_t nbasr_ctc_beam_workspace_bytes(int batch, int frames, int classes, int beam_width)
 {
-    if (batch <= 0 || frames < 0 || classes <= 0 || beam_width <= 0) return 0;
-    return beam_pool_bytes(batch, frames, beam_width) + static_cast<size_t>(batch) * frames * classes * sizeof(float);
+    return beam_workspace_bytes(batch, frames, classes, beam_width, false);
+}
+
+extern "C" size_t nbasr_ctc_beam_timed_workspace_bytes(int batch, int frames, int classes, int beam_width)
+{
+    return beam_workspace_bytes(batch, frames, classes, beam_width, true);
+}
+
+// the untimed and the timed entry points share their checks; `timed` selects the kernel instantiation
+static int beam_search(const char* fn, bool timed, const float* log_probs, const int* lengths, void* ws, int* beams, float* scores,
+                       int* timesteps, int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
+                       nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && blank >= 0 && blank < classes && cutoff_top_n > 0, NBASR_EINVAL,
+                  "%s: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d)", fn, batch, frames, classes, blank, cutoff_top_n);
+    NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
+                  "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(ws && scores && beam_lens && (frames == 0 || (log_probs && beams && (!timed || timesteps))), NBASR_ENULL, "%s: NULL pointer", fn);
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN, "%s: workspace must be 8-byte aligned", fn);
+    hipStream_t s = as_stream(stream);
+    const float* src = log_probs;
+    if (cutoff_top_n < classes && frames > 0) {
+        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_pool_bytes(batch, frames, beam_width, timed));
+        const long long n_frames = static_cast<long long>(batch) * frames;
+        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
+                           classes, cutoff_top_n);
+        src = pruned;
+    }
+    if (timed)
+        hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
+                           beam_lens, frames, classes, beam_width, blank, timesteps);
+    else
+        hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
+                           beam_lens, frames, classes, beam_width, blank, timesteps);
+    return launch_status(fn);
 }
 
 extern "C" int nbasr_ctc_beam_search(const float* log_probs, const int* lengths, void* ws, int* beams, float* scores, int* beam_lens,
                                      int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
                                      nbasr_stream_t stream)
 {
-    clear_error();
-    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && blank >= 0 && blank < classes && cutoff_top_n > 0, NBASR_EINVAL,
-                  "nbasr_ctc_beam_search: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d)", batch, frames, classes, blank, cutoff_top_n);
-    NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
-                  "nbasr_ctc_beam_search: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", classes, BEAM_CLASSES, beam_width, BEAM_MAX);
-    if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(ws && scores && beam_lens && (frames == 0 || (log_probs && beams)), NBASR_ENULL, "nbasr_ctc_beam_search: NULL pointer");
-    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_search: workspace must be 8-byte aligned");
-    hipStream_t s = as_stream(stream);
-    const float* src = log_probs;
-    if (cutoff_top_n < classes && frames > 0) {
-        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_pool_bytes(batch, frames, beam_width));
-        const long long n_frames = static_cast<long long>(batch) * frames;
-        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
-                           classes, cutoff_top_n);
-        src = pruned;
-    }
-    hipLaunchKernelGGL(ctc_beam_search_kernel, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
-                       beam_lens, frames, classes, beam_width, blank);
-    return launch_status("nbasr_ctc_beam_search");
+    return beam_search("nbasr_ctc_beam_search", false, log_probs, lengths, ws, beams, scores, nullptr, beam_lens, batch, frames, classes,
+                       beam_width, blank, cutoff_top_n, stream);
+}
+
+extern "C" int nbasr_ctc_beam_search_timed(const float* log_probs, const int* lengths, void* ws, int* beams, float* scores, int* timesteps,
+                                           int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
+                                           nbasr_stream_t stream)
+{
+    return beam_search("nbasr_ctc_beam_search_timed", true, log_probs, lengths, ws, beams, scores, timesteps, beam_lens, batch, frames,
+                       classes, beam_width, blank, cutoff_top_n, stream);
+}
+
+static size_t beam_stream_state_bytes(int batch, int beam_width, int pool_nodes, bool timed)
+{
+    if (batch <= 0 || beam_width <= 0 || beam_width > BEAM_MAX || pool_nodes <= 0) return 0;
+    return static_cast<size_t>(batch) * beam_stream_record_bytes(beam_width, pool_nodes, timed);
 }
 
 extern "C" size_t nbasr_ctc_beam_stream_state_bytes(int batch, int beam_width, int pool_nodes)
 {
-    if (batch <= 0 || beam_width <= 0 || beam_width > BEAM_MAX || pool_nodes <= 0) return 0;
-    return static_cast<size_t>(batch) * beam_stream_record_bytes(beam_width, pool_nodes);
+    return beam_stream_state_bytes(batch, beam_width, pool_nodes, false);
+}
+
+extern "C" size_t nbasr_ctc_beam_stream_timed_state_bytes(int batch, int beam_width, int pool_nodes)
+{
+    return beam_stream_state_bytes(batch, beam_width, pool_nodes, true);
 }
 
 extern "C" size_t nbasr_ctc_beam_stream_workspace_bytes(int batch, int frames, int classes, int pool_nodes)
@@ -854,33 +963,45 @@ extern "C" size_t nbasr_ctc_beam_stream_workspace_bytes(int batch, int frames, i
     return static_cast<size_t>(batch) * pool_nodes * sizeof(int) + static_cast<size_t>(batch) * frames * classes * sizeof(float);
 }
 
-extern "C" int nbasr_ctc_beam_stream_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+static int beam_stream_init(const char* fn, bool timed, void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
 {
     clear_error();
-    NBASR_REQUIRE(batch >= 0 && pool_nodes >= 1, NBASR_EINVAL, "nbasr_ctc_beam_stream_init: bad sizes (batch=%d pool_nodes=%d)", batch, pool_nodes);
-    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "nbasr_ctc_beam_stream_init: beam_width=%d (limit %d) unsupported",
-                  beam_width, BEAM_MAX);
+    NBASR_REQUIRE(batch >= 0 && pool_nodes >= 1, NBASR_EINVAL, "%s: bad sizes (batch=%d pool_nodes=%d)", fn, batch, pool_nodes);
+    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "%s: beam_width=%d (limit %d) unsupported", fn, beam_width, BEAM_MAX);
     if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(state, NBASR_ENULL, "nbasr_ctc_beam_stream_init: NULL pointer");
-    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_init: state must be 8-byte aligned");
-    hipLaunchKernelGGL(ctc_beam_stream_init_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
-    return launch_status("nbasr_ctc_beam_stream_init");
+    NBASR_REQUIRE(state, NBASR_ENULL, "%s: NULL pointer", fn);
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
+    if (timed)
+        hipLaunchKernelGGL(ctc_beam_stream_init_kernel<true>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
+    else
+        hipLaunchKernelGGL(ctc_beam_stream_init_kernel<false>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
+    return launch_status(fn);
 }
 
-extern "C" int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
-                                          int* committed_counts, int* partial, int* partial_counts, int* usage, int batch, int frames,
-                                          int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+extern "C" int nbasr_ctc_beam_stream_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_init("nbasr_ctc_beam_stream_init", false, state, batch, beam_width, pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_timed_init(void* state, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_init("nbasr_ctc_beam_stream_timed_init", true, state, batch, beam_width, pool_nodes, stream);
+}
+
+static int beam_stream_step(const char* fn, bool timed, const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+                            int* committed_frames, int* committed_counts, int* partial, int* partial_frames, int* partial_counts, int* usage,
+                            int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
     clear_error();
     NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && blank >= 0 && blank < classes && cutoff_top_n > 0 && pool_nodes >= 1,
-                  NBASR_EINVAL, "nbasr_ctc_beam_stream_step: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d pool_nodes=%d)",
-                  batch, frames, classes, blank, cutoff_top_n, pool_nodes);
+                  NBASR_EINVAL, "%s: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d pool_nodes=%d)",
+                  fn, batch, frames, classes, blank, cutoff_top_n, pool_nodes);
     NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
-                  "nbasr_ctc_beam_stream_step: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+                  "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
     if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(state && ws && committed && committed_counts && partial && partial_counts && usage && (frames == 0 || log_probs), NBASR_ENULL,
-                  "nbasr_ctc_beam_stream_step: NULL pointer");
-    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_step: state must be 8-byte aligned");
+    NBASR_REQUIRE(state && ws && committed && committed_counts && partial && partial_counts && usage && (frames == 0 || log_probs) &&
+                      (!timed || (committed_frames && partial_frames)), NBASR_ENULL, "%s: NULL pointer", fn);
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
     hipStream_t s = as_stream(stream);
     const float* src = log_probs;
     if (cutoff_top_n < classes && frames > 0) {
@@ -890,25 +1011,66 @@ extern "C" int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chu
                            classes, cutoff_top_n);
         src = pruned;
     }
-    hipLaunchKernelGGL(ctc_beam_stream_kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state), static_cast<int*>(ws),
-                       committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank, pool_nodes);
-    return launch_status("nbasr_ctc_beam_stream_step");
+    if (timed)
+        hipLaunchKernelGGL(ctc_beam_stream_kernel<true>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state),
+                           static_cast<int*>(ws), committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank,
+                           pool_nodes, committed_frames, partial_frames);
+    else
+        hipLaunchKernelGGL(ctc_beam_stream_kernel<false>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state),
+                           static_cast<int*>(ws), committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank,
+                           pool_nodes, committed_frames, partial_frames);
+    return launch_status(fn);
+}
+
+extern "C" int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+                                          int* committed_counts, int* partial, int* partial_counts, int* usage, int batch, int frames,
+                                          int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_step("nbasr_ctc_beam_stream_step", false, log_probs, chunk_lengths, state, ws, committed, nullptr, committed_counts,
+                            partial, nullptr, partial_counts, usage, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_timed_step(const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+                                                int* committed_frames, int* committed_counts, int* partial, int* partial_frames,
+                                                int* partial_counts, int* usage, int batch, int frames, int classes, int beam_width, int blank,
+                                                int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_step("nbasr_ctc_beam_stream_timed_step", true, log_probs, chunk_lengths, state, ws, committed, committed_frames,
+                            committed_counts, partial, partial_frames, partial_counts, usage, batch, frames, classes, beam_width, blank,
+                            cutoff_top_n, pool_nodes, stream);
+}
+
+static int beam_stream_finish(const char* fn, bool timed, const void* state, int* beams, float* scores, int* timesteps, int* beam_lens,
+                              int ld_beams, int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && ld_beams >= 0 && pool_nodes >= 1, NBASR_EINVAL, "%s: bad sizes (batch=%d ld_beams=%d pool_nodes=%d)", fn, batch,
+                  ld_beams, pool_nodes);
+    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "%s: beam_width=%d (limit %d) unsupported", fn, beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(state && scores && beam_lens && (ld_beams == 0 || (beams && (!timed || timesteps))), NBASR_ENULL, "%s: NULL pointer", fn);
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
+    if (timed)
+        hipLaunchKernelGGL(ctc_beam_stream_finish_kernel<true>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
+                           scores, beam_lens, ld_beams, beam_width, pool_nodes, timesteps);
+    else
+        hipLaunchKernelGGL(ctc_beam_stream_finish_kernel<false>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
+                           scores, beam_lens, ld_beams, beam_width, pool_nodes, timesteps);
+    return launch_status(fn);
 }
 
 extern "C" int nbasr_ctc_beam_stream_finish(const void* state, int* beams, float* scores, int* beam_lens, int ld_beams, int batch,
                                             int beam_width, int pool_nodes, nbasr_stream_t stream)
 {
-    clear_error();
-    NBASR_REQUIRE(batch >= 0 && ld_beams >= 0 && pool_nodes >= 1, NBASR_EINVAL,
-                  "nbasr_ctc_beam_stream_finish: bad sizes (batch=%d ld_beams=%d pool_nodes=%d)", batch, ld_beams, pool_nodes);
-    NBASR_REQUIRE(beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL, "nbasr_ctc_beam_stream_finish: beam_width=%d (limit %d) unsupported",
-                  beam_width, BEAM_MAX);
-    if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(state && scores && beam_lens && (ld_beams == 0 || beams), NBASR_ENULL, "nbasr_ctc_beam_stream_finish: NULL pointer");
-    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "nbasr_ctc_beam_stream_finish: state must be 8-byte aligned");
-    hipLaunchKernelGGL(ctc_beam_stream_finish_kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
-                       scores, beam_lens, ld_beams, beam_width, pool_nodes);
-    return launch_status("nbasr_ctc_beam_stream_finish");
+    return beam_stream_finish("nbasr_ctc_beam_stream_finish", false, state, beams, scores, nullptr, beam_lens, ld_beams, batch, beam_width,
+                              pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_timed_finish(const void* state, int* beams, float* scores, int* timesteps, int* beam_lens, int ld_beams,
+                                                  int batch, int beam_width, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_finish("nbasr_ctc_beam_stream_timed_finish", true, state, beams, scores, timesteps, beam_lens, ld_beams, batch,
+                              beam_width, pool_nodes, stream);
 }
 
 extern "C" int nbasr_ctc_loss(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, float* losses,

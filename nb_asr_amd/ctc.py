@@ -49,18 +49,20 @@ def _lengths(lengths, batch, device):
     return lengths.to(device=device, dtype=torch.int32).contiguous()
 
 
-def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n=40):
+def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n=40, *, return_timesteps=False):
     """CTC prefix beam search over log-probabilities (B, T', C), the reference's
     ``CTCBeamDecoder(vocab, beam_width=12, log_probs_input=True).decode(output, output_len)`` (trainer.py:71,237).
 
     ``output_len``: valid output frames per utterance (``output_lengths(audio_len)``), tensor or sequence, or None.
-    Returns ``(beams, scores, out_len)`` on the device like ctcdecode does (minus its per-token time steps): beams
-    (B, beam_width, T') int32 best first (entries beyond ``out_len`` are 0), scores (B, beam_width) = -log P (lower is
-    better), out_len (B, beam_width) int32."""
+    Returns ``(beams, scores, out_len)`` on the device: beams (B, beam_width, T') int32 best first (entries beyond ``out_len``
+    are 0), scores (B, beam_width) = -log P (lower is better), out_len (B, beam_width) int32.  ``return_timesteps=True`` returns
+    ctcdecode's four outputs in its order, ``(beams, scores, timesteps, out_len)``: timesteps (B, beam_width, T') int32, for
+    every token the frame at which its class was most probable among the frames that extended into it (DESIGN.md §9 "Beam
+    decode"; 0 beyond ``out_len``).  The search is the same one, bit for bit."""
     if log_probs.dim() != 3:
         raise ValueError(f'log_probs must be (batch, frames, classes), got {tuple(log_probs.shape)}')
     return hip.ctc_beam_search(log_probs.contiguous(), _lengths(output_len, log_probs.shape[0], log_probs.device),
-                               beam_width, blank, cutoff_top_n)
+                               beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps))
 
 
 class BeamSearchStream:
@@ -75,15 +77,21 @@ class BeamSearchStream:
     the current best beam's tokens after everything committed so far.  ``lengths`` (B) gives each utterance's frames in this
     chunk; fewer than the chunk has ends that utterance, and it takes no frames after that.  The token pool of the search keeps only
     the uncommitted parts of the live beams and grows (keeping its contents) when a push could overflow it: memory depends on how
-    far the beams diverge, not on the length of the stream."""
+    far the beams diverge, not on the length of the stream.
 
-    def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None):
+    ``timesteps=True`` (``beam_decode(..., return_timesteps=True)`` fed chunk by chunk): ``push`` returns ``(committed, partial,
+    committed_frames, partial_frames)`` -- lists of int32 CPU tensors aligned with the token lists, each token's frame counted per
+    utterance from ``reset()`` across pushes; a committed token's frame is final -- and ``finish()`` returns
+    ``(beams, scores, timesteps, out_len)``."""
+
+    def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None, timesteps=False):
         batch, beam_width = int(batch), int(beam_width)
         if batch < 1:
             raise ValueError(f'batch must be positive (got {batch})')
         if not 1 <= beam_width <= 32:
             raise ValueError(f'beam_width must be in [1, 32] (got {beam_width})')
         self.batch, self.beam_width, self.blank, self.cutoff_top_n = batch, beam_width, int(blank), int(cutoff_top_n)
+        self.timesteps = bool(timesteps)
         device = torch.device('cuda' if device is None else device)
         if device.type != 'cuda':
             raise ValueError(f'the beam search runs on a HIP device (got {device}); this package has no CPU path')
@@ -102,18 +110,20 @@ class BeamSearchStream:
         if self.state is None:
             self.pool_nodes = self.initial_pool_nodes
             self.state = torch.empty(self._words(self.pool_nodes), dtype=torch.int64, device=self.device)
-        hip.ctc_beam_stream_init(self.state, self.batch, self.beam_width, self.pool_nodes)
+        hip.ctc_beam_stream_init(self.state, self.batch, self.beam_width, self.pool_nodes, self.timesteps)
         self.usage = torch.ones(self.batch, dtype=torch.int64)
         self.ended = torch.zeros(self.batch, dtype=torch.bool)
         self.committed = [[] for _ in range(self.batch)]
         self.partial = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
+        self.committed_frames = [[] for _ in range(self.batch)]       # with timesteps: aligned with committed / partial
+        self.partial_frames = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
         self.frames = 0
         self.classes = None
         self.grown = 0
         self._finished = False
 
     def _words(self, pool_nodes):
-        return (hip.ctc_beam_stream_state_bytes(self.batch, self.beam_width, pool_nodes) + 7) // 8
+        return (hip.ctc_beam_stream_state_bytes(self.batch, self.beam_width, pool_nodes, self.timesteps) + 7) // 8
 
     def _grow(self, need):
         """Enlarge the pool to at least ``need`` nodes: every utterance's record keeps its bytes at the start of its new record."""
@@ -125,7 +135,8 @@ class BeamSearchStream:
         self.grown += 1
 
     def push(self, log_probs, lengths=None):
-        """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``."""
+        """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``, with
+        ``timesteps`` ``(committed, partial, committed_frames, partial_frames)``."""
         if self._finished:
             raise ValueError('push after finish(): call reset() to start the next utterances')
         if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.shape[0] != self.batch:
@@ -147,49 +158,69 @@ class BeamSearchStream:
             raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
         self.classes = c
         if n == 0:
-            return [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)], list(self.partial)
+            none = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
+            return (none, list(self.partial), list(none), list(self.partial_frames)) if self.timesteps else (none, list(self.partial))
         need = int(self.usage.max()) + self.beam_width * n + 1
         if need > self.pool_nodes:
             self._grow(need)
         chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
-        committed, partial, counts = hip.ctc_beam_stream_step(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width,
-                                                              self.pool_nodes, self.blank, self.cutoff_top_n)
+        *rows_out, counts = hip.ctc_beam_stream_step(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes,
+                                                     self.blank, self.cutoff_top_n, self.timesteps)
+        committed, partial = rows_out[:2]
         counts = counts.cpu()
         if bool((counts[2] < 0).any()):
             raise hip.HipError('ctc_beam_stream_step: the token pool was too small for the chunk')
         self.usage = counts[2].to(torch.int64)
         n_c, n_p = int(counts[0].max()), int(counts[1].max())
-        host = torch.cat([committed[:, :n_c], partial[:, :n_p]], 1).cpu()
+        parts = [committed[:, :n_c], partial[:, :n_p]]
+        if self.timesteps:
+            parts += [rows_out[2][:, :n_c], rows_out[3][:, :n_p]]
+        host = torch.cat(parts, 1).cpu()
         new_c = [host[i, : int(counts[0, i])].clone() for i in range(self.batch)]
         self.partial = [host[i, n_c: n_c + int(counts[1, i])].clone() for i in range(self.batch)]
         for i in range(self.batch):
             self.committed[i].append(new_c[i])
         self.ended |= rows < n
         self.frames += n
-        return new_c, list(self.partial)
+        if not self.timesteps:
+            return new_c, list(self.partial)
+        at = n_c + n_p
+        new_f = [host[i, at: at + int(counts[0, i])].clone() for i in range(self.batch)]
+        self.partial_frames = [host[i, at + n_c: at + n_c + int(counts[1, i])].clone() for i in range(self.batch)]
+        for i in range(self.batch):
+            self.committed_frames[i].append(new_f[i])
+        return new_c, list(self.partial), new_f, list(self.partial_frames)
 
     def finish(self):
         """End the utterances: ``(beams (B, W, T) int32, scores (B, W), out_len (B, W) int32)`` on the device, ``beam_decode``'s layout
-        over the T frames pushed."""
+        over the T frames pushed; with ``timesteps`` ``(beams, scores, timesteps (B, W, T) int32, out_len)``."""
         if self._finished:
             raise ValueError('finish() called twice: call reset() to start the next utterances')
         self._finished = True
         ld = max(int(self.usage.max()) - 1, 1)
-        suffix, scores, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld)
-        suffix, lens = suffix.cpu(), lens.cpu()
-        beams = torch.zeros(self.batch, self.beam_width, self.frames, dtype=torch.int32)
+        if self.timesteps:
+            suffix, scores, suffix_t, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld, True)
+            tails = [(suffix.cpu(), self.committed), (suffix_t.cpu(), self.committed_frames)]
+        else:
+            suffix, scores, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld)
+            tails = [(suffix.cpu(), self.committed)]
+        lens = lens.cpu()
+        outs = [torch.zeros(self.batch, self.beam_width, self.frames, dtype=torch.int32) for _ in tails]
         out_len = torch.zeros(self.batch, self.beam_width, dtype=torch.int32)
-        for i in range(self.batch):
-            head = torch.cat(self.committed[i]) if self.committed[i] else torch.zeros(0, dtype=torch.int32)
-            n_c = head.numel()
-            for r in range(self.beam_width):
-                n_s = int(lens[i, r])
-                if n_s < 0:
-                    continue                                     # no such beam: length 0, padded with 0
-                beams[i, r, :n_c] = head
-                beams[i, r, n_c: n_c + n_s] = suffix[i, r, :n_s]
-                out_len[i, r] = n_c + n_s
-        return beams.to(self.device), scores, out_len.to(self.device)
+        for (tail, heads), out in zip(tails, outs):               # the tokens, then (timed) their frames: committed head + live suffix
+            for i in range(self.batch):
+                head = torch.cat(heads[i]) if heads[i] else torch.zeros(0, dtype=torch.int32)
+                n_c = head.numel()
+                for r in range(self.beam_width):
+                    n_s = int(lens[i, r])
+                    if n_s < 0:
+                        continue                                 # no such beam: length 0, padded with 0
+                    out[i, r, :n_c] = head
+                    out[i, r, n_c: n_c + n_s] = tail[i, r, :n_s]
+                    out_len[i, r] = n_c + n_s
+        if self.timesteps:
+            return outs[0].to(self.device), scores, outs[1].to(self.device), out_len.to(self.device)
+        return outs[0].to(self.device), scores, out_len.to(self.device)
 
 
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):

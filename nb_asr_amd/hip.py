@@ -109,6 +109,12 @@ SIGNATURES = {
     'nbasr_ctc_beam_stream_init': (_c_int, [ctypes.c_void_p] + [_c_int] * 3 + [_c_stream]),
     'nbasr_ctc_beam_stream_step': (_c_int, [_c_float_p] * 9 + [_c_int] * 7 + [_c_stream]),
     'nbasr_ctc_beam_stream_finish': (_c_int, [ctypes.c_void_p] + [_c_float_p] * 3 + [_c_int] * 4 + [_c_stream]),
+    'nbasr_ctc_beam_timed_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
+    'nbasr_ctc_beam_search_timed': (_c_int, [_c_float_p] * 7 + [_c_int] * 6 + [_c_stream]),
+    'nbasr_ctc_beam_stream_timed_state_bytes': (ctypes.c_size_t, [_c_int] * 3),
+    'nbasr_ctc_beam_stream_timed_init': (_c_int, [ctypes.c_void_p] + [_c_int] * 3 + [_c_stream]),
+    'nbasr_ctc_beam_stream_timed_step': (_c_int, [_c_float_p] * 11 + [_c_int] * 7 + [_c_stream]),
+    'nbasr_ctc_beam_stream_timed_finish': (_c_int, [ctypes.c_void_p] + [_c_float_p] * 4 + [_c_int] * 4 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -972,9 +978,10 @@ def _int_tensor(t, what, device, shape=None):
     return t
 
 
-def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40):
+def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False):
     """log_probs (B, T', C) float32 log-probabilities -> (beams (B, W, T') int32 best first, scores (B, W) = -log P,
-    beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None."""
+    beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None.  ``timesteps``: the timed search
+    (nbasr_ctc_beam_search_timed) -> (beams, scores, timesteps (B, W, T') int32, beam_lens)."""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     if lengths is not None:
@@ -984,16 +991,26 @@ def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_
     scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
     lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
     lib = load_library()
+    lengths_ptr = None if lengths is None else lengths.data_ptr()
+    if timesteps:
+        steps = torch.empty(b, beam_width, t, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(lib.nbasr_ctc_beam_timed_workspace_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
+        _check(lib.nbasr_ctc_beam_search_timed(log_probs.data_ptr(), lengths_ptr, ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
+                                               steps.data_ptr(), lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n,
+                                               _stream(log_probs)), 'nbasr_ctc_beam_search_timed')
+        return beams, scores, steps, lens
     ws = torch.empty(max(lib.nbasr_ctc_beam_workspace_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
-    _check(lib.nbasr_ctc_beam_search(log_probs.data_ptr(), None if lengths is None else lengths.data_ptr(), ws.data_ptr(),
+    _check(lib.nbasr_ctc_beam_search(log_probs.data_ptr(), lengths_ptr, ws.data_ptr(),
                                      beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n,
                                      _stream(log_probs)), 'nbasr_ctc_beam_search')
     return beams, scores, lens
 
 
-def ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes):
-    """Bytes of the state of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_state_bytes); 0 for bad sizes."""
-    return int(load_library().nbasr_ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes))
+def ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes, timesteps=False):
+    """Bytes of the state of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_state_bytes, or _timed_state_bytes); 0 for bad sizes."""
+    lib = load_library()
+    fn = lib.nbasr_ctc_beam_stream_timed_state_bytes if timesteps else lib.nbasr_ctc_beam_stream_state_bytes
+    return int(fn(batch, beam_width, pool_nodes))
 
 
 def _state(state, what='state'):
@@ -1002,45 +1019,62 @@ def _state(state, what='state'):
     return state.data_ptr()
 
 
-def ctc_beam_stream_init(state, batch, beam_width, pool_nodes):
+def ctc_beam_stream_init(state, batch, beam_width, pool_nodes, timesteps=False):
     """Every utterance of ``state`` (a device tensor of ``ctc_beam_stream_state_bytes`` bytes) to the empty prefix."""
-    if state.numel() * state.element_size() < ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes):
+    if state.numel() * state.element_size() < ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes, timesteps):
         raise HipError('ctc_beam_stream_init: state tensor too small (ctc_beam_stream_state_bytes)')
-    _check(load_library().nbasr_ctc_beam_stream_init(_state(state), batch, beam_width, pool_nodes, _stream(state)),
-           'nbasr_ctc_beam_stream_init')
+    lib = load_library()
+    name = 'nbasr_ctc_beam_stream_timed_init' if timesteps else 'nbasr_ctc_beam_stream_init'
+    _check(getattr(lib, name)(_state(state), batch, beam_width, pool_nodes, _stream(state)), name)
 
 
-def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40):
+def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40, timesteps=False):
     """One chunk of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_step): log_probs (B, n, C) float32, chunk_lengths (B)
     int32 device tensor or None.  Returns device tensors (committed (B, pool_nodes), partial (B, pool_nodes), counts (3, B) int32 =
-    committed counts, partial counts, pool usage (-1: refused, the pool is too small for this chunk))."""
+    committed counts, partial counts, pool usage (-1: refused, the pool is too small for this chunk)).  ``timesteps`` (a state of the
+    timed family, nbasr_ctc_beam_stream_timed_step): (committed, partial, committed_frames, partial_frames, counts)."""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     dev = log_probs.device
     if chunk_lengths is not None:
         _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
-    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes):
+    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
         raise HipError('ctc_beam_stream_step: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
     lib = load_library()
-    out = torch.empty(2, b, pool_nodes, dtype=torch.int32, device=dev)
+    out = torch.empty(4 if timesteps else 2, b, pool_nodes, dtype=torch.int32, device=dev)
     counts = torch.empty(3, b, dtype=torch.int32, device=dev)
     ws = torch.empty(max(lib.nbasr_ctc_beam_stream_workspace_bytes(b, t, c, pool_nodes), 8) // 4 + 1, dtype=torch.int32, device=dev)
-    _check(lib.nbasr_ctc_beam_stream_step(log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr(),
+    lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
+    if timesteps:
+        _check(lib.nbasr_ctc_beam_stream_timed_step(lp_ptr, len_ptr, _state(state), ws.data_ptr(), out[0].data_ptr(), out[2].data_ptr(),
+                                                    counts[0].data_ptr(), out[1].data_ptr(), out[3].data_ptr(), counts[1].data_ptr(),
+                                                    counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes,
+                                                    _stream(log_probs)), 'nbasr_ctc_beam_stream_timed_step')
+        return out[0], out[1], out[2], out[3], counts
+    _check(lib.nbasr_ctc_beam_stream_step(lp_ptr, len_ptr,
                                           _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(),
                                           counts[1].data_ptr(), counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes,
                                           _stream(log_probs)), 'nbasr_ctc_beam_stream_step')
     return out[0], out[1], counts
 
 
-def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld):
+def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld, timesteps=False):
     """The live prefixes' uncommitted suffixes (nbasr.h: nbasr_ctc_beam_stream_finish): (suffixes (B, W, ld) int32, scores (B, W),
-    suffix lengths (B, W) int32, -1 beyond the live prefixes)."""
+    suffix lengths (B, W) int32, -1 beyond the live prefixes).  ``timesteps`` (nbasr_ctc_beam_stream_timed_finish): (suffixes, scores,
+    the suffix tokens' frames (B, W, ld) int32, suffix lengths)."""
     dev = state.device
     beams = torch.empty(batch, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
     scores = torch.empty(batch, beam_width, dtype=torch.float32, device=dev)
     lens = torch.empty(batch, beam_width, dtype=torch.int32, device=dev)
-    _check(load_library().nbasr_ctc_beam_stream_finish(_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2],
-                                                       batch, beam_width, pool_nodes, _stream(state)), 'nbasr_ctc_beam_stream_finish')
+    lib = load_library()
+    if timesteps:
+        steps = torch.empty_like(beams)
+        _check(lib.nbasr_ctc_beam_stream_timed_finish(_state(state), beams.data_ptr(), scores.data_ptr(), steps.data_ptr(), lens.data_ptr(),
+                                                      beams.shape[2], batch, beam_width, pool_nodes, _stream(state)),
+               'nbasr_ctc_beam_stream_timed_finish')
+        return beams, scores, steps, lens
+    _check(lib.nbasr_ctc_beam_stream_finish(_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2],
+                                            batch, beam_width, pool_nodes, _stream(state)), 'nbasr_ctc_beam_stream_finish')
     return beams, scores, lens
 
 

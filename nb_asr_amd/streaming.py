@@ -8,6 +8,8 @@
 
     logits, committed, partial = sess.push(chunk, decode='beam')       # also the prefix beam search of ctc.beam_decode
     logits, (beams, scores, out_len) = sess.flush(decode='beam')
+    logits, committed, partial, committed_frames, partial_frames = sess.push(chunk, decode='beam-timed')    # + each token's output frame
+    logits, (beams, scores, timesteps, out_len) = sess.flush(decode='beam-timed')
 
     sess = model.eval().stream(batch=B, frontend=fe)                   # fe: frontend.LogMelFrontend on the model's device
     logits = sess.push_audio(wave_chunk)         # (B, n) float32 samples: the front-end's stream (frontend.FrontendStream), then push
@@ -36,6 +38,7 @@ LSTM_HIDDEN = 500
 CONTEXT = 4
 OP_NAMES = ('linear', 'conv5', 'conv5d2', 'conv7', 'conv7d2', 'zero')
 CONV_OPS = {'conv5': (5, 1), 'conv5d2': (5, 2), 'conv7': (7, 1), 'conv7d2': (7, 2)}
+BEAM_DECODES = ('beam', 'beam-timed')               # ``decode=`` values of a session that run the prefix beam search
 
 
 def pad_amounts(kernel, dilation, stride, context=CONTEXT):
@@ -214,6 +217,7 @@ class StreamingSession:
         self.model, self.batch, self.max_chunk, self.device = model, batch, max_chunk, p0.device
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
         self._beam = None                         # ctc.BeamSearchStream, made by the first push with decode='beam'
+        self._beam_timed = None                   # ... with timesteps=True, by the first push with decode='beam-timed'
         arch = [[type(n.op).__name__, *(int(type(br).__name__ == 'Identity') for br in n.branch_ops)] for n in model.model[2].nodes]
         names = []
         for (kind, *flags), node in zip(arch, model.model[2].nodes):
@@ -322,7 +326,7 @@ class StreamingSession:
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, and with a
         front-end its sample tails and the staging buffer)."""
-        return (sum(t.numel() * t.element_size() for t in self._bufs) + (self._beam.state_bytes if self._beam is not None else 0)
+        return (sum(t.numel() * t.element_size() for t in self._bufs) + sum(d.state_bytes for d in (self._beam, self._beam_timed) if d is not None)
                 + (self._frontend.state_bytes if self._frontend is not None else 0))
 
     def reset(self):
@@ -335,8 +339,10 @@ class StreamingSession:
         self._ld_prev = [0] * len(self.specs)     # row pitch of every stage's current window
         self.prev_token.fill_(-1)
         self._beam_frames = 0                    # logit frames fed to the beam search in this utterance
-        if self._beam is not None:
-            self._beam.reset()
+        self._beam_mode = None                   # 'beam' or 'beam-timed': the decoder that has seen this utterance's frames
+        for dec in (self._beam, self._beam_timed):
+            if dec is not None:
+                dec.reset()
         self._fed = None                         # 'features' (push) or 'audio' (push_audio): one utterance takes one of them
         if self._frontend is not None:
             self._frontend.reset()
@@ -345,7 +351,10 @@ class StreamingSession:
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
         the greedy CTC tokens of those frames (a list of int32 CPU tensors), repeats collapsed across pushes.  ``decode='beam'`` returns
         ``(logits, committed, partial)``: the prefix beam search of ``ctc.beam_decode`` run over the log-probabilities of the final frames
-        (``ctc.BeamSearchStream``): tokens that are now final, and the best beam's tokens after all committed ones."""
+        (``ctc.BeamSearchStream``): tokens that are now final, and the best beam's tokens after all committed ones.
+        ``decode='beam-timed'`` returns ``(logits, committed, partial, committed_frames, partial_frames)``: the same search with each
+        token's time step (``BeamSearchStream(timesteps=True)``), an output-frame index -- one output frame is 4 input frames, 40 ms at
+        the front-end's 10 ms hop.  One utterance is decoded with one of the two."""
         if self._flushed:
             raise ValueError('push after flush: call reset() to start the next utterance')
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or chunk.shape[0] != self.batch or chunk.shape[1] != FEATURES:
@@ -355,8 +364,8 @@ class StreamingSession:
         if self._fed == 'audio':
             raise ValueError('push after push_audio: an utterance is fed features or samples, not both (reset() starts the next one)')
         self._check_params()
-        if decode == 'beam':
-            self._beam_ready()
+        if decode in BEAM_DECODES:
+            self._beam_ready(decode)
         self._fed = 'features'
         chunk = chunk.detach().contiguous()
         outs, n = [], chunk.shape[2]
@@ -368,8 +377,8 @@ class StreamingSession:
 
     def _pushed(self, outs, decode):
         logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
-        if decode == 'beam':
-            return (logits,) + self._beam_push(logits)
+        if decode in BEAM_DECODES:
+            return (logits,) + self._beam_push(logits, decode)
         return (logits, self._decode(logits)) if decode else logits
 
     def push_audio(self, wave_chunk, decode=False):
@@ -387,8 +396,8 @@ class StreamingSession:
             raise ValueError(f'expected a ({self.batch}, samples) float32 chunk on {self.device}, got {tuple(getattr(wave_chunk, "shape", ()))} '
                              f'{getattr(wave_chunk, "dtype", None)} on {getattr(wave_chunk, "device", None)}')
         self._check_params()
-        if decode == 'beam':
-            self._beam_ready()
+        if decode in BEAM_DECODES:
+            self._beam_ready(decode)
         self._fed = 'audio'
         outs = [self._step(self._staging if k else None, 0, k, False)
                 for k in self._frontend.push_tiled(wave_chunk, self._staging, self.max_chunk)]
@@ -396,12 +405,13 @@ class StreamingSession:
 
     def flush(self, decode=False):
         """End the utterance: the remaining logits, computed with the full forward's zero right-padding.  ``decode='beam'`` returns
-        ``(logits, (beams, scores, out_len))``: ``ctc.beam_decode`` of the log-probabilities of all the utterance's logits."""
+        ``(logits, (beams, scores, out_len))``: ``ctc.beam_decode`` of the log-probabilities of all the utterance's logits;
+        ``decode='beam-timed'`` ``(logits, (beams, scores, timesteps, out_len))``, its ``return_timesteps=True`` form."""
         if self._flushed:
             raise ValueError('flush called twice: call reset() to start the next utterance')
         self._check_params()
-        if decode == 'beam':
-            self._beam_ready()
+        if decode in BEAM_DECODES:
+            self._beam_ready(decode)
         last = []
         if self._fed == 'audio':                 # the front-end's last 1 or 2 frames first, as a push of features
             m = self._frontend.flush(out=(self._staging, 0)).shape[2]
@@ -410,22 +420,33 @@ class StreamingSession:
         if last:
             logits = torch.cat(last + [logits], 1)
         self._flushed = True
-        if decode == 'beam':
-            self._beam_push(logits)
-            return logits, self._beam.finish()
+        if decode in BEAM_DECODES:
+            self._beam_push(logits, decode)
+            return logits, self._beam_decoder(decode).finish()
         return (logits, self._decode(logits)) if decode else logits
 
-    def _beam_ready(self):
-        if self._beam_frames != self.frames_out:
-            raise ValueError("decode='beam' must see every logit frame of the utterance: use it from the first push on (or reset())")
-        if self._beam is None:
-            from .ctc import BeamSearchStream
-            self._beam = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device)
+    def _beam_decoder(self, decode):
+        return self._beam_timed if decode == 'beam-timed' else self._beam
 
-    def _beam_push(self, logits):
+    def _beam_ready(self, decode):
+        if self._beam_mode not in (None, decode):
+            raise ValueError(f"decode={decode!r} after decode={self._beam_mode!r} in one utterance: one search sees every frame "
+                             '(call reset() to start the next utterance with the other)')
+        if self._beam_frames != self.frames_out:
+            raise ValueError(f"decode={decode!r} must see every logit frame of the utterance: use it from the first push on (or reset())")
+        self._beam_mode = decode
+        if self._beam_decoder(decode) is None:
+            from .ctc import BeamSearchStream
+            dec = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device, timesteps=decode == 'beam-timed')
+            if decode == 'beam-timed':
+                self._beam_timed = dec
+            else:
+                self._beam = dec
+
+    def _beam_push(self, logits, decode):
         log_probs = hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits
         self._beam_frames += logits.shape[1]
-        return self._beam.push(log_probs)
+        return self._beam_decoder(decode).push(log_probs)
 
     def _decode(self, logits):
         tokens, counts = hip.ctc_greedy_stream(logits, self.prev_token)
