@@ -456,6 +456,27 @@ int nbasr_ctc_beam_stream_timed_step(const float* log_probs, const int* chunk_le
 int nbasr_ctc_beam_stream_timed_finish(const void* state, int* beams, float* scores, int* timesteps, int* beam_lens, int ld_beams,
                                        int batch, int beam_width, int pool_nodes, nbasr_stream_t stream);
 
+/* ---- peek: a read-only "finish after these frames" (nb_asr_amd/ctc.py BeamSearchStream.peek) ---------------------------------
+ * nbasr_ctc_beam_stream_peek takes one chunk log_probs(batch, frames, classes) with chunk_lengths(batch) or NULL, as _step does, and
+ *   writes what _finish would write if _step had first been run on that chunk: beams(batch, beam_width, ld_beams) = the live prefixes'
+ *   tokens after the prefix the STATE has committed (the step would commit more of them: the same tokens, split elsewhere), best first,
+ *   padded with 0; scores = -log P (FLT_MAX beyond the live prefixes); beam_lens = suffix lengths (-1 beyond the live prefixes).
+ *   ld_beams >= the largest usage - 1 + frames holds every suffix.  The state is only read: nothing is committed, the pool is not
+ *   compacted, and any number of peeks may precede the next _step or _finish.  frames == 0 gives exactly _finish.
+ *   ws: nbasr_ctc_beam_stream_peek_workspace_bytes(batch, frames, classes, beam_width, pool_nodes), 8-byte aligned, no state between
+ *   calls (0 for sizes beyond the limits).  It holds a scratch pool of pool_nodes + beam_width * frames + 1 nodes per utterance, so a
+ *   peek never needs the state's pool grown and reports no usage = -1 case.
+ * nbasr_ctc_beam_stream_timed_peek: the same over a state of the timed family, plus timesteps(batch, beam_width, ld_beams) as _timed_finish
+ *   (frames counted on from the record's own frame counter).  One workspace size serves both.
+ * Limits and checks as _step: classes <= 64, beam_width <= 32. */
+size_t nbasr_ctc_beam_stream_peek_workspace_bytes(int batch, int frames, int classes, int beam_width, int pool_nodes);
+int nbasr_ctc_beam_stream_peek(const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams, float* scores,
+                               int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width, int blank,
+                               int cutoff_top_n, int pool_nodes, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams, float* scores,
+                                     int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width,
+                                     int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

@@ -609,6 +609,103 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_finish_kernel(const char* 
     beam_lens[static_cast<size_t>(b) * width + lane] = live ? n : -1;
 }
 
+// Nodes per utterance of a peek's scratch pool: the record's live nodes (at most pool_nodes) plus what `frames` frames can add.
+__host__ __device__ constexpr size_t beam_stream_peek_nodes(int frames, int width, int pool_nodes)
+{
+    return static_cast<size_t>(pool_nodes) + static_cast<size_t>(width) * frames + 1;
+}
+
+// "Finish after these frames": what ctc_beam_stream_finish_kernel would write if ctc_beam_stream_kernel had first run on the chunk, with
+// nothing committed, nothing compacted and no store to `state`.  The lanes are loaded from the record, the record's n_nodes live pool nodes
+// are copied (at their indices, so the lanes' p_node stay valid) into a scratch pool of beam_stream_peek_nodes nodes, the shared frame body
+// runs there, and the finish layout is written from the lanes in registers: suffixes after the record's committed prefix (the step would
+// commit more of them, which moves tokens from the suffix to the head and changes no token).  The scratch holds the record's nodes and the
+// chunk's, so there is no refusal for a full pool.  frames == 0 is the finish kernel.
+template <bool TIMED>
+__global__ __launch_bounds__(64) void ctc_beam_stream_peek_kernel(
+    const float* __restrict__ log_probs, const int* __restrict__ chunk_lengths, const char* __restrict__ state, int2* __restrict__ scratch_all,
+    int* __restrict__ beams, float* __restrict__ scores, int* __restrict__ beam_lens, int ld, int frames, int classes, int width, int blank,
+    int pool_nodes, int* __restrict__ timesteps)
+{
+    constexpr int NS = NODE_INT2<TIMED>;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const BeamStreamRecord rec = beam_stream_record(const_cast<char*>(state), b, width, pool_nodes, TIMED);
+    const int2* __restrict__ src_pool = rec.pool;
+    int2* __restrict__ pool = scratch_all + static_cast<size_t>(b) * beam_stream_peek_nodes(frames, width, pool_nodes) * NS;
+    const int t0 = TIMED ? rec.hdr[BS_FRAMES] : 0;
+    const int n_live0 = min(max(rec.hdr[BS_N_LIVE], 0), width), n_nodes0 = min(max(rec.hdr[BS_N_NODES], 1), pool_nodes);
+    const int c_old = rec.hdr[BS_COMMITTED], ended = rec.hdr[BS_ENDED];
+    const int cl = chunk_lengths ? chunk_lengths[b] : frames;
+    const int len = ended ? 0 : min(max(cl, 0), frames);
+    const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
+
+    for (int i = lane; i < n_nodes0 * NS; i += 64) pool[i] = src_pool[i];
+    __syncthreads();
+
+    BeamLanes st;
+    beam_lane_reset(st);
+    if (lane < n_live0) {
+        st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
+        st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
+        st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
+        if (TIMED) st.p_best = rec.best[lane];
+    }
+    st.n_live = n_live0; st.n_nodes = n_nodes0;
+    st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
+
+    float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
+    for (int t = 0; t < len; ++t) {
+        const float lp = lp_next;
+        if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];
+        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t0 + t);
+    }
+    __syncthreads();                                                   // pool entries written by other lanes
+
+    // TIMED: the step commits the longest common token prefix of the live prefixes and reports the committed tokens' frames from the BEST
+    // prefix's nodes, for every beam.  Two live prefixes can spell that common part through different nodes with different records (a prefix
+    // that left the beam and was created again has a fresh node), so the first `lcp` frames of every row are lane 0's here too; the walk is
+    // the step's.  The tokens agree by definition, so the untimed peek needs none of this.
+    const bool live = lane < st.n_live;
+    int lcp = 0;
+    if (TIMED) {
+        int d_min = INT_MAX;
+        for (int i = 0; i < st.n_live; ++i) d_min = min(d_min, rl(st.p_len, i));
+        d_min -= c_old;
+        int node = live ? st.p_node : 0;
+        for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node * NS].x;
+        lcp = d_min;
+        for (int k = d_min; k >= 1; --k) {
+            if (__ballot(live && node != rl(node, 0)) == 0ull) break;
+            const int2 e = live ? pool[node * NS] : make_int2(0, 0);
+            if (__ballot(live && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;
+            node = e.x;
+        }
+    }
+
+    if (lane >= width) return;
+    const int n = live ? st.p_len - c_old : 0;
+    int* out = beams + (static_cast<size_t>(b) * width + lane) * ld;
+    int* out_t = TIMED ? timesteps + (static_cast<size_t>(b) * width + lane) * ld : nullptr;
+    if (live) {
+        int node = st.p_node;
+        for (int k = n - 1; k >= 0; --k) {
+            const int2 e = pool[node * NS];
+            if (k < ld) out[k] = e.y;
+            if (TIMED && k < ld) {
+                const int frame = pool[node * NS + 1].x;
+                if (k >= lcp) out_t[k] = frame;
+                else if (lane == 0)
+                    for (int r = 0; r < st.n_live; ++r) timesteps[(static_cast<size_t>(b) * width + r) * ld + k] = frame;
+            }
+            node = e.x;
+        }
+    }
+    for (int k = max(n, 0); k < ld; ++k) out[k] = 0;
+    if (TIMED) for (int k = max(n, 0); k < ld; ++k) out_t[k] = 0;
+    scores[static_cast<size_t>(b) * width + lane] = live ? -st.p_score : FLT_MAX;
+    beam_lens[static_cast<size_t>(b) * width + lane] = live ? n : -1;
+}
+
 // ---- CTC loss (forward value) -----------------------------------------------------------------------------------------------
 // The reference's loss (training/torch/trainer.py:36-42): F.ctc_loss(log_probs (T, B, C), targets, output_len, targets_len,
 // reduction='none', zero_infinity=True) / output_len, then the mean over the batch (the mean is left to the caller).
@@ -1071,6 +1168,69 @@ extern "C" int nbasr_ctc_beam_stream_timed_finish(const void* state, int* beams,
 {
     return beam_stream_finish("nbasr_ctc_beam_stream_timed_finish", true, state, beams, scores, timesteps, beam_lens, ld_beams, batch,
                               beam_width, pool_nodes, stream);
+}
+
+// the peek's workspace: the scratch pools (8-byte nodes, or 16-byte ones for the timed family: sized for those, one size serves both), then
+// the pruned log-probabilities
+static size_t beam_stream_peek_pool_bytes(int batch, int frames, int beam_width, int pool_nodes)
+{
+    return static_cast<size_t>(batch) * beam_stream_peek_nodes(frames, beam_width, pool_nodes) * 2 * sizeof(int2);
+}
+
+extern "C" size_t nbasr_ctc_beam_stream_peek_workspace_bytes(int batch, int frames, int classes, int beam_width, int pool_nodes)
+{
+    if (batch <= 0 || frames < 0 || classes <= 0 || classes > BEAM_CLASSES || beam_width <= 0 || beam_width > BEAM_MAX || pool_nodes <= 0) return 0;
+    const size_t pruned = (static_cast<size_t>(batch) * frames * classes * sizeof(float) + 7) & ~size_t(7);
+    return beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes) + pruned;
+}
+
+static int beam_stream_peek(const char* fn, bool timed, const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams,
+                            float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width,
+                            int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    clear_error();
+    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && blank >= 0 && blank < classes && cutoff_top_n > 0 && pool_nodes >= 1 && ld_beams >= 0,
+                  NBASR_EINVAL, "%s: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d pool_nodes=%d ld_beams=%d)",
+                  fn, batch, frames, classes, blank, cutoff_top_n, pool_nodes, ld_beams);
+    NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
+                  "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    if (batch == 0) return NBASR_OK;
+    NBASR_REQUIRE(state && ws && scores && beam_lens && (frames == 0 || log_probs) && (ld_beams == 0 || (beams && (!timed || timesteps))),
+                  NBASR_ENULL, "%s: NULL pointer", fn);
+    NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0 && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN,
+                  "%s: state and workspace must be 8-byte aligned", fn);
+    hipStream_t s = as_stream(stream);
+    const float* src = log_probs;
+    if (cutoff_top_n < classes && frames > 0) {
+        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes));
+        const long long n_frames = static_cast<long long>(batch) * frames;
+        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
+                           classes, cutoff_top_n);
+        src = pruned;
+    }
+    if (timed)
+        hipLaunchKernelGGL(ctc_beam_stream_peek_kernel<true>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state),
+                           static_cast<int2*>(ws), beams, scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
+    else
+        hipLaunchKernelGGL(ctc_beam_stream_peek_kernel<false>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state),
+                           static_cast<int2*>(ws), beams, scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
+    return launch_status(fn);
+}
+
+extern "C" int nbasr_ctc_beam_stream_peek(const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams, float* scores,
+                                          int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width, int blank,
+                                          int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_peek("nbasr_ctc_beam_stream_peek", false, log_probs, chunk_lengths, state, ws, beams, scores, nullptr, beam_lens, ld_beams,
+                            batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams,
+                                                float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes,
+                                                int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
+{
+    return beam_stream_peek("nbasr_ctc_beam_stream_timed_peek", true, log_probs, chunk_lengths, state, ws, beams, scores, timesteps, beam_lens,
+                            ld_beams, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
 }
 
 extern "C" int nbasr_ctc_loss(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, float* losses,

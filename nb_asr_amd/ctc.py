@@ -71,6 +71,7 @@ class BeamSearchStream:
         dec = BeamSearchStream(batch, beam_width=12, blank=0, cutoff_top_n=40, device=dev)
         committed, partial = dec.push(log_probs_chunk, lengths=None)   # lists of int32 CPU tensors, one per utterance
         beams, scores, out_len = dec.finish()     # == beam_decode(all frames, total lengths), bit for bit
+        beams, scores, out_len = dec.peek(next_chunk)                  # what finish() would give after push(next_chunk); changes nothing
 
     ``committed``: the tokens that became final with this chunk -- a prefix of every beam the search can still return, so they
     never change; the committed tokens of all pushes, concatenated, start every finite-score beam of ``finish()``.  ``partial``:
@@ -98,6 +99,7 @@ class BeamSearchStream:
         self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
         self.initial_pool_nodes = int(pool_nodes) if pool_nodes is not None else 1 + beam_width * 4 * 40
         self.state = None
+        self._peek_ws = None                      # peek's scratch pool, kept between peeks (reset() keeps it too)
         self.reset()
 
     @property
@@ -198,26 +200,74 @@ class BeamSearchStream:
             raise ValueError('finish() called twice: call reset() to start the next utterances')
         self._finished = True
         ld = max(int(self.usage.max()) - 1, 1)
+        return self._assemble(hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld, self.timesteps), self.frames)
+
+    def peek(self, log_probs=None, lengths=None):
+        """What ``finish()`` would return if ``push(log_probs, lengths)`` had been called first (None: no more frames), with the search left
+        exactly as it was: the state is only read (nbasr_ctc_beam_stream_peek), no attribute changes, the pool never grows.  Allowed any
+        number of times before ``finish()``; only the workspace (``peek_bytes``) is kept, for the next peek."""
+        if self._finished:
+            raise ValueError('push after finish(): call reset() to start the next utterances')
+        if log_probs is None:
+            log_probs = torch.empty(self.batch, 0, self.classes or self.blank + 1, dtype=torch.float32, device=self.device)
+        if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.shape[0] != self.batch:
+            raise ValueError(f'expected log-probabilities ({self.batch}, frames, classes), got {tuple(getattr(log_probs, "shape", ()))}')
+        if log_probs.dtype != torch.float32 or log_probs.device != self.device:
+            raise ValueError(f'log-probabilities must be float32 on {self.device} (got {log_probs.dtype} on {log_probs.device})')
+        n, c = log_probs.shape[1], log_probs.shape[2]
+        if self.classes is not None and n and c != self.classes:
+            raise ValueError(f'every chunk must have {self.classes} classes (got {c})')
+        chunk_lengths = None
+        if lengths is not None:
+            rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
+            if rows.numel() != self.batch:
+                raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
+            if bool(((rows < 0) | (rows > n)).any()):
+                raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
+            if bool((self.ended & (rows > 0)).any()):
+                raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+            chunk_lengths = rows.to(device=self.device, dtype=torch.int32)
+        elif n and bool(self.ended.any()):
+            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        self.reserve_peek(n, c)
+        ld = max(int(self.usage.max()) - 1 + n, 1)               # a frame lengthens a suffix by at most one token
+        outs = hip.ctc_beam_stream_peek(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes, ld, self.blank,
+                                        self.cutoff_top_n, self.timesteps, self._peek_ws)
+        return self._assemble(outs, self.frames + n)
+
+    def reserve_peek(self, frames, classes=None):
+        """Make the cached peek workspace large enough for peeks of up to ``frames`` frames (a caller that bounds its memory calls this
+        once; ``peek`` calls it with its own chunk, so the workspace only ever grows)."""
+        need = hip.ctc_beam_stream_peek_workspace_bytes(self.batch, frames, classes or self.classes or 1, self.beam_width, self.pool_nodes)
+        if self._peek_ws is None or self._peek_ws.numel() * 8 < need:
+            self._peek_ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=self.device)
+
+    @property
+    def peek_bytes(self):
+        """Device bytes of the cached peek workspace (0 before the first ``peek``); not part of ``state_bytes``."""
+        return 0 if self._peek_ws is None else self._peek_ws.numel() * 8
+
+    def _assemble(self, outs, frames):
+        """Committed heads + the live suffixes of a finish / peek launch -> ``beam_decode``'s layout over ``frames`` frames."""
         if self.timesteps:
-            suffix, scores, suffix_t, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld, True)
+            suffix, scores, suffix_t, lens = outs
             tails = [(suffix.cpu(), self.committed), (suffix_t.cpu(), self.committed_frames)]
         else:
-            suffix, scores, lens = hip.ctc_beam_stream_finish(self.state, self.batch, self.beam_width, self.pool_nodes, ld)
+            suffix, scores, lens = outs
             tails = [(suffix.cpu(), self.committed)]
         lens = lens.cpu()
-        outs = [torch.zeros(self.batch, self.beam_width, self.frames, dtype=torch.int32) for _ in tails]
-        out_len = torch.zeros(self.batch, self.beam_width, dtype=torch.int32)
+        outs = [torch.zeros(self.batch, self.beam_width, frames, dtype=torch.int32) for _ in tails]
+        live = lens >= 0                                         # (B, W): beyond the live prefixes there is no beam: length 0, padded with 0
+        n_c = torch.tensor([sum(c.numel() for c in self.committed[i]) for i in range(self.batch)], dtype=torch.int32)
+        out_len = torch.where(live, n_c[:, None] + lens, 0).to(torch.int32)
         for (tail, heads), out in zip(tails, outs):               # the tokens, then (timed) their frames: committed head + live suffix
             for i in range(self.batch):
-                head = torch.cat(heads[i]) if heads[i] else torch.zeros(0, dtype=torch.int32)
-                n_c = head.numel()
-                for r in range(self.beam_width):
-                    n_s = int(lens[i, r])
-                    if n_s < 0:
-                        continue                                 # no such beam: length 0, padded with 0
-                    out[i, r, :n_c] = head
-                    out[i, r, n_c: n_c + n_s] = tail[i, r, :n_s]
-                    out_len[i, r] = n_c + n_s
+                at = int(n_c[i])
+                if at:
+                    out[i, live[i], :at] = torch.cat(heads[i])
+                w = min(tail.shape[2], frames - at)               # a beam holds at most one token per frame: every suffix ends by `frames`
+                keep = torch.arange(w)[None, :] < lens[i][:, None]
+                out[i, :, at: at + w] = torch.where(keep, tail[i, :, :w], 0)
         if self.timesteps:
             return outs[0].to(self.device), scores, outs[1].to(self.device), out_len.to(self.device)
         return outs[0].to(self.device), scores, out_len.to(self.device)

@@ -68,6 +68,12 @@ def frames_total(samples, hop=160, win=400):
     return samples // hop + 1
 
 
+def frames_peek(samples, hop=160, win=400):
+    """Frames a peek of the stream returns after ``samples`` samples: those a flush would emit now (1 or 2), and none while the utterance
+    is too short to be ended (``frames_total`` refuses it: a peek ends nothing, so it has nothing to refuse)."""
+    return 0 if samples <= win // 2 else frames_total(samples, hop, win) - frames_final(samples, hop, win)
+
+
 def retain_from(frames_emitted, hop=160, win=400):
     """First sample a stream must keep once ``frames_emitted`` frames are out.  One more than the next frame's left edge: when the
     length turns out to be a multiple of hop, the last frame's end reflection reaches back to sample L - win/2 - 1.  With
@@ -160,6 +166,7 @@ class FrontendStream:
         for chunk in waveform_chunks:              # (B, n) float32 on the device, any n >= 0
             feats = fs.push(chunk)                 # (B, 80, m): the frames that are final now (frames_final)
         last = fs.flush()                          # (B, 80, 1 or 2): the frames that needed the utterance's end
+        # fs.peek() at any point before: the frames flush() would return then, the stream left as it was
         # torch.cat([*pushes, last], 2) has the L // 160 + 1 frames of frontend(whole waveform); the bits do not depend on the chunking
 
     ``out=(tensor, col0)``: write the frames into columns ``col0`` .. of a caller's contiguous (B, 80, ld) float32 tensor (ld % 4 == 0)
@@ -218,6 +225,17 @@ class FrontendStream:
         feats, col0, view = self._destination(out, m)
         self._step(None, m, feats, col0, self.frames_out, True, True)
         self._flushed = True
+        return view
+
+    def peek(self, out=None):
+        """The frames ``flush()`` would return now (``frames_peek``: 1 or 2, none in the utterance's first ``win // 2`` samples), with the
+        stream left as it was: the launch that ends an utterance retains nothing, and nothing advances."""
+        if self._flushed:
+            raise ValueError('peek after flush: call reset() to start the next utterance')
+        m = frames_peek(self.samples_in, self.hop, self.win)          # (== frames_total - frames_out: a push emits every final frame)
+        feats, col0, view = self._destination(out, m)
+        if m:
+            self._step(None, m, feats, col0, self.frames_out, False, True)
         return view
 
     # ---- one launch ------------------------------------------------------------------------------------------------------------

@@ -115,6 +115,9 @@ SIGNATURES = {
     'nbasr_ctc_beam_stream_timed_init': (_c_int, [ctypes.c_void_p] + [_c_int] * 3 + [_c_stream]),
     'nbasr_ctc_beam_stream_timed_step': (_c_int, [_c_float_p] * 11 + [_c_int] * 7 + [_c_stream]),
     'nbasr_ctc_beam_stream_timed_finish': (_c_int, [ctypes.c_void_p] + [_c_float_p] * 4 + [_c_int] * 4 + [_c_stream]),
+    'nbasr_ctc_beam_stream_peek_workspace_bytes': (ctypes.c_size_t, [_c_int] * 5),
+    'nbasr_ctc_beam_stream_peek': (_c_int, [_c_float_p] * 2 + [ctypes.c_void_p] + [_c_float_p] * 4 + [_c_int] * 8 + [_c_stream]),
+    'nbasr_ctc_beam_stream_timed_peek': (_c_int, [_c_float_p] * 2 + [ctypes.c_void_p] + [_c_float_p] * 5 + [_c_int] * 8 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -1075,6 +1078,46 @@ def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld, timesteps=F
         return beams, scores, steps, lens
     _check(lib.nbasr_ctc_beam_stream_finish(_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2],
                                             batch, beam_width, pool_nodes, _stream(state)), 'nbasr_ctc_beam_stream_finish')
+    return beams, scores, lens
+
+
+def ctc_beam_stream_peek_workspace_bytes(batch, frames, classes, beam_width, pool_nodes):
+    """Bytes of the workspace of ``ctc_beam_stream_peek`` (nbasr.h: nbasr_ctc_beam_stream_peek_workspace_bytes, one size for both families);
+    0 for sizes beyond the limits."""
+    return int(load_library().nbasr_ctc_beam_stream_peek_workspace_bytes(int(batch), int(frames), int(classes), int(beam_width), int(pool_nodes)))
+
+
+def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes, ld, blank=0, cutoff_top_n=40, timesteps=False, ws=None):
+    """What ``ctc_beam_stream_finish`` would return after a ``ctc_beam_stream_step`` of this chunk, with ``state`` only read (nbasr.h:
+    nbasr_ctc_beam_stream_peek, ``timesteps``: nbasr_ctc_beam_stream_timed_peek): log_probs (B, n, C) float32, n >= 0; returns
+    ``ctc_beam_stream_finish``'s tuple with suffixes (B, W, ld).  ``ws``: a device tensor of ``ctc_beam_stream_peek_workspace_bytes`` bytes
+    to use (None: one is allocated)."""
+    _dev(log_probs, 'log_probs')
+    b, t, c = log_probs.shape
+    dev = log_probs.device
+    if chunk_lengths is not None:
+        _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
+    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
+        raise HipError('ctc_beam_stream_peek: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
+    need = ctc_beam_stream_peek_workspace_bytes(b, t, c, beam_width, pool_nodes)
+    if ws is None:
+        ws = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
+    elif ws.device != dev or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
+        raise HipError(f'ctc_beam_stream_peek: the workspace must be a contiguous tensor of {need} bytes on {dev}')
+    beams = torch.empty(b, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
+    scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
+    lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
+    lib = load_library()
+    lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
+    if timesteps:
+        steps = torch.empty_like(beams)
+        _check(lib.nbasr_ctc_beam_stream_timed_peek(lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
+                                                    steps.data_ptr(), lens.data_ptr(), beams.shape[2], b, t, c, beam_width, blank, cutoff_top_n,
+                                                    pool_nodes, _stream(log_probs)), 'nbasr_ctc_beam_stream_timed_peek')
+        return beams, scores, steps, lens
+    _check(lib.nbasr_ctc_beam_stream_peek(lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(),
+                                          beams.shape[2], b, t, c, beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)),
+           'nbasr_ctc_beam_stream_peek')
     return beams, scores, lens
 
 

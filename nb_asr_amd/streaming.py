@@ -11,6 +11,9 @@
     logits, committed, partial, committed_frames, partial_frames = sess.push(chunk, decode='beam-timed')    # + each token's output frame
     logits, (beams, scores, timesteps, out_len) = sess.flush(decode='beam-timed')
 
+    provisional = sess.peek()                    # what flush() would return now; the session stays as it was (any time before flush)
+    provisional, (beams, scores, out_len) = sess.peek(decode='beam')   # ... with flush's decode forms (True, 'beam', 'beam-timed')
+
     sess = model.eval().stream(batch=B, frontend=fe)                   # fe: frontend.LogMelFrontend on the model's device
     logits = sess.push_audio(wave_chunk)         # (B, n) float32 samples: the front-end's stream (frontend.FrontendStream), then push
 
@@ -183,6 +186,18 @@ class StreamPlanner:
             self.finished = True
         return plans
 
+    def copy(self):
+        """A throw-away planner in this one's state: steps on it (an uncommitted push, then the final step) leave this one alone."""
+        other = StreamPlanner.__new__(StreamPlanner)
+        other.specs, other.lookahead = self.specs, self.lookahead
+        other.have, other.done, other.start, other.next_start = list(self.have), list(self.done), list(self.start), list(self.next_start)
+        other.finished = self.finished
+        return other
+
+    def peek(self, n_new=0):
+        """The plans ``step(n_new, final=True)`` would return, with the planner left as it was."""
+        return self.copy().step(n_new, final=True)
+
     def capacities(self, max_chunk):
         """Upper bounds of every stage's window (input frames) for pushes of at most ``max_chunk`` frames and the final flush: the frames a
         step can deliver to stage k + 1 are at most new_k / s + right / s + 2, its retained history at most left + right + s + 1."""
@@ -191,6 +206,26 @@ class StreamPlanner:
             caps.append(new + sp.left + sp.right + sp.stride + 4)
             new = new // sp.stride + sp.right // sp.stride + 3
         return caps
+
+
+class _Peek:
+    """What ``StreamingSession.peek`` runs on instead of the session's carried state: a planner copy, a table of every stage's current
+    window (buffer, row pitch), copies of the LSTM state and of the greedy decoder's previous token.  A ping-pong pair can host ONE
+    uncommitted step (built in the other buffer, the pair not flipped).  A peek of an audio session is two: the front-end's end frames
+    as a push, then the final step, which would overwrite the window the push just built.  The final step's windows are consumed by
+    their own stage at once and never retained, so it builds all of them in one shared scratch window (sized for the largest stage
+    window).  Only a session with ``max_chunk`` 1 pushes its two end frames in two steps; it gets a third buffer per stage."""
+
+    def __init__(self):
+        self.planner = self.window = self.pushes = self.scratch_window = self.thirds = self.prev_token = self.c_state = self.h_state = None
+        self._lstm_started, self.max_frames = False, 1
+
+    def destination(self, k, other):
+        """Where the step under way builds stage k's window: the final step in the scratch window, push 0 in the pair's other buffer,
+        push 1 (retained for the final step, so one per stage) in a third buffer."""
+        if self.pushes is None:
+            return self.scratch_window
+        return other if self.pushes == 0 else self.thirds[k]
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -218,6 +253,7 @@ class StreamingSession:
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
         self._beam = None                         # ctc.BeamSearchStream, made by the first push with decode='beam'
         self._beam_timed = None                   # ... with timesteps=True, by the first push with decode='beam-timed'
+        self._peek = None                         # _Peek: scratch window and state copies, made by the first peek
         arch = [[type(n.op).__name__, *(int(type(br).__name__ == 'Identity') for br in n.branch_ops)] for n in model.model[2].nodes]
         names = []
         for (kind, *flags), node in zip(arch, model.model[2].nodes):
@@ -324,9 +360,11 @@ class StreamingSession:
     # ---- public ----------------------------------------------------------------------------------------------------------------
     @property
     def buffer_bytes(self):
-        """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, and with a
-        front-end its sample tails and the staging buffer)."""
-        return (sum(t.numel() * t.element_size() for t in self._bufs) + sum(d.state_bytes for d in (self._beam, self._beam_timed) if d is not None)
+        """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
+        front-end its sample tails and the staging buffer, and from the first ``peek`` on the peek's scratch window, state copies and
+        beam workspace)."""
+        return (sum(t.numel() * t.element_size() for t in self._bufs)
+                + sum(d.state_bytes + d.peek_bytes for d in (self._beam, self._beam_timed) if d is not None)
                 + (self._frontend.state_bytes if self._frontend is not None else 0))
 
     def reset(self):
@@ -425,16 +463,103 @@ class StreamingSession:
             return logits, self._beam_decoder(decode).finish()
         return (logits, self._decode(logits)) if decode else logits
 
+    def peek(self, decode=False):
+        """What ``flush(decode)`` would return now, without ending anything: the provisional logits (batch, m, 49) of the output frames
+        [frames_out, output_frames(frames_in)) -- with a front-end, ``frames_in`` after its end frames -- computed with the utterance-end
+        zero padding in place of the right context that has not arrived.  ``decode`` as ``flush``: ``True`` -> ``(logits, tokens)``,
+        ``'beam'`` -> ``(logits, (beams, scores, out_len))``, ``'beam-timed'`` -> ``(logits, (beams, scores, timesteps, out_len))`` over
+        all the utterance's frames so far.  The session is left exactly as it was (DESIGN.md 9 "Peek"): every later push / flush / peek
+        returns the bits it would have returned without this call.  Before any frame: (batch, 0, 49) and empty hypotheses, no launch."""
+        if self._flushed:
+            raise ValueError('peek after flush: call reset() to start the next utterance')
+        self._check_params()
+        if decode in BEAM_DECODES:
+            self._beam_check(decode)
+        B, classes = self.batch, self.model.model[self.specs[-1].layer].out_features
+        if self.frames_in == 0:                  # (with a front-end: at most win // 2 samples so far, too few to end an utterance)
+            logits = torch.empty(B, 0, classes, device=self.device, dtype=torch.float32)
+            if decode in BEAM_DECODES:           # the empty prefix alone, at -log P = -0.0: finish() of a search that saw no frame
+                W = self.beam_width
+                scores = torch.full((B, W), torch.finfo(torch.float32).max)
+                scores[:, 0] = -0.0
+                none, lens = torch.zeros(B, W, 0, dtype=torch.int32).to(self.device), torch.zeros(B, W, dtype=torch.int32).to(self.device)
+                return logits, ((none, scores.to(self.device), none.clone(), lens) if decode == 'beam-timed' else (none, scores.to(self.device), lens))
+            return (logits, [torch.zeros(0, dtype=torch.int32) for _ in range(B)]) if decode else logits
+        pk = self._peek_begin()
+        outs = []
+        if self._fed == 'audio':                 # the front-end's end frames as an uncommitted push, then the final step
+            m = self._frontend.peek(out=(self._staging, 0)).shape[2]
+            for off in range(0, m, self.max_chunk):
+                outs.append(self._step(self._staging, off, min(self.max_chunk, m - off), False, pk))
+                pk.pushes += 1
+        pk.pushes = None
+        outs.append(self._step(None, 0, 0, True, pk))
+        logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+        if decode in BEAM_DECODES:
+            self._beam_make(decode)
+            dec = self._beam_decoder(decode)
+            dec.reserve_peek(pk.max_frames, classes)
+            return logits, dec.peek(hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits)
+        if decode:
+            pk.prev_token.copy_(self.prev_token)
+            tokens, counts = hip.ctc_greedy_stream(logits, pk.prev_token)
+            tokens, counts = tokens.cpu(), counts.cpu()
+            return logits, [tokens[i, : int(counts[i])] for i in range(B)]
+        return logits
+
+    def _peek_begin(self):
+        """The peek context (``_Peek``), armed with the session's present state; its buffers are allocated by the first peek."""
+        if self._peek is None:
+            B, pk = self.batch, _Peek()
+            n = max(B * sp.c_in * hip.round_up4(cap) for sp, cap in zip(self.specs, self.caps))
+            numels = [n]
+            if self._frontend is not None and self.max_chunk < 2:
+                pk.thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
+                self._bufs.extend(pk.thirds)
+            if self.model.use_rnn:
+                numels += [B * LSTM_HIDDEN] * 2
+            bufs = [torch.empty(max(k, 4), device=self.device, dtype=torch.float32) for k in numels] + [torch.empty(max(B, 4), device=self.device, dtype=torch.int32)]
+            self._bufs.extend(bufs)
+            pk.prev_token = bufs.pop()[:B]
+            if self.model.use_rnn:
+                pk.c_state, pk.h_state = bufs.pop(), bufs.pop()
+            pk.scratch_window = bufs.pop()
+            # the most output frames a peek can return (its beam workspace is sized once): the emitted count is a function of frames_in alone
+            # and repeats with period 4 once frames are emitted, so the first lookahead + 32 input frames (+ 2 front-end end frames) show it
+            probe, pk.max_frames = StreamPlanner(self.specs), 1
+            for f in range(1, self.lookahead_frames + 33):
+                probe.step(1)
+                total = f + 2
+                for sp in self.specs:
+                    total = out_length(total, sp.stride)
+                pk.max_frames = max(pk.max_frames, total - probe.done[-1])
+            self._peek = pk
+        pk = self._peek
+        pk.planner = self.planner.copy()
+        pk.window = [(bufs[t], ld) for bufs, t, ld in zip(self.windows, self.turn, self._ld_prev)]
+        pk.pushes = 0
+        pk._lstm_started = self._lstm_started
+        if self.model.use_rnn and self._lstm_started:
+            pk.c_state.copy_(self.c_state)
+            pk.h_state.copy_(self.h_state)
+        return pk
+
     def _beam_decoder(self, decode):
         return self._beam_timed if decode == 'beam-timed' else self._beam
 
-    def _beam_ready(self, decode):
+    def _beam_check(self, decode):
         if self._beam_mode not in (None, decode):
             raise ValueError(f"decode={decode!r} after decode={self._beam_mode!r} in one utterance: one search sees every frame "
                              '(call reset() to start the next utterance with the other)')
         if self._beam_frames != self.frames_out:
             raise ValueError(f"decode={decode!r} must see every logit frame of the utterance: use it from the first push on (or reset())")
+
+    def _beam_ready(self, decode):
+        self._beam_check(decode)
         self._beam_mode = decode
+        self._beam_make(decode)
+
+    def _beam_make(self, decode):
         if self._beam_decoder(decode) is None:
             from .ctc import BeamSearchStream
             dec = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device, timesteps=decode == 'beam-timed')
@@ -454,8 +579,9 @@ class StreamingSession:
         return [tokens[i, : int(counts[i])] for i in range(self.batch)]
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
-    def _window(self, k, plan):
-        """Rebuild stage k's window [a, b) into its other buffer; returns the window view."""
+    def _window(self, k, plan, peek=None):
+        """Rebuild stage k's window [a, b) into its other buffer; returns the window view.  ``peek``: an uncommitted step -- the pair is not
+        flipped, and only the first such step may use the other buffer (``_Peek.destination``)."""
         sp, B = self.specs[k], self.batch
         n_w = plan.b - plan.a
         if n_w > self.caps[k]:
@@ -464,25 +590,34 @@ class StreamingSession:
         bufs = self.windows[k]
         if len(bufs) == 1 and plan.n_hist:
             raise RuntimeError(f'stage {k} ({sp.kind}) has no context but retains {plan.n_hist} frames')
-        old = bufs[self.turn[k]]
-        if len(bufs) == 2:
-            self.turn[k] ^= 1
-        dst = bufs[self.turn[k]][: B * sp.c_in * ld].view(B, sp.c_in, ld)
+        if peek is None:
+            old, ld_old = bufs[self.turn[k]], self._ld_prev[k]
+            if len(bufs) == 2:
+                self.turn[k] ^= 1
+            new = bufs[self.turn[k]]
+            self._ld_prev[k] = ld
+        else:
+            old, ld_old = peek.window[k]
+            new = peek.destination(k, bufs[len(bufs) - 1 - self.turn[k]])
+            peek.window[k] = (new, ld)
+        dst = new[: B * sp.c_in * ld].view(B, sp.c_in, ld)
         hist = None
         if plan.n_hist:
-            hist = old[: B * sp.c_in * self._ld_prev[k]].view(B, sp.c_in, self._ld_prev[k])
+            hist = old[: B * sp.c_in * ld_old].view(B, sp.c_in, ld_old)
         src, src_off = self._src
         absmax = self.absmax if (sp.kind == 'dense' and sp.blk > 0) else None
         hip.stream_window(hist, plan.hist_off, plan.n_hist, src, src_off, plan.n_new, dst, absmax)
-        self._ld_prev[k] = ld
         return dst, n_w
 
-    def _step(self, chunk, off, n, final):
+    def _step(self, chunk, off, n, final, peek=None):
+        """One step of the planner on the device; returns its logits.  ``peek`` (a ``_Peek``): the step is not committed -- it runs on the
+        peek's planner copy, window table and LSTM state copies, and no field of the session moves."""
         from .executor import node_into
         from .walk import fused_cell
-        plans = self.planner.step(n, final)
+        plans = (self.planner if peek is None else peek.planner).step(n, final)
         m, B = self.model.model, self.batch
-        self.frames_in += n
+        if peek is None:
+            self.frames_in += n
         self._src = (chunk, off)                 # (tensor, first column) of the frames the next stage appends to its window
         logits = None
         for k, (sp, plan) in enumerate(zip(self.specs, plans)):
@@ -495,7 +630,7 @@ class StreamingSession:
                 logits = torch.empty(B, h.shape[1], head.out_features, device=self.device, dtype=torch.float32)
                 hip.linear_head(h, head.weight.detach(), head.bias.detach(), logits)
                 break
-            win, n_w = self._window(k, plan)
+            win, n_w = self._window(k, plan, peek)
             if not plan.compute:
                 self._src = (None, 0)
                 continue
@@ -537,10 +672,11 @@ class StreamingSession:
                 hip.lstm_input_projection_packed(win, nf, self._packed['w_ih'], lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), gates,
                                                  LSTM_HIDDEN, self.pointwise_ws)
                 h = self.h_out[: B * nf * LSTM_HIDDEN].view(B, nf, LSTM_HIDDEN)
-                h_state, cont = self.h_state[: B * LSTM_HIDDEN], self._lstm_started
-                hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], self.c_state[: B * LSTM_HIDDEN], h, self.xcd_ws,
+                carried = self if peek is None else peek             # (a peek runs from copies: cell_ws is in/out)
+                h_state, c_state, cont = carried.h_state[: B * LSTM_HIDDEN], carried.c_state[: B * LSTM_HIDDEN], carried._lstm_started
+                hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], c_state, h, self.xcd_ws,
                                                    h_state if cont else None, hip.LSTM_CONTINUE if cont else 0)
-                self._lstm_started = True
+                carried._lstm_started = True
                 # h_n = the last frame's h becomes the next call's h0 (h_out seen as one row of nf * H floats per utterance)
                 hip.stream_window(None, 0, 0, h.view(B, 1, nf * LSTM_HIDDEN), (nf - 1) * LSTM_HIDDEN, LSTM_HIDDEN, h_state.view(B, 1, LSTM_HIDDEN))
                 self._src = (h, 0)
@@ -550,5 +686,6 @@ class StreamingSession:
                 hip.linear_head_bct(win, n_w, head.weight.detach(), head.bias.detach(), logits)
         if logits is None:
             logits = torch.empty(B, 0, m[self.specs[-1].layer].out_features, device=self.device, dtype=torch.float32)
-        self.frames_out += logits.shape[1]
+        if peek is None:
+            self.frames_out += logits.shape[1]
         return logits

@@ -5,14 +5,25 @@
 
 A frame is 10 ms of audio (the reference's 10 ms hop): 1 000 frames = 10 s.  Real-time factor = GPU time of the session over the utterance
 / 10 s (lower is better; below 1 keeps up with live audio).  Streamed / whole = GPU time of every push + the flush over one model(x).
-One JSON line per configuration; with --out also the list as a JSON file."""
+One JSON line per configuration; with --out also the list as a JSON file.
+
+    python tools/stream_bench.py --peek [--pairs 50] [--reps 7] [--out profiles/streaming/peek_bench.json] [--baseline parent.json]
+
+``--peek``: the cost of ``StreamingSession.peek`` in mid-stream.  Per configuration four loops take turns, window by window: ``pairs``
+pushes; ``pairs`` times push + ``peek()``; the same two with ``decode='beam'``.  A window is device time between two HIP events around the
+loop (launch gaps count, as they do for a user), after the session has been fed past its lookahead; the median of ``--reps`` windows.
+peek_ms = (push + peek window - push window) / pairs.  ``--package-root DIR`` measures the package of another checkout (one without
+``peek`` gives the push-only columns); ``--baseline FILE`` copies that run's push-only columns next to this run's as ``parent_*``."""
 import argparse
 import json
 import pathlib
+import statistics
 import sys
 import time
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
+if '--package-root' in sys.argv:
+    REPO = pathlib.Path(sys.argv[sys.argv.index('--package-root') + 1]).resolve()
 sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
@@ -36,8 +47,81 @@ def timed(fn, reps):
     return best
 
 
+def window_ms(fn):
+    """Device milliseconds of one call of fn (HIP events on the current stream)."""
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    fn()
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop)
+
+
+def peek_rows(model, args):
+    """One row per (batch, chunk): ms per push, per peek() and per peek(decode='beam') in mid-stream, and their ratios."""
+    dev, pairs, rows = 'cuda:0', args.pairs, []
+    for b in (int(v) for v in args.batches.split(',')):
+        for chunk in (int(v) for v in args.chunks.split(',')):
+            sess = model.stream(batch=b, max_chunk=chunk)
+            lead = -(-(sess.lookahead_frames + chunk) // chunk)                  # pushes until every push emits frames
+            x = keyed_input(b, (lead + pairs) * chunk, seed=0).to(dev)
+            pieces = [x[:, :, i * chunk:(i + 1) * chunk].contiguous() for i in range(lead + pairs)]
+            can_peek = hasattr(sess, 'peek')
+
+            def loop(decode, peek):
+                def fn():
+                    for p in pieces[lead:]:
+                        sess.push(p, decode=decode)
+                        if peek:
+                            sess.peek(decode=decode)
+
+                def window():
+                    sess.reset()
+                    for p in pieces[:lead]:
+                        sess.push(p, decode=decode)
+                    assert sess.frames_out > 0
+                    return window_ms(fn)
+                return window
+            loops = {'push': loop(False, False), 'push_beam': loop('beam', False)}
+            if can_peek:
+                loops.update({'push_peek': loop(False, True), 'push_beam_peek': loop('beam', True)})
+            for w in loops.values():                                            # warm-up: code objects, cached chains, allocator
+                w()
+                w()
+            times = {k: [] for k in loops}
+            for _ in range(args.reps):
+                for k, w in loops.items():
+                    times[k].append(w())
+            med = {k: statistics.median(t) / pairs for k, t in times.items()}
+            row = {'batch': b, 'chunk': chunk, 'pairs_per_window': pairs, 'windows': args.reps, 'lookahead_frames': sess.lookahead_frames,
+                   'build_id': nb.hip.load_library().nbasr_build_id().decode(),
+                   'push_ms': round(med['push'], 3), 'push_ms_range': [round(min(times['push']) / pairs, 3), round(max(times['push']) / pairs, 3)],
+                   'push_beam_ms': round(med['push_beam'], 3)}
+            if can_peek:
+                peek, peek_beam = med['push_peek'] - med['push'], med['push_beam_peek'] - med['push_beam']
+                row.update({'push_peek_ms': round(med['push_peek'], 3), 'push_beam_peek_ms': round(med['push_beam_peek'], 3),
+                            'peek_ms': round(peek, 3), 'peek_beam_ms': round(peek_beam, 3),
+                            'peek_over_push': round(peek / med['push'], 2), 'peek_beam_over_push_beam': round(peek_beam / med['push_beam'], 2),
+                            'provisional_frames': int(sess.peek().shape[1]), 'session_mib': round(sess.buffer_bytes / 2**20, 1)})
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del sess
+    if args.baseline:
+        base = {(r['batch'], r['chunk']): r for r in json.loads(pathlib.Path(args.baseline).read_text())}
+        for r in rows:
+            p = base.get((r['batch'], r['chunk']))
+            if p:
+                r.update({'parent_build_id': p['build_id'], 'parent_push_ms': p['push_ms'], 'parent_push_ms_range': p['push_ms_range'],
+                          'parent_push_beam_ms': p['push_beam_ms'], 'push_over_parent': round(r['push_ms'] / p['push_ms'], 3)})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--peek', action='store_true')
+    ap.add_argument('--pairs', type=int, default=50)
+    ap.add_argument('--package-root', default=None)
+    ap.add_argument('--baseline', default=None)
     ap.add_argument('--frames', type=int, default=1000)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--batches', default='1,16,64')
@@ -49,8 +133,13 @@ def main():
     keyed_fill_(model, seed=1235, mode='lively')
     model = model.to(dev).eval()
     rows = []
+    if args.peek:
+        if '--reps' not in sys.argv:
+            args.reps = 7
+        with torch.no_grad():
+            rows = peek_rows(model, args)
     with torch.no_grad():
-        for b in (int(v) for v in args.batches.split(',')):
+        for b in (int(v) for v in args.batches.split(',') if not args.peek):
             x = keyed_input(b, args.frames, seed=0).to(dev)
             model(x)                                                            # warm the whole forward (tapes, packed weights)
             model(x)
@@ -75,6 +164,7 @@ def main():
                 rows.append(row)
                 del sess
     if args.out:
+        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         pathlib.Path(args.out).write_text(json.dumps(rows, indent=1) + '\n')
 
 
