@@ -2,7 +2,7 @@
 //   log_probs = log_softmax(logits, dim = classes);   output_len = audio_len // 4;   decode.
 // This file: log_softmax, the length mapping and GREEDY CTC decoding (per-frame argmax, collapse repeats, drop the blank =
 // class 0, F.ctc_loss's default blank).  The beam search the reference's Trainer.decode uses (ctcdecode), the phoneme folding
-// and the error rate are in ctc_decode.hip.
+// and the error rate are in ctc_decode.hip; the CTC loss and its gradient (trainer.py:36-42) are in ctc_loss.hip.
 //
 // One 256-thread workgroup per utterance: a thread owns a frame (49 contiguous floats), computes max / log-sum-exp / argmax
 // in registers, then the surviving tokens are compacted with a workgroup prefix sum so the output order is the frame order.

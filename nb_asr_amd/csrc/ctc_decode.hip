@@ -316,6 +316,24 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
     if (TIMED) st.p_best = p_best;
 }
 
+// `len` frames of one utterance, rows of `classes` log-probabilities from lp_b on; frame t is the utterance's frame t0 + t (TIMED).
+// The next frame's row is loaded before the current frame runs.  A macro, not a function: a helper is optimised on its own before it
+// is inlined, and the frame body then lands 8 to 12 bytes earlier in the search and step kernels, which costs them 2 % (measured:
+// profiles/streaming/beam_refactor_ab.json).  Expanded in place, the loop is compiled as it was when each kernel spelled it out.
+#define BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0)                                                   \
+    do {                                                                                                                           \
+        float lp_next = ((len) > 0 && (lane) < (classes)) ? (lp_b)[lane] : NEG;                                                    \
+        for (int t = 0; t < (len); ++t) {                                                                                          \
+            const float lp = lp_next;                                     /* class `lane` of frame t */                            \
+            if (t + 1 < (len) && (lane) < (classes))                      /* in flight during this frame */                        \
+                lp_next = (lp_b)[static_cast<size_t>(t + 1) * (classes) + (lane)];                                                 \
+            beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, (t0) + t);                                                \
+        }                                                                                                                          \
+    } while (0)
+
+// The rows of the search, the finish and the peek ("walk a beam's nodes backwards into its row, pad with 0") stay written out in their
+// kernels.  One shared writer was measured: it moves the code around the frame loop of the search and the peek and costs the timed search
+// 2.5 %, the timed peek 2 % and the width-1 search 3 % (profiles/streaming/beam_refactor_ab.json), for 15 lines saved.
 // TIMED: timesteps(batch, width, frames) = the frame of every token's record, 0 beyond the beam's length.  (What the timed instantiations
 // take in addition comes last in every kernel's arguments: the untimed ones read theirs where they always did.)
 template <bool TIMED>
@@ -337,12 +355,7 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     st.n_live = 1; st.n_nodes = 1;
     if (lane == 0) pool[0] = make_int2(-1, -1);
 
-    float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
-    for (int t = 0; t < len; ++t) {
-        const float lp = lp_next;                                                                       // class `lane` of frame t
-        if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];  // in flight during this frame
-        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t);
-    }
+    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, 0);
 
     // results, best first (the selection of the last frame already ordered them; a zero-length utterance has the empty prefix)
     __syncthreads();                                                   // pool entries written by other lanes
@@ -430,6 +443,24 @@ __device__ __forceinline__ void beam_stream_store(const BeamStreamRecord& rec, c
     }
 }
 
+// The inverse of beam_stream_store: the lanes as the previous chunk left them (lanes >= n_live: the defaults the frame body gives them).
+// n_live and n_nodes come from the record's header; the caller passes them, as it trusts them (the step) or clamped (the peek).
+template <bool TIMED>
+__device__ __forceinline__ BeamLanes beam_stream_load(const BeamStreamRecord& rec, int n_live, int n_nodes, int lane)
+{
+    BeamLanes st;
+    beam_lane_reset(st);
+    if (lane < n_live) {
+        st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
+        st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
+        st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
+        if (TIMED) st.p_best = rec.best[lane];
+    }
+    st.n_live = n_live; st.n_nodes = n_nodes;
+    st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
+    return st;
+}
+
 template <bool TIMED>
 __global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restrict__ state, int width, int pool_nodes)
 {
@@ -442,6 +473,26 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restri
     if (lane < BS_HEADER_INTS) rec.hdr[lane] = lane == BS_N_LIVE || lane == BS_N_NODES ? 1 : 0;
     if (lane == 0) rec.pool[0] = make_int2(-1, -1);
 }
+
+// lcp = the longest common token prefix of all n_live lanes beyond the `c_old` tokens committed before, in tokens (walked from the shortest
+// suffix's depth upwards; once every lane stands on one node, the tokens above agree).  By all lanes, after the pool's writes are visible.
+// A macro for BEAM_FRAMES' reason: as a function it moves the compaction loops behind it and the timed step loses 0.3 %.
+#define BEAM_COMMON_PREFIX(lcp, st, pool, NS, c_old, lane)                                                                         \
+    do {                                                                                                                           \
+        const bool live_ = (lane) < (st).n_live;                                                                                   \
+        int d_min = INT_MAX;                                                                                                       \
+        for (int i = 0; i < (st).n_live; ++i) d_min = min(d_min, rl((st).p_len, i));                                               \
+        d_min -= (c_old);                                             /* >= 0: every live prefix extends the committed one */      \
+        int node = live_ ? (st).p_node : 0;                                                                                        \
+        for (int skip = live_ ? (st).p_len - (c_old) - d_min : 0; skip > 0; --skip) node = (pool)[node * (NS)].x;                  \
+        lcp = d_min;                                                                                                               \
+        for (int k = d_min; k >= 1; --k) {                                                                                         \
+            if (__ballot(live_ && node != rl(node, 0)) == 0ull) break;                                                             \
+            const int2 e = live_ ? (pool)[node * (NS)] : make_int2(0, 0);                                                          \
+            if (__ballot(live_ && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;                                                         \
+            node = e.x;                                                                                                            \
+        }                                                                                                                          \
+    } while (0)
 
 // One chunk of frames for every utterance (one wavefront each).  `ids`: pool_nodes ints of scratch per utterance (the renumbering).
 // committed / partial: rows of pool_nodes ints (the host keeps usage + width * n + 1 <= pool_nodes, which bounds both counts).
@@ -469,42 +520,15 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     }
     const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
 
-    // ---- the lanes as the previous chunk left them (lanes >= n_live: the defaults the frame body gives them)
-    BeamLanes st;
-    beam_lane_reset(st);
-    if (lane < n_live0) {
-        st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
-        st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
-        st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
-        if (TIMED) st.p_best = rec.best[lane];
-    }
-    st.n_live = n_live0; st.n_nodes = n_nodes0;
-    st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
-
-    float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
-    for (int t = 0; t < len; ++t) {
-        const float lp = lp_next;
-        if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];
-        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t0 + t);
-    }
+    BeamLanes st = beam_stream_load<TIMED>(rec, n_live0, n_nodes0, lane);
+    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0);
     __syncthreads();                                                   // pool entries written by other lanes
 
-    // ---- the committed prefix: longest common token prefix of all n_live lanes (walked from the shortest suffix's depth upwards;
-    //      once every lane stands on one node, the tokens above agree)
+    // ---- the committed prefix
     const int n_live = st.n_live;
     const bool live = lane < n_live;
-    int d_min = INT_MAX;
-    for (int i = 0; i < n_live; ++i) d_min = min(d_min, rl(st.p_len, i));
-    d_min -= c_old;                                                    // >= 0: every live prefix extends the committed one
-    int node = live ? st.p_node : 0;
-    for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node * NS].x;
-    int lcp = d_min;
-    for (int k = d_min; k >= 1; --k) {
-        if (__ballot(live && node != rl(node, 0)) == 0ull) break;
-        const int2 e = live ? pool[node * NS] : make_int2(0, 0);
-        if (__ballot(live && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;
-        node = e.x;
-    }
+    int lcp;
+    BEAM_COMMON_PREFIX(lcp, st, pool, NS, c_old, lane);
     const int c_new = c_old + lcp;
 
     // ---- mark the nodes below the committed prefix that a live lane reaches; lane 0 (the best prefix) also writes its tokens:
@@ -642,45 +666,17 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_peek_kernel(
     for (int i = lane; i < n_nodes0 * NS; i += 64) pool[i] = src_pool[i];
     __syncthreads();
 
-    BeamLanes st;
-    beam_lane_reset(st);
-    if (lane < n_live0) {
-        st.p_hash = rec.hash[lane]; st.p_phash = rec.phash[lane];
-        st.p_b = rec.pb[lane]; st.p_nb = rec.pnb[lane]; st.p_score = rec.pscore[lane];
-        st.p_last = rec.last[lane]; st.p_node = rec.node[lane]; st.p_len = rec.len[lane]; st.p_mp = rec.mp[lane];
-        if (TIMED) st.p_best = rec.best[lane];
-    }
-    st.n_live = n_live0; st.n_nodes = n_nodes0;
-    st.merged = merged_mask(st.p_mp, st.p_last, st.n_live, lane);
-
-    float lp_next = (len > 0 && lane < classes) ? lp_b[lane] : NEG;
-    for (int t = 0; t < len; ++t) {
-        const float lp = lp_next;
-        if (t + 1 < len && lane < classes) lp_next = lp_b[static_cast<size_t>(t + 1) * classes + lane];
-        beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, t0 + t);
-    }
+    BeamLanes st = beam_stream_load<TIMED>(rec, n_live0, n_nodes0, lane);
+    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0);
     __syncthreads();                                                   // pool entries written by other lanes
 
     // TIMED: the step commits the longest common token prefix of the live prefixes and reports the committed tokens' frames from the BEST
     // prefix's nodes, for every beam.  Two live prefixes can spell that common part through different nodes with different records (a prefix
-    // that left the beam and was created again has a fresh node), so the first `lcp` frames of every row are lane 0's here too; the walk is
-    // the step's.  The tokens agree by definition, so the untimed peek needs none of this.
+    // that left the beam and was created again has a fresh node), so the first `lcp` frames of every row are lane 0's here too.  The
+    // tokens agree by definition, so the untimed peek needs none of this.
     const bool live = lane < st.n_live;
     int lcp = 0;
-    if (TIMED) {
-        int d_min = INT_MAX;
-        for (int i = 0; i < st.n_live; ++i) d_min = min(d_min, rl(st.p_len, i));
-        d_min -= c_old;
-        int node = live ? st.p_node : 0;
-        for (int skip = live ? st.p_len - c_old - d_min : 0; skip > 0; --skip) node = pool[node * NS].x;
-        lcp = d_min;
-        for (int k = d_min; k >= 1; --k) {
-            if (__ballot(live && node != rl(node, 0)) == 0ull) break;
-            const int2 e = live ? pool[node * NS] : make_int2(0, 0);
-            if (__ballot(live && e.y != rl(e.y, 0)) != 0ull) lcp = k - 1;
-            node = e.x;
-        }
-    }
+    if (TIMED) BEAM_COMMON_PREFIX(lcp, st, pool, NS, c_old, lane);                            // by all lanes
 
     if (lane >= width) return;
     const int n = live ? st.p_len - c_old : 0;
@@ -704,195 +700,6 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_peek_kernel(
     if (TIMED) for (int k = max(n, 0); k < ld; ++k) out_t[k] = 0;
     scores[static_cast<size_t>(b) * width + lane] = live ? -st.p_score : FLT_MAX;
     beam_lens[static_cast<size_t>(b) * width + lane] = live ? n : -1;
-}
-
-// ---- CTC loss (forward value) -----------------------------------------------------------------------------------------------
-// The reference's loss (training/torch/trainer.py:36-42): F.ctc_loss(log_probs (T, B, C), targets, output_len, targets_len,
-// reduction='none', zero_infinity=True) / output_len, then the mean over the batch (the mean is left to the caller).
-// Standard alpha recursion in log space over the blank-extended label sequence l' (2L + 1 positions), as ATen's ctc_loss does
-// it: alpha_t(s) = logsumexp(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2) if l'_s != blank and l'_s != l'_{s-2}) +
-// log_probs[t][l'_s];  nll = -logsumexp(alpha_{T-1}(2L), alpha_{T-1}(2L-1)).  One wavefront per utterance, positions strided
-// over the lanes, alpha double-buffered in LDS (a single wavefront needs no barrier: its LDS operations execute in issue
-// order, wave_sync only keeps the compiler from reordering them).
-constexpr int CTC_MAX_LABELS = 1024;
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__global__ __launch_bounds__(64) void ctc_loss_kernel(const float* __restrict__ log_probs, const int* __restrict__ lengths,
-                                                      const int* __restrict__ targets, const int* __restrict__ target_lengths,
-                                                      float* __restrict__ losses, int frames, int classes, int ld_targets, int blank,
-                                                      int divide_by_length)
-{
-    __shared__ float s_alpha[2][2 * CTC_MAX_LABELS + 1];
-    __shared__ int s_label[2 * CTC_MAX_LABELS + 1];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int len = min(max(lengths[b], 0), frames);
-    const int n_lab = min(max(target_lengths[b], 0), ld_targets);
-    const int n_pos = 2 * n_lab + 1;
-    const float ninf = -INFINITY;
-    const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
-    bool bad = false;
-    for (int s = lane; s < n_pos; s += 64) {
-        int lab = blank;
-        if (s & 1) {
-            lab = targets[static_cast<size_t>(b) * ld_targets + (s >> 1)];
-            if (lab < 0 || lab >= classes) { bad = true; lab = blank; }
-        }
-        s_label[s] = lab;
-    }
-    wave_sync();
-    float nll = INFINITY;
-    if (len > 0) {
-        // t = 0: only the first blank and the first label are reachable
-        for (int s = lane; s < n_pos; s += 64) s_alpha[0][s] = s < 2 ? lp_b[s_label[s]] : ninf;
-        wave_sync();
-        int cur = 0;
-        for (int t = 1; t < len; ++t) {
-            const float* __restrict__ row = lp_b + static_cast<size_t>(t) * classes;
-            const float* prev = s_alpha[cur];
-            float* next = s_alpha[cur ^ 1];
-            for (int s = lane; s < n_pos; s += 64) {
-                const int lab = s_label[s];
-                const float lp = row[lab];
-                const float a = prev[s];
-                const float a1 = s > 0 ? prev[s - 1] : ninf;
-                const float a2 = (s > 1 && lab != blank && lab != s_label[s - 2]) ? prev[s - 2] : ninf;
-                const float m = fmaxf(a, fmaxf(a1, a2));
-                next[s] = m == ninf ? ninf : logf(expf(a - m) + expf(a1 - m) + expf(a2 - m)) + m + lp;
-            }
-            cur ^= 1;
-            wave_sync();
-        }
-        if (lane == 0) {
-            const float l1 = s_alpha[cur][n_pos - 1], l2 = n_pos > 1 ? s_alpha[cur][n_pos - 2] : ninf;
-            const float m = fmaxf(l1, l2);
-            nll = m == ninf ? INFINITY : -(logf(expf(l1 - m) + expf(l2 - m)) + m);
-        }
-    } else if (n_lab == 0) {
-        nll = 0.f;                                                // nothing to emit in no frames: probability 1
-    }
-    const bool any_bad = __any(bad);
-    if (lane == 0) {
-        float out = (nll == INFINITY) ? 0.f : nll;               // zero_infinity=True
-        if (divide_by_length) out = out / static_cast<float>(lengths[b]);       // the reference divides by output_len as given
-        losses[b] = any_bad ? NAN : out;
-    }
-}
-
-// ---- CTC loss gradient (first step of the backward pass) -------------------------------------------------
-// d L / d logits for L = mean_b( nll_b / len_b ), log_probs = log_softmax(logits)  (reference trainer.py:36-42, 217-222: this is
-// what `_regu_loss.backward()` propagates into the model, without the weight-norm term).  With alpha as above and beta the
-// mirrored recursion from the last frame,
-//     grad[b][t][c] = ( exp(lp[t][c]) - exp( log sum_{s: l'_s = c} exp(alpha_t(s) + beta_t(s)) + nll - lp[t][c] ) ) / (B len_b)
-// for t < len_b, 0 beyond (ATen's ctc_loss backward composed with log_softmax's; Graves et al. 2006, eq. 16); 0 for utterances
-// whose loss is infinite (zero_infinity).  One wavefront per utterance: alpha of every frame goes to a global workspace in
-// the forward sweep, the backward sweep keeps beta in LDS and turns each frame into its gradient row: lane c sums, in a fixed
-// order, the positions that carry class c (deterministic; classes <= 64).
-__global__ __launch_bounds__(64) void ctc_grad_kernel(const float* __restrict__ log_probs, const int* __restrict__ lengths,
-                                                      const int* __restrict__ targets, const int* __restrict__ target_lengths,
-                                                      float* __restrict__ alpha_ws, float* __restrict__ losses, float* __restrict__ grad,
-                                                      int batch, int frames, int classes, int ld_targets, int blank)
-{
-    __shared__ float s_beta[2][2 * CTC_MAX_LABELS + 1];
-    __shared__ float s_ab[2 * CTC_MAX_LABELS + 1];
-    __shared__ int s_label[2 * CTC_MAX_LABELS + 1];
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const int len = min(max(lengths[b], 0), frames);
-    const int n_lab = min(max(target_lengths[b], 0), ld_targets);
-    const int n_pos = 2 * n_lab + 1;
-    const float ninf = -INFINITY;
-    const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
-    float* __restrict__ g_b = grad + static_cast<size_t>(b) * frames * classes;
-    float* __restrict__ al = alpha_ws + static_cast<size_t>(b) * frames * (2 * static_cast<size_t>(ld_targets) + 1);
-    const int pitch = 2 * ld_targets + 1;
-    bool bad = false;
-    for (int s = lane; s < n_pos; s += 64) {
-        int lab = blank;
-        if (s & 1) {
-            lab = targets[static_cast<size_t>(b) * ld_targets + (s >> 1)];
-            if (lab < 0 || lab >= classes) { bad = true; lab = blank; }
-        }
-        s_label[s] = lab;
-    }
-    wave_sync();
-    const bool any_bad = __any(bad);
-    // ---- forward sweep: alpha_t for every frame --------------------------------------------------------------------
-    float nll = INFINITY;
-    if (len > 0) {
-        for (int s = lane; s < n_pos; s += 64) al[s] = s < 2 ? lp_b[s_label[s]] : ninf;
-        __threadfence_block();
-        for (int t = 1; t < len; ++t) {
-            const float* __restrict__ row = lp_b + static_cast<size_t>(t) * classes;
-            const float* prev = al + static_cast<size_t>(t - 1) * pitch;
-            float* next = al + static_cast<size_t>(t) * pitch;
-            __syncthreads();                                           // previous row (global memory) written by other lanes
-            for (int s = lane; s < n_pos; s += 64) {
-                const int lab = s_label[s];
-                const float a = prev[s];
-                const float a1 = s > 0 ? prev[s - 1] : ninf;
-                const float a2 = (s > 1 && lab != blank && lab != s_label[s - 2]) ? prev[s - 2] : ninf;
-                const float m = fmaxf(a, fmaxf(a1, a2));
-                next[s] = m == ninf ? ninf : logf(expf(a - m) + expf(a1 - m) + expf(a2 - m)) + m + row[lab];
-            }
-        }
-        __syncthreads();
-        const float* last = al + static_cast<size_t>(len - 1) * pitch;
-        const float l1 = last[n_pos - 1], l2 = n_pos > 1 ? last[n_pos - 2] : ninf;
-        const float m = fmaxf(l1, l2);
-        nll = m == ninf ? INFINITY : -(logf(expf(l1 - m) + expf(l2 - m)) + m);
-    } else if (n_lab == 0) {
-        nll = 0.f;
-    }
-    const bool finite = nll != INFINITY && !any_bad && len > 0;
-    if (lane == 0) losses[b] = any_bad ? NAN : (nll == INFINITY ? 0.f : nll / static_cast<float>(lengths[b]));
-    const float scale = finite ? 1.0f / (static_cast<float>(batch) * static_cast<float>(lengths[b])) : 0.f;
-    // ---- backward sweep: beta in LDS, one gradient row per frame --------------------------------------------------------
-    int cur = 0;
-    for (int t = frames - 1; t >= 0; --t) {
-        float* grow = g_b + static_cast<size_t>(t) * classes;
-        if (t >= len || !finite) {                                      // beyond the utterance, or no gradient at all
-            if (lane < classes) grow[lane] = 0.f;
-            for (int c = 64 + lane; c < classes; c += 64) grow[c] = 0.f;
-            continue;
-        }
-        const float* __restrict__ row = lp_b + static_cast<size_t>(t) * classes;
-        const float* arow = al + static_cast<size_t>(t) * pitch;
-        float* beta = s_beta[cur];
-        const float* bnext = s_beta[cur ^ 1];
-        for (int s = lane; s < n_pos; s += 64) {
-            const int lab = s_label[s];
-            float bt;
-            if (t == len - 1) {
-                bt = (s >= n_pos - 2) ? row[lab] : ninf;               // only the last blank and the last label can end the path
-            } else {
-                const float b0 = bnext[s];
-                const float b1 = s + 1 < n_pos ? bnext[s + 1] : ninf;
-                const float b2 = (s + 2 < n_pos && s_label[s + 2] != blank && s_label[s + 2] != lab) ? bnext[s + 2] : ninf;
-                const float m = fmaxf(b0, fmaxf(b1, b2));
-                bt = m == ninf ? ninf : logf(expf(b0 - m) + expf(b1 - m) + expf(b2 - m)) + m + row[lab];
-            }
-            beta[s] = bt;
-            s_ab[s] = arow[s] + bt;                                     // alpha and beta both contain lp[t][l'_s]: divided out below
-        }
-        wave_sync();
-        for (int c = lane; c < classes; c += 64) {
-            float m = ninf;
-            for (int s = (c == blank ? 0 : 1); s < n_pos; s += 2) if (s_label[s] == c) m = fmaxf(m, s_ab[s]);      // blanks sit at even positions
-            float sum = 0.f;
-            if (m != ninf)
-                for (int s = (c == blank ? 0 : 1); s < n_pos; s += 2) if (s_label[s] == c) sum += expf(s_ab[s] - m);
-            const float lp = row[c];
-            const float lcab = m == ninf ? ninf : logf(sum) + m;
-            grow[c] = (expf(lp) - (lcab == ninf ? 0.f : expf(lcab + nll - lp))) * scale;
-        }
-        cur ^= 1;
-        wave_sync();
-    }
 }
 
 // ---- label table + blank removal + Levenshtein distance, one workgroup per utterance -------------------------------------
@@ -991,6 +798,17 @@ extern "C" size_t nbasr_ctc_beam_timed_workspace_bytes(int batch, int frames, in
     return beam_workspace_bytes(batch, frames, classes, beam_width, true);
 }
 
+// The prune pre-pass of a search over batch * frames rows, when the cutoff leaves classes out: `pruned` receives the rows the search
+// should read.  -> the search's source (the log-probabilities themselves when nothing is cut)
+static const float* beam_prune(const float* log_probs, float* pruned, int batch, int frames, int classes, int cutoff_top_n, hipStream_t s)
+{
+    if (cutoff_top_n >= classes || frames <= 0) return log_probs;
+    const long long n_frames = static_cast<long long>(batch) * frames;
+    hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
+                       classes, cutoff_top_n);
+    return pruned;
+}
+
 // the untimed and the timed entry points share their checks; `timed` selects the kernel instantiation
 static int beam_search(const char* fn, bool timed, const float* log_probs, const int* lengths, void* ws, int* beams, float* scores,
                        int* timesteps, int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
@@ -1005,20 +823,11 @@ static int beam_search(const char* fn, bool timed, const float* log_probs, const
     NBASR_REQUIRE(ws && scores && beam_lens && (frames == 0 || (log_probs && beams && (!timed || timesteps))), NBASR_ENULL, "%s: NULL pointer", fn);
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN, "%s: workspace must be 8-byte aligned", fn);
     hipStream_t s = as_stream(stream);
-    const float* src = log_probs;
-    if (cutoff_top_n < classes && frames > 0) {
-        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_pool_bytes(batch, frames, beam_width, timed));
-        const long long n_frames = static_cast<long long>(batch) * frames;
-        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
-                           classes, cutoff_top_n);
-        src = pruned;
-    }
-    if (timed)
-        hipLaunchKernelGGL(ctc_beam_search_kernel<true>, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
-                           beam_lens, frames, classes, beam_width, blank, timesteps);
-    else
-        hipLaunchKernelGGL(ctc_beam_search_kernel<false>, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores,
-                           beam_lens, frames, classes, beam_width, blank, timesteps);
+    float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_pool_bytes(batch, frames, beam_width, timed));
+    const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
+    auto kernel = timed ? ctc_beam_search_kernel<true> : ctc_beam_search_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores, beam_lens, frames, classes,
+                       beam_width, blank, timesteps);
     return launch_status(fn);
 }
 
@@ -1068,10 +877,8 @@ static int beam_stream_init(const char* fn, bool timed, void* state, int batch, 
     if (batch == 0) return NBASR_OK;
     NBASR_REQUIRE(state, NBASR_ENULL, "%s: NULL pointer", fn);
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
-    if (timed)
-        hipLaunchKernelGGL(ctc_beam_stream_init_kernel<true>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
-    else
-        hipLaunchKernelGGL(ctc_beam_stream_init_kernel<false>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
+    auto kernel = timed ? ctc_beam_stream_init_kernel<true> : ctc_beam_stream_init_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<char*>(state), beam_width, pool_nodes);
     return launch_status(fn);
 }
 
@@ -1100,22 +907,12 @@ static int beam_stream_step(const char* fn, bool timed, const float* log_probs, 
                       (!timed || (committed_frames && partial_frames)), NBASR_ENULL, "%s: NULL pointer", fn);
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
     hipStream_t s = as_stream(stream);
-    const float* src = log_probs;
-    if (cutoff_top_n < classes && frames > 0) {
-        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + static_cast<size_t>(batch) * pool_nodes * sizeof(int));
-        const long long n_frames = static_cast<long long>(batch) * frames;
-        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
-                           classes, cutoff_top_n);
-        src = pruned;
-    }
-    if (timed)
-        hipLaunchKernelGGL(ctc_beam_stream_kernel<true>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state),
-                           static_cast<int*>(ws), committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank,
-                           pool_nodes, committed_frames, partial_frames);
-    else
-        hipLaunchKernelGGL(ctc_beam_stream_kernel<false>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state),
-                           static_cast<int*>(ws), committed, committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank,
-                           pool_nodes, committed_frames, partial_frames);
+    float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + static_cast<size_t>(batch) * pool_nodes * sizeof(int));
+    const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
+    auto kernel = timed ? ctc_beam_stream_kernel<true> : ctc_beam_stream_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state), static_cast<int*>(ws), committed,
+                       committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank, pool_nodes, committed_frames,
+                       partial_frames);
     return launch_status(fn);
 }
 
@@ -1147,12 +944,9 @@ static int beam_stream_finish(const char* fn, bool timed, const void* state, int
     if (batch == 0) return NBASR_OK;
     NBASR_REQUIRE(state && scores && beam_lens && (ld_beams == 0 || (beams && (!timed || timesteps))), NBASR_ENULL, "%s: NULL pointer", fn);
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0, NBASR_EALIGN, "%s: state must be 8-byte aligned", fn);
-    if (timed)
-        hipLaunchKernelGGL(ctc_beam_stream_finish_kernel<true>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
-                           scores, beam_lens, ld_beams, beam_width, pool_nodes, timesteps);
-    else
-        hipLaunchKernelGGL(ctc_beam_stream_finish_kernel<false>, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams,
-                           scores, beam_lens, ld_beams, beam_width, pool_nodes, timesteps);
+    auto kernel = timed ? ctc_beam_stream_finish_kernel<true> : ctc_beam_stream_finish_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, as_stream(stream), static_cast<const char*>(state), beams, scores, beam_lens, ld_beams,
+                       beam_width, pool_nodes, timesteps);
     return launch_status(fn);
 }
 
@@ -1200,20 +994,11 @@ static int beam_stream_peek(const char* fn, bool timed, const float* log_probs, 
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(state) & 7u) == 0 && (reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN,
                   "%s: state and workspace must be 8-byte aligned", fn);
     hipStream_t s = as_stream(stream);
-    const float* src = log_probs;
-    if (cutoff_top_n < classes && frames > 0) {
-        float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes));
-        const long long n_frames = static_cast<long long>(batch) * frames;
-        hipLaunchKernelGGL(ctc_prune_kernel, dim3(static_cast<unsigned>((n_frames + 3) / 4)), dim3(256), 0, s, log_probs, pruned, n_frames,
-                           classes, cutoff_top_n);
-        src = pruned;
-    }
-    if (timed)
-        hipLaunchKernelGGL(ctc_beam_stream_peek_kernel<true>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state),
-                           static_cast<int2*>(ws), beams, scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
-    else
-        hipLaunchKernelGGL(ctc_beam_stream_peek_kernel<false>, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state),
-                           static_cast<int2*>(ws), beams, scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
+    float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes));
+    const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
+    auto kernel = timed ? ctc_beam_stream_peek_kernel<true> : ctc_beam_stream_peek_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state), static_cast<int2*>(ws), beams,
+                       scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
     return launch_status(fn);
 }
 
@@ -1231,43 +1016,6 @@ extern "C" int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const in
 {
     return beam_stream_peek("nbasr_ctc_beam_stream_timed_peek", true, log_probs, chunk_lengths, state, ws, beams, scores, timesteps, beam_lens,
                             ld_beams, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
-}
-
-extern "C" int nbasr_ctc_loss(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, float* losses,
-                              int batch, int frames, int classes, int ld_targets, int blank, int divide_by_length, nbasr_stream_t stream)
-{
-    clear_error();
-    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && ld_targets >= 0 && blank >= 0 && blank < classes, NBASR_EINVAL,
-                  "nbasr_ctc_loss: bad sizes (batch=%d frames=%d classes=%d ld_targets=%d blank=%d)", batch, frames, classes, ld_targets, blank);
-    NBASR_REQUIRE(ld_targets <= CTC_MAX_LABELS, NBASR_EINVAL, "nbasr_ctc_loss: at most %d labels per utterance, got ld_targets=%d", CTC_MAX_LABELS, ld_targets);
-    if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(lengths && target_lengths && losses && (frames == 0 || log_probs) && (ld_targets == 0 || targets), NBASR_ENULL,
-                  "nbasr_ctc_loss: NULL pointer");
-    hipLaunchKernelGGL(ctc_loss_kernel, dim3(batch), dim3(64), 0, as_stream(stream), log_probs, lengths, targets, target_lengths, losses,
-                       frames, classes, ld_targets, blank, divide_by_length);
-    return launch_status("nbasr_ctc_loss");
-}
-
-extern "C" size_t nbasr_ctc_grad_workspace_bytes(int batch, int frames, int ld_targets)
-{
-    if (batch <= 0 || frames <= 0 || ld_targets < 0) return 0;
-    return static_cast<size_t>(batch) * frames * (2 * static_cast<size_t>(ld_targets) + 1) * sizeof(float);
-}
-
-extern "C" int nbasr_ctc_loss_grad(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, void* ws,
-                                   float* losses, float* grad_logits, int batch, int frames, int classes, int ld_targets, int blank,
-                                   nbasr_stream_t stream)
-{
-    clear_error();
-    NBASR_REQUIRE(batch >= 0 && frames >= 0 && classes > 0 && ld_targets >= 0 && blank >= 0 && blank < classes, NBASR_EINVAL,
-                  "nbasr_ctc_loss_grad: bad sizes (batch=%d frames=%d classes=%d ld_targets=%d blank=%d)", batch, frames, classes, ld_targets, blank);
-    NBASR_REQUIRE(ld_targets <= CTC_MAX_LABELS, NBASR_EINVAL, "nbasr_ctc_loss_grad: at most %d labels per utterance, got ld_targets=%d", CTC_MAX_LABELS, ld_targets);
-    if (batch == 0) return NBASR_OK;
-    NBASR_REQUIRE(lengths && target_lengths && losses && (frames == 0 || (log_probs && grad_logits && ws)) && (ld_targets == 0 || targets), NBASR_ENULL,
-                  "nbasr_ctc_loss_grad: NULL pointer");
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3(batch), dim3(64), 0, as_stream(stream), log_probs, lengths, targets, target_lengths,
-                       static_cast<float*>(ws), losses, grad_logits, batch, frames, classes, ld_targets, blank);
-    return launch_status("nbasr_ctc_loss_grad");
 }
 
 extern "C" int nbasr_token_error_counts(const int* hyp, const int* hyp_len, int ld_hyp, const int* ref, const int* ref_len, int ld_ref,

@@ -136,9 +136,9 @@ class BeamSearchStream:
         self.state, self.pool_nodes = new, new_nodes
         self.grown += 1
 
-    def push(self, log_probs, lengths=None):
-        """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``, with
-        ``timesteps`` ``(committed, partial, committed_frames, partial_frames)``."""
+    def _chunk(self, log_probs, lengths, empty_has_classes=True):
+        """Is this a valid chunk with valid lengths for this stream?  -> (frames, classes, the utterances' frames in the chunk: int64 (B) on
+        the host).  ``empty_has_classes``: a chunk of no frames must have the stream's classes too."""
         if self._finished:
             raise ValueError('push after finish(): call reset() to start the next utterances')
         if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.shape[0] != self.batch:
@@ -146,7 +146,7 @@ class BeamSearchStream:
         if log_probs.dtype != torch.float32 or log_probs.device != self.device:
             raise ValueError(f'log-probabilities must be float32 on {self.device} (got {log_probs.dtype} on {log_probs.device})')
         n, c = log_probs.shape[1], log_probs.shape[2]
-        if self.classes is not None and c != self.classes:
+        if self.classes is not None and c != self.classes and (n or empty_has_classes):
             raise ValueError(f'every chunk must have {self.classes} classes (got {c})')
         if lengths is None:
             rows = torch.full((self.batch,), n, dtype=torch.int64)
@@ -158,6 +158,12 @@ class BeamSearchStream:
                 raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
         if bool((self.ended & (rows > 0)).any()):
             raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        return n, c, rows
+
+    def push(self, log_probs, lengths=None):
+        """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``, with
+        ``timesteps`` ``(committed, partial, committed_frames, partial_frames)``."""
+        n, c, rows = self._chunk(log_probs, lengths)
         self.classes = c
         if n == 0:
             none = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
@@ -206,29 +212,10 @@ class BeamSearchStream:
         """What ``finish()`` would return if ``push(log_probs, lengths)`` had been called first (None: no more frames), with the search left
         exactly as it was: the state is only read (nbasr_ctc_beam_stream_peek), no attribute changes, the pool never grows.  Allowed any
         number of times before ``finish()``; only the workspace (``peek_bytes``) is kept, for the next peek."""
-        if self._finished:
-            raise ValueError('push after finish(): call reset() to start the next utterances')
-        if log_probs is None:
+        if log_probs is None and not self._finished:
             log_probs = torch.empty(self.batch, 0, self.classes or self.blank + 1, dtype=torch.float32, device=self.device)
-        if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3 or log_probs.shape[0] != self.batch:
-            raise ValueError(f'expected log-probabilities ({self.batch}, frames, classes), got {tuple(getattr(log_probs, "shape", ()))}')
-        if log_probs.dtype != torch.float32 or log_probs.device != self.device:
-            raise ValueError(f'log-probabilities must be float32 on {self.device} (got {log_probs.dtype} on {log_probs.device})')
-        n, c = log_probs.shape[1], log_probs.shape[2]
-        if self.classes is not None and n and c != self.classes:
-            raise ValueError(f'every chunk must have {self.classes} classes (got {c})')
-        chunk_lengths = None
-        if lengths is not None:
-            rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
-            if rows.numel() != self.batch:
-                raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
-            if bool(((rows < 0) | (rows > n)).any()):
-                raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
-            if bool((self.ended & (rows > 0)).any()):
-                raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
-            chunk_lengths = rows.to(device=self.device, dtype=torch.int32)
-        elif n and bool(self.ended.any()):
-            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        n, c, rows = self._chunk(log_probs, lengths, empty_has_classes=False)
+        chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
         self.reserve_peek(n, c)
         ld = max(int(self.usage.max()) - 1 + n, 1)               # a frame lengthens a suffix by at most one token
         outs = hip.ctc_beam_stream_peek(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes, ld, self.blank,

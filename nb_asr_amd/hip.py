@@ -981,6 +981,16 @@ def _int_tensor(t, what, device, shape=None):
     return t
 
 
+def _beam_call(lib, name, timed_name, timesteps, args, timed_tensors=()):
+    """One call of the beam entry point ``name``; with ``timesteps`` of its timed relative ``timed_name``, whose arguments are the same
+    with the pointers of ``timed_tensors`` = ((position in the TIMED argument list, tensor), ...), in ascending order, put in."""
+    if timesteps:
+        name, args = timed_name, list(args)
+        for at, tensor in timed_tensors:
+            args.insert(at, tensor.data_ptr())
+    _check(getattr(lib, name)(*args), name)
+
+
 def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False):
     """log_probs (B, T', C) float32 log-probabilities -> (beams (B, W, T') int32 best first, scores (B, W) = -log P,
     beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None.  ``timesteps``: the timed search
@@ -994,19 +1004,13 @@ def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_
     scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
     lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
     lib = load_library()
-    lengths_ptr = None if lengths is None else lengths.data_ptr()
-    if timesteps:
-        steps = torch.empty(b, beam_width, t, dtype=torch.int32, device=dev)
-        ws = torch.empty(max(lib.nbasr_ctc_beam_timed_workspace_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
-        _check(lib.nbasr_ctc_beam_search_timed(log_probs.data_ptr(), lengths_ptr, ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
-                                               steps.data_ptr(), lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n,
-                                               _stream(log_probs)), 'nbasr_ctc_beam_search_timed')
-        return beams, scores, steps, lens
-    ws = torch.empty(max(lib.nbasr_ctc_beam_workspace_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
-    _check(lib.nbasr_ctc_beam_search(log_probs.data_ptr(), lengths_ptr, ws.data_ptr(),
-                                     beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n,
-                                     _stream(log_probs)), 'nbasr_ctc_beam_search')
-    return beams, scores, lens
+    steps = torch.empty(b, beam_width, t, dtype=torch.int32, device=dev) if timesteps else None
+    ws_bytes = lib.nbasr_ctc_beam_timed_workspace_bytes if timesteps else lib.nbasr_ctc_beam_workspace_bytes
+    ws = torch.empty(max(ws_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
+    _beam_call(lib, 'nbasr_ctc_beam_search', 'nbasr_ctc_beam_search_timed', timesteps,
+               (log_probs.data_ptr(), None if lengths is None else lengths.data_ptr(), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
+                lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, _stream(log_probs)), [(5, steps)] if timesteps else ())
+    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
 
 
 def ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes, timesteps=False):
@@ -1048,17 +1052,11 @@ def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes
     counts = torch.empty(3, b, dtype=torch.int32, device=dev)
     ws = torch.empty(max(lib.nbasr_ctc_beam_stream_workspace_bytes(b, t, c, pool_nodes), 8) // 4 + 1, dtype=torch.int32, device=dev)
     lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
-    if timesteps:
-        _check(lib.nbasr_ctc_beam_stream_timed_step(lp_ptr, len_ptr, _state(state), ws.data_ptr(), out[0].data_ptr(), out[2].data_ptr(),
-                                                    counts[0].data_ptr(), out[1].data_ptr(), out[3].data_ptr(), counts[1].data_ptr(),
-                                                    counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes,
-                                                    _stream(log_probs)), 'nbasr_ctc_beam_stream_timed_step')
-        return out[0], out[1], out[2], out[3], counts
-    _check(lib.nbasr_ctc_beam_stream_step(lp_ptr, len_ptr,
-                                          _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(),
-                                          counts[1].data_ptr(), counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes,
-                                          _stream(log_probs)), 'nbasr_ctc_beam_stream_step')
-    return out[0], out[1], counts
+    _beam_call(lib, 'nbasr_ctc_beam_stream_step', 'nbasr_ctc_beam_stream_timed_step', timesteps,
+               (lp_ptr, len_ptr, _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(), counts[1].data_ptr(),
+                counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)),
+               [(5, out[2]), (8, out[3])] if timesteps else ())
+    return (*out, counts)
 
 
 def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld, timesteps=False):
@@ -1069,16 +1067,11 @@ def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld, timesteps=F
     beams = torch.empty(batch, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
     scores = torch.empty(batch, beam_width, dtype=torch.float32, device=dev)
     lens = torch.empty(batch, beam_width, dtype=torch.int32, device=dev)
-    lib = load_library()
-    if timesteps:
-        steps = torch.empty_like(beams)
-        _check(lib.nbasr_ctc_beam_stream_timed_finish(_state(state), beams.data_ptr(), scores.data_ptr(), steps.data_ptr(), lens.data_ptr(),
-                                                      beams.shape[2], batch, beam_width, pool_nodes, _stream(state)),
-               'nbasr_ctc_beam_stream_timed_finish')
-        return beams, scores, steps, lens
-    _check(lib.nbasr_ctc_beam_stream_finish(_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2],
-                                            batch, beam_width, pool_nodes, _stream(state)), 'nbasr_ctc_beam_stream_finish')
-    return beams, scores, lens
+    steps = torch.empty_like(beams) if timesteps else None
+    _beam_call(load_library(), 'nbasr_ctc_beam_stream_finish', 'nbasr_ctc_beam_stream_timed_finish', timesteps,
+               (_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2], batch, beam_width, pool_nodes, _stream(state)),
+               [(3, steps)] if timesteps else ())
+    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
 
 
 def ctc_beam_stream_peek_workspace_bytes(batch, frames, classes, beam_width, pool_nodes):
@@ -1107,18 +1100,12 @@ def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes
     beams = torch.empty(b, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
     scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
     lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
-    lib = load_library()
+    steps = torch.empty_like(beams) if timesteps else None
     lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
-    if timesteps:
-        steps = torch.empty_like(beams)
-        _check(lib.nbasr_ctc_beam_stream_timed_peek(lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
-                                                    steps.data_ptr(), lens.data_ptr(), beams.shape[2], b, t, c, beam_width, blank, cutoff_top_n,
-                                                    pool_nodes, _stream(log_probs)), 'nbasr_ctc_beam_stream_timed_peek')
-        return beams, scores, steps, lens
-    _check(lib.nbasr_ctc_beam_stream_peek(lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(),
-                                          beams.shape[2], b, t, c, beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)),
-           'nbasr_ctc_beam_stream_peek')
-    return beams, scores, lens
+    _beam_call(load_library(), 'nbasr_ctc_beam_stream_peek', 'nbasr_ctc_beam_stream_timed_peek', timesteps,
+               (lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2], b, t, c,
+                beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)), [(6, steps)] if timesteps else ())
+    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
 
 
 def token_error_counts(hyp, hyp_len, ref, ref_len, table=None, blank=0):
