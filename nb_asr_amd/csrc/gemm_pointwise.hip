@@ -24,9 +24,10 @@
 //             PwF16x2  [split][block][half][128 rows][8 ch] fp16 (16 KiB), then per-row 2^kw and 2^-kw;
 //             PwBf16          [block][half][128 rows][8 ch] bf16 (8 KiB) -- the values of a bf16 parameter: the rounding is exact;
 //   GEMM:   128 x 256 tile per 512-thread workgroup (8 waves of 64 x 64 = 4 x 4 MFMA tiles), K-step = 32 channels = one MFMA k-block;
-//           per step the packed weights + the image by global_load_lds, double-buffered, one barrier per step; `big` / `small`
-//           accumulators as in the convolution kernel; epilogue: [exact rescale,] bias [+ second bias], [ReLU, min(20)], [skip sum
-//           with LayerNorm on skip0], store (bf16: ONE rounding) -- or the fp32 time-major store of the LSTM gates.
+//           per step the packed weights + the image by global_load_lds into a ring of THREE step buffers, fetched TWO steps ahead, one
+//           barrier per step (see the loop); `big` / `small` accumulators as in the convolution kernel; epilogue: [exact rescale,] bias
+//           [+ second bias], [ReLU, min(20)], [skip sum with LayerNorm on skip0], store (bf16: ONE rounding) -- or the fp32 time-major
+//           store of the LSTM gates, staged through LDS so that a store instruction writes whole 256-byte row segments.
 #include "storage.h"
 
 namespace nbasr {
@@ -49,7 +50,9 @@ struct PwSteps {
     static constexpr int NS = TERMS;
     static constexpr int A_STEP = TERMS * 2 * 2 * PW_M * 16;     // [split][block][half][128 rows][8 ch]: 16 / 8 KiB
     static constexpr int X_STEP = TERMS * 2 * 2 * PW_N * 16;     // [split][block][half][256 frames][8 ch]: 32 / 16 KiB
-    static constexpr int LDS = 2 * (A_STEP + X_STEP);            // 96 / 48 KiB
+    static constexpr int RING = 3;                               // step buffers: the one being multiplied + two in flight
+    static constexpr int LDS = RING * (A_STEP + X_STEP);         // 144 / 72 KiB (of 160 per compute unit)
+    static constexpr int DMA_PER_WAVE = 3 * TERMS;               // LDS-DMA instructions of one wave per K-step
 };
 
 struct PwF16x2 : PwSteps<2> {
@@ -255,8 +258,8 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_gemm_kernel(const PointwiseA
     typedef typename P::act_t act_t;
     constexpr int NS = P::NS, A_STEP = P::A_STEP, X_STEP = P::X_STEP;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* const Abuf = smem;                       // [2][A_STEP]
-    unsigned char* const Xbuf = smem + 2 * A_STEP;          // [2][X_STEP]
+    unsigned char* const Abuf = smem;                       // [RING][A_STEP]
+    unsigned char* const Xbuf = smem + P::RING * A_STEP;    // [RING][X_STEP]
 
     // XCD-aware tile order: every XCD takes a contiguous run of the linear tile index L, dispatched in order.
     //  m-major (rounds 1-2): L = (mt, b, nt) -- an XCD keeps ONE or two weight tiles in its L2 and streams the whole operand image
@@ -324,41 +327,82 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_gemm_kernel(const PointwiseA
     const int a_lane = ((kq * PW_M) + wm * 64 + l15) * 16;
     const int x_lane = ((kq * PW_N) + wn * 64 + l15) * 16;
 
-    dma_step(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll 1
-    for (int ks = 0; ks < a.n_ks; ++ks) {
-        const int buf = ks & 1;
-        if (ks + 1 < a.n_ks) dma_step(ks + 1, buf ^ 1);
-        if (wave_active) {
-            const unsigned char* A = Abuf + buf * A_STEP + a_lane;
-            const unsigned char* X = Xbuf + buf * X_STEP + x_lane;
-            vec8 bt[4][NS];                                 // terms: [0] = hi (or the value), [1] = lo
+    // One K-step of this wave's 64 x 64 tile on step buffer `buf`.  The fragment reads are software-pipelined in place (as mma_step of
+    // gemm_conv_split.hip): the A fragments of row block i + 1 are read behind the first MFMA block of row block i, so only the first
+    // reads of a step wait on LDS latency.  Every accumulator sees the MFMAs it always saw, in the same order (`small`: lo * hi, then
+    // hi * lo; `big`: hi * hi; ks ascending): the sums are the same bit for bit.
+    auto mma_step = [&](int buf) {
+        const unsigned char* A = Abuf + buf * A_STEP + a_lane;
+        const unsigned char* X = Xbuf + buf * X_STEP + x_lane;
+        auto read_a = [&](int i, vec8 (&f)[NS]) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
+            for (int s = 0; s < NS; ++s) f[s] = *reinterpret_cast<const vec8*>(A + s * (A_STEP / NS) + i * 16 * 16);
+        };
+        vec8 bt[4][NS], at[2][NS];                          // terms: [0] = hi (or the value), [1] = lo
 #pragma unroll
-                for (int s = 0; s < NS; ++s) bt[j][s] = *reinterpret_cast<const vec8*>(X + s * (X_STEP / NS) + j * 16 * 16);
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                vec8 at[NS];
+            for (int s = 0; s < NS; ++s) bt[j][s] = *reinterpret_cast<const vec8*>(X + s * (X_STEP / NS) + j * 16 * 16);
+        read_a(0, at[0]);
 #pragma unroll
-                for (int s = 0; s < NS; ++s) at[s] = *reinterpret_cast<const vec8*>(A + s * (A_STEP / NS) + i * 16 * 16);
+        for (int i = 0; i < 4; ++i) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if constexpr (NS == 2) {
-                        floatx4 c = small[i][j];
-                        c = P::mfma(at[1], bt[j][0], c);
-                        c = P::mfma(at[0], bt[j][1], c);
-                        small[i][j] = c;
-                    }
-                    big[i][j] = P::mfma(at[0], bt[j][0], big[i][j]);
+            for (int j = 0; j < 4; ++j) {
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (NS == 2) {
+                    floatx4 c = small[i][j];
+                    c = P::mfma(at[i & 1][1], bt[j][0], c);
+                    c = P::mfma(at[i & 1][0], bt[j][1], c);
+                    small[i][j] = c;
                 }
+                big[i][j] = P::mfma(at[i & 1][0], bt[j][0], big[i][j]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (j == 0 && i < 3) read_a(i + 1, at[(i + 1) & 1]);      // behind the first block: 9 (3) MFMAs to land
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    // ---- main loop: ONE barrier per K-step, operands fetched TWO steps ahead -----------------------------------------------------------
+    // A step multiplies for ~0.65 us at the matrix pipe's rate, an LDS-DMA piece that misses the L2 (the weights always do under the
+    // n-major order) takes longer than that to land; fetched one step ahead and waited for at the end of that step, the DMA's
+    // latency set the step time.  A K-step of 64 k would hide it as well, but two double steps of the split scheme are 192 KiB; a
+    // ring of THREE single steps (144 KiB) gives the same two steps of flight.
+    //   step ks:  DMA of step ks + 2 -> buffer (ks + 2) % 3;  MFMAs on buffer ks % 3;
+    //             wait until this wave's DMA of step ks + 1 has landed (the newest batch may stay in flight: loads retire in order,
+    //             so vmcnt(DMA_PER_WAVE) leaves only step ks + 2 outstanding);  barrier.
+    // Hazards.  Read after fill: buffer (ks + 1) % 3 is read in step ks + 1 only, i.e. behind the barrier that ends step ks, which
+    // every wave reaches only after the counted wait for its own pieces of step ks + 1 -- all 8 waves' pieces have landed.  Fill after
+    // read: buffer (ks + 2) % 3 = (ks - 1) % 3 was last read in step ks - 1; its refill is issued inside step ks, behind the barrier that
+    // ended step ks - 1, and every wave's fragment reads of a step have RETURNED before that barrier (the MFMAs consumed them, and the
+    // wait in front of the barrier names lgkmcnt(0)) -- in either phase order below.  The barrier is the bare instruction: the fence of
+    // __syncthreads() would drain vmcnt to 0 and with it the second step of flight.
+    // Waves 0-3 and 4-7 share the four SIMDs pairwise.  As in gemm_conv_split.hip the two halves run a step in OPPOSITE order: the older
+    // wave issues its DMA first and multiplies last, the younger one multiplies first (at s_setprio 1, so that it really gets the pipe)
+    // and issues last -- each wave's ~1 500 cycles of DMA issue sit beside its partner's MFMAs.
+    const bool older = wave < 4;
+    const int n_ks = a.n_ks;
+    dma_step(0, 0);
+    if (n_ks > 1) {
+        dma_step(1, 1);
+        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" :: "n"(P::DMA_PER_WAVE) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
     }
+    if (!older) __builtin_amdgcn_s_setprio(1);
+    int buf = 0;
+#pragma unroll 1
+    for (int ks = 0; ks < n_ks; ++ks) {
+        const bool ahead = ks + 2 < n_ks;                   // there is a step after the next: fetch it
+        const int fill = buf == 0 ? 2 : buf - 1;            // (ks + 2) % RING
+        if (older && ahead) dma_step(ks + 2, fill);
+        if (wave_active) mma_step(buf);
+        if (!older && ahead) dma_step(ks + 2, fill);
+        if (ahead) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" :: "n"(P::DMA_PER_WAVE) : "memory");
+        else       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        buf = buf == 2 ? 0 : buf + 1;
+    }
+    if (!older) __builtin_amdgcn_s_setprio(0);
 
     if (!wave_active) return;
     float x_inv = 1.f;
@@ -370,14 +414,22 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_gemm_kernel(const PointwiseA
         if constexpr (P::SCALED) v = v * x_inv * a.w_inv[m];
         return v;
     };
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    if constexpr (SWAP) {
+        // Time-major store, through LDS.  Straight from the accumulators a store instruction wrote 16 rows x 64 bytes (a lane holds 4
+        // consecutive m of ONE frame, the rows of y are c_out floats apart); staged, it writes 4 rows x 256 bytes: 64 consecutive m of one
+        // (t, b) row per 16 lanes x 16 bytes.  A wave stages one 16-frame column block of its tile at a time -- 16 rows x 64 m fp32, row
+        // stride 68 floats (the 8 lanes of a ds_write_b128 group land on 8 x 4 different banks) = 4.25 KiB of the operand buffers,
+        // which nobody reads or fills any more: the loop's last barrier stood behind every wave's last reads and its vmcnt(0).  The
+        // tile is wave-private, so the passes need no barrier, only the wave's own LDS counter.  Values are computed exactly as before.
+        constexpr int TS = 64 + 4;
+        static_assert(8 * 16 * TS * 4 <= P::LDS, "output staging must fit the operand buffers");
+        float* const T = reinterpret_cast<float*>(smem) + wave * (16 * TS);
+        const int mseg = m0 + wm * 64 + l15 * 4;            // copy-out: this lane's 4 consecutive m
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int n = n0 + wn * 64 + j * 16 + l15;
-            const int mb = m0 + wm * 64 + i * 16 + kq * 4;
-            if (SWAP) {
-                if (n >= a.frames || mb >= a.c_out) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int mb = m0 + wm * 64 + i * 16 + kq * 4;
                 floatx4 o;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -390,31 +442,49 @@ __global__ __launch_bounds__(PW_THREADS, 2) void pw_gemm_kernel(const PointwiseA
                     }
                     o[r] = v;
                 }
-                float* dst = static_cast<float*>(a.y) + (static_cast<size_t>(n) * a.row_stride_t + static_cast<size_t>(b) * a.row_stride_b) * a.c_out + mb;
-                if (mb + 3 < a.c_out) *reinterpret_cast<floatx4*>(dst) = o;
-                else for (int r = 0; r < 4 && mb + r < a.c_out; ++r) dst[r] = o[r];
-            } else {
-                if (n >= a.ld_out) continue;
-                const bool live = n < a.frames;
-                float s0m = 0.f, s0r = 0.f;
-                if (a.s0 && a.ln_s0.stats) {
-                    const float* st = a.ln_s0.stats + static_cast<size_t>(b) * 2 * a.ld_out;
-                    s0m = st[n]; s0r = st[a.ld_out + n];
-                }
-                act_t* yb = static_cast<act_t*>(a.y);
+                *reinterpret_cast<floatx4*>(T + l15 * TS + i * 16 + kq * 4) = o;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's tile is written (and the reads below stay below)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = mb + r;
-                    if (m >= a.c_out) continue;
-                    float v = product(i, j, r, m) + a.bias[m];
-                    if (RELU) v = relu_clamp(v);
-                    const size_t off = (static_cast<size_t>(b) * a.c_out + m) * a.ld_out + n;
-                    // the skips in python's sum order, in fp32; ONE rounding (as the bf16 node kernels: grouped_conv_impl.h)
-                    if (a.s0) v += a.ln_s0.stats ? ln_apply(pw_load(a.s0 + off), s0m, s0r, a.ln_s0.gamma[m], a.ln_s0.beta[m]) : pw_load(a.s0 + off);
-                    if (a.s1) v += pw_load(a.s1 + off);
-                    if (a.s2) v += pw_load(a.s2 + off);
-                    pw_store(yb + off, live ? v : 0.f);
-                }
+            for (int it = 0; it < 4; ++it) {
+                const int row = it * 4 + kq;
+                const int n = n0 + wn * 64 + j * 16 + row;
+                if (n >= a.frames || mseg >= a.c_out) continue;
+                const floatx4 o = *reinterpret_cast<const floatx4*>(T + row * TS + l15 * 4);
+                float* dst = static_cast<float*>(a.y) + (static_cast<size_t>(n) * a.row_stride_t + static_cast<size_t>(b) * a.row_stride_b) * a.c_out + mseg;
+                *reinterpret_cast<floatx4*>(dst) = o;           // c_out = 4 hidden with hidden % 4 == 0 (pw_projection): a quad is inside or outside as a whole
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the reads have returned before the next pass overwrites the tile
+        }
+        return;
+    }
+    // the `linear` node: bias, ReLU, min(20), the skips, straight from the accumulators (rows of y are frame-contiguous)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int n = n0 + wn * 64 + j * 16 + l15;
+            const int mb = m0 + wm * 64 + i * 16 + kq * 4;
+            if (n >= a.ld_out) continue;
+            const bool live = n < a.frames;
+            float s0m = 0.f, s0r = 0.f;
+            if (a.s0 && a.ln_s0.stats) {
+                const float* st = a.ln_s0.stats + static_cast<size_t>(b) * 2 * a.ld_out;
+                s0m = st[n]; s0r = st[a.ld_out + n];
+            }
+            act_t* yb = static_cast<act_t*>(a.y);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = mb + r;
+                if (m >= a.c_out) continue;
+                float v = product(i, j, r, m) + a.bias[m];
+                if (RELU) v = relu_clamp(v);
+                const size_t off = (static_cast<size_t>(b) * a.c_out + m) * a.ld_out + n;
+                // the skips in python's sum order, in fp32; ONE rounding (as the bf16 node kernels: grouped_conv_impl.h)
+                if (a.s0) v += a.ln_s0.stats ? ln_apply(pw_load(a.s0 + off), s0m, s0r, a.ln_s0.gamma[m], a.ln_s0.beta[m]) : pw_load(a.s0 + off);
+                if (a.s1) v += pw_load(a.s1 + off);
+                if (a.s2) v += pw_load(a.s2 + off);
+                pw_store(yb + off, live ? v : 0.f);
             }
         }
     }

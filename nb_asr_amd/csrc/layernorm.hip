@@ -314,7 +314,15 @@ __global__ __launch_bounds__(256) void normalize_split_kernel(const float* __res
     // 64 frame quads (one wave = 1 KiB of a channel row) x 4 channel octets per pass, the octets dealt over the waves of the
     // gridDim.z workgroups of a tile; a thread turns 8 channels x 4 frames into 4 + 4 image rows of 16 bytes.  (Round 1 had 16 quads
     // x 16 octets: 256-byte row segments, 3.7 TB/s.)
-    const int ql = threadIdx.x & 63, oct0 = (threadIdx.x >> 6) + 4 * blockIdx.z;
+    // The rows leave through a wave-private LDS tile: straight from the registers a store instruction wrote 64 rows of 16 bytes 64 bytes
+    // apart (a lane owns 4 CONSECUTIVE rows), four instructions to fill 4 KiB of a plane; transposed, lane L of store k holds frame
+    // 64 k + L and an instruction writes ONE contiguous KiB.  Tile: [split][frame-in-quad r][SPLIT_PITCH rows][16 B]; the write (row
+    // r * pitch + quad, lanes along quads) is contiguous, the read (row (L & 3) * pitch + 16 k + (L >> 2)) puts the 16 lanes of every
+    // ds_read_b128 group on 16 different bank quads because the pitch is 68 rows: bank = 16 (L & 3) + 4 (L >> 2) mod 64.
+    // The next octet's loads are issued before the current one's arithmetic and stores (one more set of 8 rows in flight per thread).
+    constexpr int SPLIT_PITCH = 68;
+    __shared__ __attribute__((aligned(16))) unsigned char s_tile[4][2][4 * SPLIT_PITCH * 16];
+    const int ql = threadIdx.x & 63, wv = threadIdx.x >> 6, oct0 = wv + 4 * blockIdx.z;
     const int nq = ld >> 2;
     const int q = blockIdx.x * 64 + ql;
     const int b = blockIdx.y;
@@ -326,7 +334,8 @@ __global__ __launch_bounds__(256) void normalize_split_kernel(const float* __res
         const uint4 z = make_uint4(0u, 0u, 0u, 0u);
         for (int pl = threadIdx.x; pl < n_groups * 4; pl += 256) *reinterpret_cast<uint4*>(img_b + static_cast<size_t>(pl) * rows * 16) = z;
     }
-    if (q >= nq) return;
+    if (blockIdx.x * 64 >= nq) return;                            // (whole workgroup; cannot happen with the host's grid)
+    const bool inside = q < nq;                                   // lanes beyond the row still take part in the transpose
     // 2^k that brings the bound into [2^14, 2^15)
     float scale = 1.f;
     {
@@ -338,34 +347,50 @@ __global__ __launch_bounds__(256) void normalize_split_kernel(const float* __res
     }
     float m4[4] = {0.f, 0.f, 0.f, 0.f}, r4[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (NORM) {
-        const float* st = stats + static_cast<size_t>(b) * 2 * ld + q * 4;
-        const float4 mu = *reinterpret_cast<const float4*>(st), rs = *reinterpret_cast<const float4*>(st + ld);
-        m4[0] = mu.x; m4[1] = mu.y; m4[2] = mu.z; m4[3] = mu.w;
-        r4[0] = rs.x; r4[1] = rs.y; r4[2] = rs.z; r4[3] = rs.w;
+        if (inside) {
+            const float* st = stats + static_cast<size_t>(b) * 2 * ld + q * 4;
+            const float4 mu = *reinterpret_cast<const float4*>(st), rs = *reinterpret_cast<const float4*>(st + ld);
+            m4[0] = mu.x; m4[1] = mu.y; m4[2] = mu.z; m4[3] = mu.w;
+            r4[0] = rs.x; r4[1] = rs.y; r4[2] = rs.z; r4[3] = rs.w;
+        }
     }
     const float* xb = x + static_cast<size_t>(b) * channels * ld + static_cast<size_t>(q) * 4;
     const int n_oct = (channels + 7) >> 3;
-    for (int oct = oct0; oct < 2 * n_groups; oct += 4 * gridDim.z) {
+    const int oct_step = 4 * gridDim.z;
+    auto load_octet = [&](int oct, float4 (&t)[8]) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int ch = oct * 8 + c;
+            t[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (inside && oct < n_oct && ch < channels) t[c] = *reinterpret_cast<const float4*>(xb + static_cast<size_t>(ch) * ld);
+        }
+    };
+    unsigned char* const tile_hi = s_tile[wv][0];
+    unsigned char* const tile_lo = s_tile[wv][1];
+    float4 cur[8];
+    if (oct0 < 2 * n_groups) load_octet(oct0, cur);
+    for (int oct = oct0; oct < 2 * n_groups; oct += oct_step) {
+        float4 nxt[8];
+        if (oct + oct_step < 2 * n_groups) load_octet(oct + oct_step, nxt);
+        else {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) nxt[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         float v[8][4];
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
             const int ch = oct * 8 + c;
-            float4 t4 = make_float4(0.f, 0.f, 0.f, 0.f);
             float g = 0.f, be = 0.f;
-            if (oct < n_oct && ch < channels) {
-                t4 = *reinterpret_cast<const float4*>(xb + static_cast<size_t>(ch) * ld);
-                if constexpr (NORM) { g = gamma[ch]; be = beta[ch]; }
+            if constexpr (NORM) {
+                if (oct < n_oct && ch < channels) { g = gamma[ch]; be = beta[ch]; }
             }
-            const float e4[4] = {t4.x, t4.y, t4.z, t4.w};
+            const float e4[4] = {cur[c].x, cur[c].y, cur[c].z, cur[c].w};
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if constexpr (NORM) v[c][r] = (ch < channels) ? ln_apply(e4[r], m4[r], r4[r], g, be) * scale : 0.f;
                 else                v[c][r] = e4[r] * scale;
             }
         }
-        // group = oct >> 1, half = oct & 1; planes of a group: [split][half]
-        unsigned char* plane_hi = img_b + ((static_cast<size_t>(oct >> 1) * 4 + (oct & 1)) * rows + 1 + static_cast<size_t>(q) * 4) * 16;
-        unsigned char* plane_lo = plane_hi + 2 * rows * 16;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             halfx8 hi, lo;
@@ -375,9 +400,27 @@ __global__ __launch_bounds__(256) void normalize_split_kernel(const float* __res
                 hi[c] = h;
                 lo[c] = static_cast<_Float16>(v[c][r] - static_cast<float>(h));       // unscaled residual (gemm_conv_split.hip, SplitF16x2)
             }
-            *reinterpret_cast<halfx8*>(plane_hi + r * 16) = hi;
-            *reinterpret_cast<halfx8*>(plane_lo + r * 16) = lo;
+            *reinterpret_cast<halfx8*>(tile_hi + (r * SPLIT_PITCH + ql) * 16) = hi;
+            *reinterpret_cast<halfx8*>(tile_lo + (r * SPLIT_PITCH + ql) * 16) = lo;
         }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the wave's tile is written (wave-private: no barrier)
+        // group = oct >> 1, half = oct & 1; planes of a group: [split][half]; frame t at row t + 1
+        unsigned char* plane_hi = img_b + ((static_cast<size_t>(oct >> 1) * 4 + (oct & 1)) * rows + 1 + static_cast<size_t>(blockIdx.x) * 256) * 16;
+        unsigned char* plane_lo = plane_hi + 2 * rows * 16;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int src = ((ql & 3) * SPLIT_PITCH + 16 * k + (ql >> 2)) * 16;
+            const halfx8 hi = *reinterpret_cast<const halfx8*>(tile_hi + src);
+            const halfx8 lo = *reinterpret_cast<const halfx8*>(tile_lo + src);
+            const int f = 64 * k + ql;                            // frame within the workgroup's 256
+            if (blockIdx.x * 256 + f < ld) {
+                *reinterpret_cast<halfx8*>(plane_hi + f * 16) = hi;
+                *reinterpret_cast<halfx8*>(plane_lo + f * 16) = lo;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the reads have returned before the next octet overwrites the tile
+#pragma unroll
+        for (int c = 0; c < 8; ++c) cur[c] = nxt[c];
     }
 }
 
