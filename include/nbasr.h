@@ -396,6 +396,27 @@ size_t nbasr_ctc_grad_workspace_bytes(int batch, int frames, int ld_targets);
 int nbasr_ctc_loss_grad(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, void* ws,
                         float* losses, float* grad_logits, int batch, int frames, int classes, int ld_targets, int blank,
                         nbasr_stream_t stream);
+/* nbasr_ctc_forced_align: CTC forced alignment -- given the transcript, which frames belong to which token (torchaudio's forced_align +
+ *   merge_tokens; the reference has no aligner).  Inputs as nbasr_ctc_loss takes them: log_probs(batch, frames, classes) float32, lengths(batch)
+ *   clamped to [0, frames], targets(batch, ld_targets) int32 with target_lengths(batch) clamped to [0, ld_targets] (ld_targets <= 1024).
+ *   Everything is fp32; the only arithmetic is max and one add per cell.  Over the blank-extended label sequence l' (S = 2L + 1 positions,
+ *   blanks at even s):  v_0(0) = lp[0][blank], v_0(1) = lp[0][l'_1], every other position -inf;
+ *       v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), v_{t-1}(s-2) if l'_s != blank and l'_s != l'_{s-2}) + lp[t][l'_s],
+ *   among equal maxima the smallest step wins (stay, then s-1, then s-2).  The path ends at s_end = S-2 if S > 1 and v(S-2) >= v(S-1), else
+ *   S-1 (on a tie on the last label); scores(batch) = v_{len-1}(s_end).  Walking the chosen predecessors back from s_end gives
+ *   path(batch, frames) int32: the class (blank or a label) at each frame, -1 at frames >= len;  starts, ends(batch, ld_targets) int32: first
+ *   frame and one-past-last frame of token j, -1 for j >= L;  token_scores(batch, ld_targets): the fp32 sum of lp[t][label_j] over the token's
+ *   frames, added in increasing frame order, 0 for j >= L.
+ *   No path (score -inf: len < L + the number of adjacent equal labels, len = 0 < L, or every path crosses a class masked with -inf, which
+ *   is legal input): scores = -inf, path = -1, starts = ends = -1, token_scores = 0.  len = 0 and L = 0: scores = 0.  A label outside
+ *   [0, classes) or equal to blank among the first L gives scores = NaN for that utterance, its other outputs as for "no path"; labels beyond
+ *   L are never read for their value, nor are frames beyond len.  NaN log-probabilities inside an utterance are not defined input.
+ *   ws: nbasr_ctc_align_workspace_bytes (0 for bad sizes), the 2-bit back-pointers: frames * W * 64 32-bit words per utterance with
+ *   W = ceil(ceil((2 ld_targets + 1) / 64) / 16); 4-byte aligned, no state between calls.  Two calls give the same bits. */
+size_t nbasr_ctc_align_workspace_bytes(int batch, int frames, int ld_targets);
+int nbasr_ctc_forced_align(const float* log_probs, const int* lengths, const int* targets, const int* target_lengths, void* ws,
+                           float* scores, int* path, int* starts, int* ends, float* token_scores,
+                           int batch, int frames, int classes, int ld_targets, int blank, nbasr_stream_t stream);
 size_t nbasr_ctc_beam_workspace_bytes(int batch, int frames, int classes, int beam_width);
 int nbasr_ctc_beam_search(const float* log_probs, const int* lengths, void* ws, int* beams, float* scores, int* beam_lens,
                           int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,

@@ -20,7 +20,7 @@ LIB_PATH = PKG_DIR / 'lib' / 'libnbasr_hip.so'
 INCLUDE_DIR = REPO_DIR / 'include'
 ARCH = 'gfx950'
 
-SOURCES = ['api.cpp', 'grouped_conv.hip', 'grouped_conv_alt.hip', 'grouped_conv_osplit.hip', 'grouped_conv_ring.hip', 'grouped_conv_bf16.hip', 'grouped_cell.hip', 'grouped_cell_mfma.hip', 'layernorm.hip', 'gemm_conv.hip', 'gemm_conv_split.hip', 'gemm_pointwise.hip', 'lstm.hip', 'lstm_xcd.hip', 'backward.hip', 'ctc.hip', 'ctc_decode.hip', 'ctc_loss.hip', 'frontend.hip', 'frontend_stream.hip', 'stream.hip', 'optim.hip']
+SOURCES = ['api.cpp', 'grouped_conv.hip', 'grouped_conv_alt.hip', 'grouped_conv_osplit.hip', 'grouped_conv_ring.hip', 'grouped_conv_bf16.hip', 'grouped_cell.hip', 'grouped_cell_mfma.hip', 'layernorm.hip', 'gemm_conv.hip', 'gemm_conv_split.hip', 'gemm_pointwise.hip', 'lstm.hip', 'lstm_xcd.hip', 'backward.hip', 'ctc.hip', 'ctc_decode.hip', 'ctc_loss.hip', 'ctc_align.hip', 'frontend.hip', 'frontend_stream.hip', 'stream.hip', 'optim.hip']
 CXXFLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-Wall', '-Wno-unused-function']
 CXXFLAGS += os.environ.get('NBASR_EXTRA_CXXFLAGS', '').split()      # diagnostics (A/B builds); part of the build id
 
@@ -86,11 +86,14 @@ def build_library(force=False, verbose=False, jobs=8):
         for _, obj in pairs:
             obj.unlink(missing_ok=True)
     build_id = source_hash()
+    lib_stamp = LIB_PATH.with_suffix('.id')
+    keys = [_object_key(src, headers, build_id if src.name == 'api.cpp' else None) for src, _ in pairs]
+    if not force and LIB_PATH.exists() and lib_stamp.exists() and lib_stamp.read_text() == hashlib.sha256('\n'.join(keys).encode()).hexdigest():
+        return LIB_PATH                               # linked from exactly these sources and flags: the objects are not needed again
     with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as pool:
         rebuilt = list(pool.map(lambda p: _compile(p[0], p[1], headers, verbose, build_id if p[0].name == 'api.cpp' else None), pairs))
     objs = [obj for _, obj in pairs]
     lib_key = hashlib.sha256('\n'.join(obj.with_suffix('.id').read_text() for obj in objs).encode()).hexdigest()
-    lib_stamp = LIB_PATH.with_suffix('.id')
     if any(rebuilt) or not LIB_PATH.exists() or not lib_stamp.exists() or lib_stamp.read_text() != lib_key:
         cmd = [_hipcc(), '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(LIB_PATH)] + [str(o) for o in objs]
         if verbose:

@@ -9,16 +9,25 @@ third-party C++, not in the reference's tree), ``PhonemeEncoder.fold_encoded(., 
 removal + Levenshtein distance) and ``decode_per`` = the whole of ``Trainer.decode``.  ``greedy_decode`` is the cheap
 width-1 relative (per-frame argmax, collapse, drop blank).
 """
+import collections
+import inspect
+
 import torch
 
 from . import hip
+from .frontend import LogMelFrontend
 from .phonemes import fold_table  # noqa: F401  (part of this module's interface)
+
+OUTPUT_STRIDE = 4                 # input frames per output frame: the model's two stride-2 convolutions
+_FRONTEND = inspect.signature(LogMelFrontend.__init__).parameters
+# seconds per output frame: the front-end's hop (160 samples at 16 kHz = 10 ms) times the model's stride = 40 ms; turns frame spans into seconds
+FRAME_SECONDS = OUTPUT_STRIDE * _FRONTEND['hop_length'].default / _FRONTEND['sample_rate'].default
 
 
 def output_lengths(audio_len):
     """Frames of the model output that belong to each utterance: ``audio_len // 4`` (trainer.py:219).  Note this is the
     trainer's convention, not ceil(ceil(T/2)/2): for T not divisible by 4 the last partial output frame is ignored."""
-    return torch.div(audio_len, 4, rounding_mode='floor')
+    return torch.div(audio_len, OUTPUT_STRIDE, rounding_mode='floor')
 
 
 def log_softmax(logits):
@@ -295,6 +304,43 @@ def ctc_loss(log_probs, output_len, targets, targets_len, blank=0):
     per = hip.ctc_loss(log_probs.contiguous(), _lengths(output_len, b, dev), targets.to(device=dev, dtype=torch.int32).contiguous(),
                        _lengths(targets_len, b, dev), blank, divide_by_length=True)
     return per.mean()
+
+
+Alignment = collections.namedtuple('Alignment', ['path', 'score', 'starts', 'ends', 'token_scores'])
+
+
+def forced_align(log_probs, output_len, targets, targets_len, blank=0):
+    """CTC forced alignment (nbasr.h: nbasr_ctc_forced_align; torchaudio's ``forced_align`` + ``merge_tokens``): given the transcript, the
+    best path through it and the frames of every token.  ``log_probs`` (B, T', C) float32 on the device, ``output_len`` and
+    ``targets_len`` (B) tensors or sequences, ``targets`` (B, L) labels (never ``blank``).  Returns ``Alignment`` of device tensors:
+    ``path`` (B, T') int32, the class at each frame (-1 beyond the utterance); ``score`` (B) float32, the path's log-probability;
+    ``starts`` / ``ends`` (B, L) int32, first and one-past-last frame of each token (-1 beyond ``targets_len``; multiply by
+    ``FRAME_SECONDS`` for seconds); ``token_scores`` (B, L) float32, each token's log-probability summed over its frames.  An utterance
+    too short for its transcript has score -inf, path and spans -1; a label that is ``blank`` or outside the classes gives score NaN."""
+    if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3:
+        raise ValueError(f'log_probs must be (batch, frames, classes), got {tuple(getattr(log_probs, "shape", ()))}')
+    if log_probs.dtype != torch.float32 or not log_probs.is_cuda:
+        raise ValueError(f'log_probs must be float32 on a HIP device (got {log_probs.dtype} on {log_probs.device}); this package has no CPU path')
+    b, dev = log_probs.shape[0], log_probs.device
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 2 or targets.shape[0] != b:
+        raise ValueError(f'targets must be ({b}, labels), got {tuple(getattr(targets, "shape", ()))}')
+    scores, path, starts, ends, token_scores = hip.ctc_forced_align(
+        log_probs.contiguous(), _lengths(output_len, b, dev), targets.to(device=dev, dtype=torch.int32).contiguous(), _lengths(targets_len, b, dev), int(blank))
+    return Alignment(path, scores, starts, ends, token_scores)
+
+
+def align(model, audio, audio_len, targets, targets_len):
+    """``forced_align`` of a model's output: the ``eval()`` forward of ``audio`` (B, 80, T), ``log_softmax``, ``output_lengths(audio_len)``, then
+    the alignment of ``targets`` -- which output frames (40 ms each, ``FRAME_SECONDS``) belong to which phoneme.  No gradients; the model's
+    training flag is left as it was."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            log_probs = log_softmax(model(audio))
+    finally:
+        model.train(was_training)
+    return forced_align(log_probs, output_lengths(torch.as_tensor(audio_len)), targets, targets_len)
 
 
 def evaluation_step(model, audio, audio_len, targets, targets_len, beam_width=12):

@@ -100,6 +100,8 @@ SIGNATURES = {
     'nbasr_ctc_loss': (_c_int, [_c_float_p] * 5 + [_c_int] * 6 + [_c_stream]),
     'nbasr_ctc_grad_workspace_bytes': (ctypes.c_size_t, [_c_int] * 3),
     'nbasr_ctc_loss_grad': (_c_int, [_c_float_p] * 7 + [_c_int] * 5 + [_c_stream]),
+    'nbasr_ctc_align_workspace_bytes': (ctypes.c_size_t, [_c_int] * 3),
+    'nbasr_ctc_forced_align': (_c_int, [_c_float_p] * 10 + [_c_int] * 5 + [_c_stream]),
     'nbasr_ctc_beam_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
     'nbasr_ctc_beam_search': (_c_int, [_c_float_p] * 6 + [_c_int] * 6 + [_c_stream]),
     'nbasr_token_error_counts': (_c_int, [_c_float_p, _c_float_p, _c_int, _c_float_p, _c_float_p, _c_int, _c_float_p, _c_int, _c_int,
@@ -1161,6 +1163,23 @@ def ctc_loss_grad(log_probs, lengths, targets, target_lengths, blank=0):
     _check(load_library().nbasr_ctc_loss_grad(log_probs.data_ptr(), lengths.data_ptr(), targets.data_ptr(), target_lengths.data_ptr(), ws.data_ptr(),
                                               losses.data_ptr(), grad.data_ptr(), b, t, c, targets.shape[1], blank, _stream(log_probs)), 'nbasr_ctc_loss_grad')
     return losses, grad
+
+
+def ctc_forced_align(log_probs, lengths, targets, target_lengths, blank=0):
+    """The best CTC path of each transcript (nbasr.h: nbasr_ctc_forced_align; arguments as ``ctc_loss``) -> (scores (B) float32,
+    path (B, T') int32, starts (B, L) int32, ends (B, L) int32, token_scores (B, L) float32)."""
+    b, t, c, dev = _ctc_args(log_probs, lengths, targets, target_lengths)
+    ld = targets.shape[1]
+    lib = load_library()
+    scores = torch.empty(b, dtype=torch.float32, device=dev)
+    path = torch.empty(b, t, dtype=torch.int32, device=dev)
+    starts, ends = torch.empty(b, ld, dtype=torch.int32, device=dev), torch.empty(b, ld, dtype=torch.int32, device=dev)
+    token_scores = torch.empty(b, ld, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(lib.nbasr_ctc_align_workspace_bytes(b, t, ld) // 4, 1), dtype=torch.int32, device=dev)
+    _check(lib.nbasr_ctc_forced_align(log_probs.data_ptr(), lengths.data_ptr(), targets.data_ptr(), target_lengths.data_ptr(), ws.data_ptr(),
+                                      scores.data_ptr(), path.data_ptr(), starts.data_ptr(), ends.data_ptr(), token_scores.data_ptr(),
+                                      b, t, c, ld, blank, _stream(log_probs)), 'nbasr_ctc_forced_align')
+    return scores, path, starts, ends, token_scores
 
 
 # ---------------------------------------------------------------------------------------------
