@@ -498,6 +498,40 @@ int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const int* chunk_le
                                      int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width,
                                      int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream);
 
+/* ---- bigram LM fusion (ctcdecode's alpha / beta with a character-based scorer; nb_asr_amd/ctc.py beam_decode(lm=...),
+ * BeamSearchStream(lm=...)) --------------------------------------------------------------------------------------------------------
+ * The searches above with one fusion table W added to the log scores: `fusion`, float32, (classes, classes), row-major, on the device.
+ *   W[p][c] is added whenever a prefix whose last token is p is extended by class c.  Row `blank` is the utterance-start context (the empty
+ *   prefix has no last token, and blank is never a token).  Column `blank` is never read.  All entries must be finite (not checked here).
+ *   alpha and beta never reach the device: the caller builds W = alpha * log P(c | p) + beta once, in float32; the kernels only add, so
+ *   floating-point contraction cannot change a bit between the device and a model of it.
+ * W is added to EVERY extension contribution that is not already -FLT_MAX (ctcdecode's ctc_beam_search_decoder.cpp):
+ *   1. a new candidate, live prefix i plus class c: with v the unfused value (lp_c + P_blank(i) if c == last_i, else lp_c + P(i)), the
+ *      candidate's score -- in the ranking and as the survivor's score -- is v + W[last_i or blank][c];
+ *   2. the mass a live prefix absorbs from its live parent (the prefix minus its last token): lp_last + P_blank(parent) or lp_last + P(parent)
+ *      gets + W[last_parent or blank][last] before the log-sum-exp.
+ *   Staying on blank and repeating the last class get nothing; -FLT_MAX stays -FLT_MAX.  The order of additions is fixed: first the acoustic
+ *   sum as in the unfused search, then one add of W.  Ranking, prefix identity, the commit rule and the time-step records (which look at the
+ *   log-probabilities only) are unchanged; scores are minus the fused log score.  With a beam that holds every labelling and no pruning, the
+ *   fused score of a labelling y is log P_ctc(y) + sum_k W[y_{k-1}][y_k] (y_0 = blank).
+ * Each entry point takes the arguments of its plain relative plus `fusion` (non-NULL, even for batch == 0), `timed` (0: the untimed state /
+ *   workspace family and outputs; non-zero: the timed family's -- nbasr_ctc_beam_timed_workspace_bytes, a state initialised by
+ *   nbasr_ctc_beam_stream_timed_init) and the timed outputs (timesteps, committed_frames, partial_frames; ignored and may be NULL when
+ *   timed == 0).  No state of its own: init, finish, *_state_bytes and *_workspace_bytes are the unfused ones, and a state may be stepped
+ *   by either (a search should keep to one table).  An all-zero table gives the unfused results bit for bit.
+ *   Refused on the host before any device work: a NULL table (NBASR_ENULL), classes > 64 or beam_width > 32 (NBASR_EINVAL), timed outputs
+ *   missing when timed is set (NBASR_ENULL). */
+int nbasr_ctc_beam_search_lm(const float* log_probs, const int* lengths, const float* fusion, void* ws, int* beams, float* scores,
+                             int* timesteps, int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
+                             int timed, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_lm_step(const float* log_probs, const int* chunk_lengths, const float* fusion, void* state, void* ws, int* committed,
+                                  int* committed_frames, int* committed_counts, int* partial, int* partial_frames, int* partial_counts,
+                                  int* usage, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes,
+                                  int timed, nbasr_stream_t stream);
+int nbasr_ctc_beam_stream_lm_peek(const float* log_probs, const int* chunk_lengths, const float* fusion, const void* state, void* ws, int* beams,
+                                  float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes,
+                                  int beam_width, int blank, int cutoff_top_n, int pool_nodes, int timed, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

@@ -23,6 +23,15 @@
 // too moves its own node's record to (t, lp_t[c]) when lp_t[c] is larger (strictly: the earliest frame wins).  The lane of a live
 // prefix keeps `best` in a register, the frame lives in the pool: a timed node is two int2, (parent, class) then (frame, best).  The
 // untimed instantiations compile to the code they were before the flag existed.
+//
+// Bigram fusion (ctcdecode's alpha / beta with a character scorer; the LM instantiations, nbasr_ctc_beam_*_lm*; the contract is in nbasr.h):
+// one table W(classes, classes), W[p][c] added to the log score whenever a prefix ending in p is extended by c (row `blank`: the empty
+// prefix).  W is staged once per launch into LDS, padded to 64 x 64.  The addresses a frame needs depend on the survivors of the previous
+// frame only, so all of a frame's reads -- W[last_i][(lane + i) mod 64] for every live prefix i, and the one entry a live prefix's absorb
+// rule needs -- are issued together at the top of the frame into an unrolled register array; the candidate scan (unrolled over BEAM_MAX for
+// these instantiations, so the array is indexed by constants) adds them, and nothing in the rl / DPP chain waits on LDS.  A surviving
+// extension takes its fused score back out of its key (the key transform is a bijection of the float's bits), which is the sum the scan
+// formed, so materialising costs no dependent read either.  The instantiations without the flag compile to the code they were before.
 #include "common.h"
 
 #include <cfloat>
@@ -42,6 +51,9 @@ __device__ __forceinline__ float log_sum_exp(float x, float y)
     return logf(expf(x - m) + expf(y - m)) + m;
 }
 
+// one add of a fusion table entry to a score that is not "-infinity"
+__device__ __forceinline__ float beam_fuse(float v, float w) { return v > NEG ? v + w : v; }
+
 // order-preserving key: larger = better.  score first, then the SMALLER last class (+1: the root's -1 becomes 0), then the
 // smaller table slot (makes the choice between exact ties deterministic; ctcdecode leaves it to nth_element)
 __device__ __forceinline__ unsigned long long beam_key(float score, int last_plus1, int slot)
@@ -50,6 +62,13 @@ __device__ __forceinline__ unsigned long long beam_key(float score, int last_plu
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return (static_cast<unsigned long long>(u) << 32) | (static_cast<unsigned long long>(0xFFFF - last_plus1) << 16) |
            static_cast<unsigned long long>(0xFFFF - slot);
+}
+
+// the score a key was made from, bit for bit (the transform of beam_key maps the floats one to one)
+__device__ __forceinline__ float beam_key_score(unsigned long long key)
+{
+    const unsigned u = static_cast<unsigned>(key >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u);
 }
 
 // Vocabulary pruning of ctcdecode (get_pruned_log_probs with cutoff_prob = 1): per frame only the top_n most probable classes
@@ -180,8 +199,56 @@ __device__ __forceinline__ unsigned merged_mask(int p_mp, int p_last, int n_live
 // wide and carry their (frame, best) record; the owning lane writes a record when it creates a node or improves its own.
 template <bool TIMED> constexpr int NODE_INT2 = TIMED ? 2 : 1;
 
-template <bool TIMED>
-__device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __restrict__ pool, int classes, int width, int blank, int lane, int t)
+// The fusion table of a launch in LDS, rows and columns padded to BEAM_CLASSES (the padding is never read: classes beyond `classes` are
+// pruned, last classes are below `classes`); by all lanes of the workgroup.  Without LM: nothing, not a byte of LDS.
+template <bool LM>
+__device__ __forceinline__ const float* beam_stage_fusion(const float* __restrict__ fusion, int classes, int lane)
+{
+    if constexpr (LM) {
+        __shared__ float s_w[BEAM_CLASSES * BEAM_CLASSES];
+        // lane = column; 16 rows' loads are in flight before the first is stored (one load per trip costs a stream step of 10 frames
+        // 10 us, as much as its frames' fusion)
+        for (int p0 = 0; p0 < BEAM_CLASSES; p0 += 16) {
+            float v[16];
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v[k] = (p0 + k < classes && lane < classes) ? fusion[(p0 + k) * classes + lane] : 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) s_w[(p0 + k) * BEAM_CLASSES + lane] = v[k];
+        }
+        __syncthreads();
+        return s_w;
+    } else {
+        return nullptr;
+    }
+}
+
+// X(0) X(1) ... X(BEAM_MAX - 1): the LM instantiations write their steps over the live prefixes out
+#define BEAM_FOR_EACH_PREFIX(X)                                                                                                    \
+    X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)                                          \
+    X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31)
+static_assert(BEAM_MAX == 32, "BEAM_FOR_EACH_PREFIX lists BEAM_MAX steps");
+
+// one step of the candidate scan: the extension of live prefix i by the class this lane holds after i rotations; W_ADD(v) fuses the table
+#define BEAM_SCAN_STEP(W_ADD)                                                                                                      \
+    {                                                                                                                              \
+        const float sc = rl(p_score, i), bp = rl(p_b, i);                                                                          \
+        const int last = rl(p_last, i);                                                                                            \
+        const float v = W_ADD((cls == last) ? (bp > NEG ? lp_c + bp : NEG) : lp_c + sc);                                           \
+        unsigned long long k = beam_key(v, cls + 1, i * BEAM_CLASSES + cls);                                                       \
+        if (!(lp_c > NEG) || cls == blank || (((mrg | static_cast<int>(excluded)) >> i) & 1)) k = 0ull;                            \
+        const unsigned long long lo = k < m1 ? k : m1;                                                                             \
+        m1 = k > m1 ? k : m1;                                                                                                      \
+        m2 = lo > m2 ? lo : m2;                                                                                                    \
+        lp_c = wave_rotate(lp_c);                                                                                                  \
+        cls = wave_rotate(cls);                                                                                                    \
+        mrg = wave_rotate(mrg);                                                                                                    \
+    }
+
+// LM: `w_lds` = beam_stage_fusion's table; every score an extension contributes gets one add of W[the extended prefix's last class, or
+// `blank` for the empty prefix][the class], after the acoustic sum is formed; a score of -FLT_MAX stays -FLT_MAX.
+template <bool TIMED, bool LM>
+__device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __restrict__ pool, int classes, int width, int blank, int lane, int t,
+                                           const float* __restrict__ w_lds)
 {
     constexpr int NS = NODE_INT2<TIMED>;
     float p_b = st.p_b, p_nb = st.p_nb, p_score = st.p_score;
@@ -198,13 +265,37 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
     const int par = p_mp >= 0 ? p_mp : 0;
     const float par_score = __shfl(p_score, par), par_b = __shfl(p_b, par);
     const int par_last = __shfl(p_last, par);
+    // ---- LM: every table entry this frame can need, read now.  w_ext[i] = W[last of live prefix i][the class this lane holds at step i of
+    //      the candidate scan, (lane + i) mod 64 (wave_rotate hands lane l the value of lane l + 1)]; w_abs = the entry of this lane's absorb
+    //      rule, its parent's last class extended by its own.  Rows and columns are below BEAM_CLASSES by construction (a last class is -1
+    //      or a class of a frame, `blank` < classes), so every read lies inside the staged tile.
+    //      The steps over the live prefixes are written out BEAM_MAX times with one exit at the first i >= n_live: a loop with that exit
+    //      is not unrolled, and a guard per step costs a taken branch for every step beyond n_live.
+    float w_ext[LM ? BEAM_MAX : 1] = {};
+    float w_abs = 0.f;
+    if constexpr (LM) {
+        w_abs = w_lds[(par_last >= 0 ? par_last : blank) * BEAM_CLASSES + (p_last >= 0 ? p_last : 0)];
+#define BEAM_LOAD_STEP(i)                                                                                                          \
+        if ((i) >= n_live) goto loaded;                                                                                            \
+        {                                                                                                                          \
+            const int last = rl(p_last, i);                                                                                        \
+            w_ext[i] = w_lds[(last >= 0 ? last : blank) * BEAM_CLASSES + ((lane + (i)) & (BEAM_CLASSES - 1))];                     \
+        }
+        BEAM_FOR_EACH_PREFIX(BEAM_LOAD_STEP)
+#undef BEAM_LOAD_STEP
+    loaded:;
+    }
     float n_b = NEG, n_nb = NEG, n_score = NEG;
     unsigned long long live_key = 0ull;
     if (lane < n_live) {
         n_b = lp_blank > NEG ? lp_blank + p_score : NEG;
         if (p_last >= 0 && lp_last > NEG) {
             n_nb = lp_last + p_nb;
-            if (p_mp >= 0) n_nb = log_sum_exp(n_nb, p_last == par_last ? (par_b > NEG ? lp_last + par_b : NEG) : lp_last + par_score);
+            if (p_mp >= 0) {
+                float add = p_last == par_last ? (par_b > NEG ? lp_last + par_b : NEG) : lp_last + par_score;
+                if (LM && add > NEG) add += w_abs;
+                n_nb = log_sum_exp(n_nb, add);
+            }
         }
         n_score = log_sum_exp(n_b, n_nb);
         live_key = beam_key(n_score, p_last + 1, width * BEAM_CLASSES + lane);
@@ -227,18 +318,22 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
         unsigned long long m1 = (excluded >> 32) & 1ull ? 0ull : live_key, m2 = 0ull;
         float lp_c = lpk;                                        // log-probability of class (lane + i * step) mod 64
         int cls = lane, mrg = static_cast<int>(merged);
-        for (int i = 0; i < n_live; ++i) {
-            const float sc = rl(p_score, i), bp = rl(p_b, i);
-            const int last = rl(p_last, i);
-            const float v = (cls == last) ? (bp > NEG ? lp_c + bp : NEG) : lp_c + sc;
-            unsigned long long k = beam_key(v, cls + 1, i * BEAM_CLASSES + cls);
-            if (!(lp_c > NEG) || cls == blank || (((mrg | static_cast<int>(excluded)) >> i) & 1)) k = 0ull;
-            const unsigned long long lo = k < m1 ? k : m1;
-            m1 = k > m1 ? k : m1;
-            m2 = lo > m2 ? lo : m2;
-            lp_c = wave_rotate(lp_c);
-            cls = wave_rotate(cls);
-            mrg = wave_rotate(mrg);
+        if constexpr (LM) {                                      // unrolled: w_ext is indexed by constants and stays in registers
+#define BEAM_FUSED(v) beam_fuse(v, w_ext[i])
+#define BEAM_FUSED_STEP(I)                                                                                                         \
+            if ((I) >= n_live) goto scanned;                                                                                       \
+            {                                                                                                                      \
+                constexpr int i = I;                                                                                               \
+                BEAM_SCAN_STEP(BEAM_FUSED)                                                                                         \
+            }
+            BEAM_FOR_EACH_PREFIX(BEAM_FUSED_STEP)
+#undef BEAM_FUSED_STEP
+#undef BEAM_FUSED
+        scanned:;
+        } else {
+#define BEAM_UNFUSED(v) v
+            for (int i = 0; i < n_live; ++i) BEAM_SCAN_STEP(BEAM_UNFUSED)
+#undef BEAM_UNFUSED
         }
         return make_ulonglong2(m1, m2);
     };
@@ -282,7 +377,8 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
         p_last = s_last; p_node = s_node; p_len = s_len; p_hash = s_hash; p_phash = s_phash;
         p_best = s_best;
     } else if (mine_valid) {
-        const float v = (col == s_last) ? (s_b > NEG ? lp_col + s_b : NEG) : lp_col + s_score;
+        // LM: the fused sum the scan formed for this candidate, as its key holds it (the same adds in the same order, without a table read)
+        const float v = LM ? beam_key_score(my_pick) : (col == s_last) ? (s_b > NEG ? lp_col + s_b : NEG) : lp_col + s_score;
         p_b = NEG; p_nb = v; p_score = v;
         p_last = col; p_len = s_len + 1; p_phash = s_hash; p_hash = extend_hash(s_hash, col);
         p_node = -1 - s_node;                                       // parent's node, until this prefix gets its own
@@ -320,14 +416,14 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
 // The next frame's row is loaded before the current frame runs.  A macro, not a function: a helper is optimised on its own before it
 // is inlined, and the frame body then lands 8 to 12 bytes earlier in the search and step kernels, which costs them 2 % (measured:
 // profiles/streaming/beam_refactor_ab.json).  Expanded in place, the loop is compiled as it was when each kernel spelled it out.
-#define BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0)                                                   \
+#define BEAM_FRAMES(TIMED, LM, st, lp_b, len, pool, classes, width, blank, lane, t0, w_lds)                                        \
     do {                                                                                                                           \
         float lp_next = ((len) > 0 && (lane) < (classes)) ? (lp_b)[lane] : NEG;                                                    \
         for (int t = 0; t < (len); ++t) {                                                                                          \
             const float lp = lp_next;                                     /* class `lane` of frame t */                            \
             if (t + 1 < (len) && (lane) < (classes))                      /* in flight during this frame */                        \
                 lp_next = (lp_b)[static_cast<size_t>(t + 1) * (classes) + (lane)];                                                 \
-            beam_frame<TIMED>(st, lp, pool, classes, width, blank, lane, (t0) + t);                                                \
+            beam_frame<TIMED, LM>(st, lp, pool, classes, width, blank, lane, (t0) + t, w_lds);                                     \
         }                                                                                                                          \
     } while (0)
 
@@ -336,13 +432,15 @@ __device__ __forceinline__ void beam_frame(BeamLanes& st, float lp, int2* __rest
 // 2.5 %, the timed peek 2 % and the width-1 search 3 % (profiles/streaming/beam_refactor_ab.json), for 15 lines saved.
 // TIMED: timesteps(batch, width, frames) = the frame of every token's record, 0 beyond the beam's length.  (What the timed instantiations
 // take in addition comes last in every kernel's arguments: the untimed ones read theirs where they always did.)
-template <bool TIMED>
+template <bool TIMED, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ lengths, int2* __restrict__ pool_all, int* __restrict__ beams,
-    float* __restrict__ scores, int* __restrict__ beam_lens, int frames, int classes, int width, int blank, int* __restrict__ timesteps)
+    float* __restrict__ scores, int* __restrict__ beam_lens, int frames, int classes, int width, int blank, int* __restrict__ timesteps,
+    const float* __restrict__ fusion)
 {
     constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float* w_lds = beam_stage_fusion<LM>(fusion, classes, lane);
     const int len = lengths ? min(max(lengths[b], 0), frames) : frames;
     int2* __restrict__ pool = pool_all + static_cast<size_t>(b) * (static_cast<size_t>(frames) * width + 1) * NS;
     const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
@@ -355,7 +453,7 @@ __global__ __launch_bounds__(64) void ctc_beam_search_kernel(
     st.n_live = 1; st.n_nodes = 1;
     if (lane == 0) pool[0] = make_int2(-1, -1);
 
-    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, 0);
+    BEAM_FRAMES(TIMED, LM, st, lp_b, len, pool, classes, width, blank, lane, 0, w_lds);
 
     // results, best first (the selection of the last frame already ordered them; a zero-length utterance has the empty prefix)
     __syncthreads();                                                   // pool entries written by other lanes
@@ -499,15 +597,16 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_init_kernel(char* __restri
 // usage[b] = pool nodes in use afterwards, or -1: the chunk could overflow the pool, nothing was done.
 // TIMED: committed_frames / partial_frames, rows like committed / partial, hold each written token's frame (counted per utterance from the
 // init, over the frames of all steps that counted for it); the records move with their nodes through the compaction.
-template <bool TIMED>
+template <bool TIMED, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ chunk_lengths, char* __restrict__ state, int* __restrict__ ids_all,
     int* __restrict__ committed, int* __restrict__ committed_counts, int* __restrict__ partial, int* __restrict__ partial_counts,
     int* __restrict__ usage, int frames, int classes, int width, int blank, int pool_nodes, int* __restrict__ committed_frames,
-    int* __restrict__ partial_frames)
+    int* __restrict__ partial_frames, const float* __restrict__ fusion)
 {
     constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float* w_lds = beam_stage_fusion<LM>(fusion, classes, lane);      // before the refusal below: a barrier every lane reaches
     const BeamStreamRecord rec = beam_stream_record(state, b, width, pool_nodes, TIMED);
     int2* __restrict__ pool = rec.pool;
     const int t0 = TIMED ? rec.hdr[BS_FRAMES] : 0;
@@ -521,7 +620,7 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_kernel(
     const float* __restrict__ lp_b = log_probs + static_cast<size_t>(b) * frames * classes;
 
     BeamLanes st = beam_stream_load<TIMED>(rec, n_live0, n_nodes0, lane);
-    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0);
+    BEAM_FRAMES(TIMED, LM, st, lp_b, len, pool, classes, width, blank, lane, t0, w_lds);
     __syncthreads();                                                   // pool entries written by other lanes
 
     // ---- the committed prefix
@@ -645,14 +744,15 @@ __host__ __device__ constexpr size_t beam_stream_peek_nodes(int frames, int widt
 // runs there, and the finish layout is written from the lanes in registers: suffixes after the record's committed prefix (the step would
 // commit more of them, which moves tokens from the suffix to the head and changes no token).  The scratch holds the record's nodes and the
 // chunk's, so there is no refusal for a full pool.  frames == 0 is the finish kernel.
-template <bool TIMED>
+template <bool TIMED, bool LM>
 __global__ __launch_bounds__(64) void ctc_beam_stream_peek_kernel(
     const float* __restrict__ log_probs, const int* __restrict__ chunk_lengths, const char* __restrict__ state, int2* __restrict__ scratch_all,
     int* __restrict__ beams, float* __restrict__ scores, int* __restrict__ beam_lens, int ld, int frames, int classes, int width, int blank,
-    int pool_nodes, int* __restrict__ timesteps)
+    int pool_nodes, int* __restrict__ timesteps, const float* __restrict__ fusion)
 {
     constexpr int NS = NODE_INT2<TIMED>;
     const int b = blockIdx.x, lane = threadIdx.x;
+    const float* w_lds = beam_stage_fusion<LM>(fusion, classes, lane);
     const BeamStreamRecord rec = beam_stream_record(const_cast<char*>(state), b, width, pool_nodes, TIMED);
     const int2* __restrict__ src_pool = rec.pool;
     int2* __restrict__ pool = scratch_all + static_cast<size_t>(b) * beam_stream_peek_nodes(frames, width, pool_nodes) * NS;
@@ -667,7 +767,7 @@ __global__ __launch_bounds__(64) void ctc_beam_stream_peek_kernel(
     __syncthreads();
 
     BeamLanes st = beam_stream_load<TIMED>(rec, n_live0, n_nodes0, lane);
-    BEAM_FRAMES(TIMED, st, lp_b, len, pool, classes, width, blank, lane, t0);
+    BEAM_FRAMES(TIMED, LM, st, lp_b, len, pool, classes, width, blank, lane, t0, w_lds);
     __syncthreads();                                                   // pool entries written by other lanes
 
     // TIMED: the step commits the longest common token prefix of the live prefixes and reports the committed tokens' frames from the BEST
@@ -809,8 +909,9 @@ static const float* beam_prune(const float* log_probs, float* pruned, int batch,
     return pruned;
 }
 
-// the untimed and the timed entry points share their checks; `timed` selects the kernel instantiation
-static int beam_search(const char* fn, bool timed, const float* log_probs, const int* lengths, void* ws, int* beams, float* scores,
+// the untimed, the timed and the fused entry points share their checks; `timed` and `lm` select the kernel instantiation.  lm: `fusion` is
+// the table (classes x classes floats on the device), refused when NULL before anything else is looked at
+static int beam_search(const char* fn, bool timed, bool lm, const float* fusion, const float* log_probs, const int* lengths, void* ws, int* beams, float* scores,
                        int* timesteps, int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
                        nbasr_stream_t stream)
 {
@@ -819,15 +920,17 @@ static int beam_search(const char* fn, bool timed, const float* log_probs, const
                   "%s: bad sizes (batch=%d frames=%d classes=%d blank=%d cutoff_top_n=%d)", fn, batch, frames, classes, blank, cutoff_top_n);
     NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
                   "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    NBASR_REQUIRE(!lm || fusion, NBASR_ENULL, "%s: NULL fusion table", fn);
     if (batch == 0) return NBASR_OK;
     NBASR_REQUIRE(ws && scores && beam_lens && (frames == 0 || (log_probs && beams && (!timed || timesteps))), NBASR_ENULL, "%s: NULL pointer", fn);
     NBASR_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, NBASR_EALIGN, "%s: workspace must be 8-byte aligned", fn);
     hipStream_t s = as_stream(stream);
     float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_pool_bytes(batch, frames, beam_width, timed));
     const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
-    auto kernel = timed ? ctc_beam_search_kernel<true> : ctc_beam_search_kernel<false>;
+    auto kernel = lm ? (timed ? ctc_beam_search_kernel<true, true> : ctc_beam_search_kernel<false, true>)
+                     : (timed ? ctc_beam_search_kernel<true, false> : ctc_beam_search_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, lengths, static_cast<int2*>(ws), beams, scores, beam_lens, frames, classes,
-                       beam_width, blank, timesteps);
+                       beam_width, blank, timesteps, fusion);
     return launch_status(fn);
 }
 
@@ -835,7 +938,7 @@ extern "C" int nbasr_ctc_beam_search(const float* log_probs, const int* lengths,
                                      int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
                                      nbasr_stream_t stream)
 {
-    return beam_search("nbasr_ctc_beam_search", false, log_probs, lengths, ws, beams, scores, nullptr, beam_lens, batch, frames, classes,
+    return beam_search("nbasr_ctc_beam_search", false, false, nullptr, log_probs, lengths, ws, beams, scores, nullptr, beam_lens, batch, frames, classes,
                        beam_width, blank, cutoff_top_n, stream);
 }
 
@@ -843,8 +946,16 @@ extern "C" int nbasr_ctc_beam_search_timed(const float* log_probs, const int* le
                                            int* beam_lens, int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n,
                                            nbasr_stream_t stream)
 {
-    return beam_search("nbasr_ctc_beam_search_timed", true, log_probs, lengths, ws, beams, scores, timesteps, beam_lens, batch, frames,
-                       classes, beam_width, blank, cutoff_top_n, stream);
+    return beam_search("nbasr_ctc_beam_search_timed", true, false, nullptr, log_probs, lengths, ws, beams, scores, timesteps, beam_lens, batch,
+                       frames, classes, beam_width, blank, cutoff_top_n, stream);
+}
+
+extern "C" int nbasr_ctc_beam_search_lm(const float* log_probs, const int* lengths, const float* fusion, void* ws, int* beams, float* scores,
+                                        int* timesteps, int* beam_lens, int batch, int frames, int classes, int beam_width, int blank,
+                                        int cutoff_top_n, int timed, nbasr_stream_t stream)
+{
+    return beam_search("nbasr_ctc_beam_search_lm", timed != 0, true, fusion, log_probs, lengths, ws, beams, scores, timed ? timesteps : nullptr,
+                       beam_lens, batch, frames, classes, beam_width, blank, cutoff_top_n, stream);
 }
 
 static size_t beam_stream_state_bytes(int batch, int beam_width, int pool_nodes, bool timed)
@@ -892,7 +1003,7 @@ extern "C" int nbasr_ctc_beam_stream_timed_init(void* state, int batch, int beam
     return beam_stream_init("nbasr_ctc_beam_stream_timed_init", true, state, batch, beam_width, pool_nodes, stream);
 }
 
-static int beam_stream_step(const char* fn, bool timed, const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
+static int beam_stream_step(const char* fn, bool timed, bool lm, const float* fusion, const float* log_probs, const int* chunk_lengths, void* state, void* ws, int* committed,
                             int* committed_frames, int* committed_counts, int* partial, int* partial_frames, int* partial_counts, int* usage,
                             int batch, int frames, int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
@@ -902,6 +1013,7 @@ static int beam_stream_step(const char* fn, bool timed, const float* log_probs, 
                   fn, batch, frames, classes, blank, cutoff_top_n, pool_nodes);
     NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
                   "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    NBASR_REQUIRE(!lm || fusion, NBASR_ENULL, "%s: NULL fusion table", fn);
     if (batch == 0) return NBASR_OK;
     NBASR_REQUIRE(state && ws && committed && committed_counts && partial && partial_counts && usage && (frames == 0 || log_probs) &&
                       (!timed || (committed_frames && partial_frames)), NBASR_ENULL, "%s: NULL pointer", fn);
@@ -909,10 +1021,11 @@ static int beam_stream_step(const char* fn, bool timed, const float* log_probs, 
     hipStream_t s = as_stream(stream);
     float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + static_cast<size_t>(batch) * pool_nodes * sizeof(int));
     const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
-    auto kernel = timed ? ctc_beam_stream_kernel<true> : ctc_beam_stream_kernel<false>;
+    auto kernel = lm ? (timed ? ctc_beam_stream_kernel<true, true> : ctc_beam_stream_kernel<false, true>)
+                     : (timed ? ctc_beam_stream_kernel<true, false> : ctc_beam_stream_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<char*>(state), static_cast<int*>(ws), committed,
                        committed_counts, partial, partial_counts, usage, frames, classes, beam_width, blank, pool_nodes, committed_frames,
-                       partial_frames);
+                       partial_frames, fusion);
     return launch_status(fn);
 }
 
@@ -920,7 +1033,7 @@ extern "C" int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chu
                                           int* committed_counts, int* partial, int* partial_counts, int* usage, int batch, int frames,
                                           int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
-    return beam_stream_step("nbasr_ctc_beam_stream_step", false, log_probs, chunk_lengths, state, ws, committed, nullptr, committed_counts,
+    return beam_stream_step("nbasr_ctc_beam_stream_step", false, false, nullptr, log_probs, chunk_lengths, state, ws, committed, nullptr, committed_counts,
                             partial, nullptr, partial_counts, usage, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
 }
 
@@ -929,9 +1042,19 @@ extern "C" int nbasr_ctc_beam_stream_timed_step(const float* log_probs, const in
                                                 int* partial_counts, int* usage, int batch, int frames, int classes, int beam_width, int blank,
                                                 int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
-    return beam_stream_step("nbasr_ctc_beam_stream_timed_step", true, log_probs, chunk_lengths, state, ws, committed, committed_frames,
-                            committed_counts, partial, partial_frames, partial_counts, usage, batch, frames, classes, beam_width, blank,
-                            cutoff_top_n, pool_nodes, stream);
+    return beam_stream_step("nbasr_ctc_beam_stream_timed_step", true, false, nullptr, log_probs, chunk_lengths, state, ws, committed,
+                            committed_frames, committed_counts, partial, partial_frames, partial_counts, usage, batch, frames, classes, beam_width,
+                            blank, cutoff_top_n, pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_lm_step(const float* log_probs, const int* chunk_lengths, const float* fusion, void* state, void* ws,
+                                             int* committed, int* committed_frames, int* committed_counts, int* partial, int* partial_frames,
+                                             int* partial_counts, int* usage, int batch, int frames, int classes, int beam_width, int blank,
+                                             int cutoff_top_n, int pool_nodes, int timed, nbasr_stream_t stream)
+{
+    return beam_stream_step("nbasr_ctc_beam_stream_lm_step", timed != 0, true, fusion, log_probs, chunk_lengths, state, ws, committed,
+                            timed ? committed_frames : nullptr, committed_counts, partial, timed ? partial_frames : nullptr, partial_counts, usage,
+                            batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
 }
 
 static int beam_stream_finish(const char* fn, bool timed, const void* state, int* beams, float* scores, int* timesteps, int* beam_lens,
@@ -978,7 +1101,7 @@ extern "C" size_t nbasr_ctc_beam_stream_peek_workspace_bytes(int batch, int fram
     return beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes) + pruned;
 }
 
-static int beam_stream_peek(const char* fn, bool timed, const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams,
+static int beam_stream_peek(const char* fn, bool timed, bool lm, const float* fusion, const float* log_probs, const int* chunk_lengths, const void* state, void* ws, int* beams,
                             float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width,
                             int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
@@ -988,6 +1111,7 @@ static int beam_stream_peek(const char* fn, bool timed, const float* log_probs, 
                   fn, batch, frames, classes, blank, cutoff_top_n, pool_nodes, ld_beams);
     NBASR_REQUIRE(classes <= BEAM_CLASSES && beam_width >= 1 && beam_width <= BEAM_MAX, NBASR_EINVAL,
                   "%s: classes=%d (limit %d) / beam_width=%d (limit %d) unsupported", fn, classes, BEAM_CLASSES, beam_width, BEAM_MAX);
+    NBASR_REQUIRE(!lm || fusion, NBASR_ENULL, "%s: NULL fusion table", fn);
     if (batch == 0) return NBASR_OK;
     NBASR_REQUIRE(state && ws && scores && beam_lens && (frames == 0 || log_probs) && (ld_beams == 0 || (beams && (!timed || timesteps))),
                   NBASR_ENULL, "%s: NULL pointer", fn);
@@ -996,9 +1120,10 @@ static int beam_stream_peek(const char* fn, bool timed, const float* log_probs, 
     hipStream_t s = as_stream(stream);
     float* pruned = reinterpret_cast<float*>(static_cast<char*>(ws) + beam_stream_peek_pool_bytes(batch, frames, beam_width, pool_nodes));
     const float* src = beam_prune(log_probs, pruned, batch, frames, classes, cutoff_top_n, s);
-    auto kernel = timed ? ctc_beam_stream_peek_kernel<true> : ctc_beam_stream_peek_kernel<false>;
+    auto kernel = lm ? (timed ? ctc_beam_stream_peek_kernel<true, true> : ctc_beam_stream_peek_kernel<false, true>)
+                     : (timed ? ctc_beam_stream_peek_kernel<true, false> : ctc_beam_stream_peek_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(batch), dim3(64), 0, s, src, chunk_lengths, static_cast<const char*>(state), static_cast<int2*>(ws), beams,
-                       scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps);
+                       scores, beam_lens, ld_beams, frames, classes, beam_width, blank, pool_nodes, timesteps, fusion);
     return launch_status(fn);
 }
 
@@ -1006,7 +1131,7 @@ extern "C" int nbasr_ctc_beam_stream_peek(const float* log_probs, const int* chu
                                           int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width, int blank,
                                           int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
-    return beam_stream_peek("nbasr_ctc_beam_stream_peek", false, log_probs, chunk_lengths, state, ws, beams, scores, nullptr, beam_lens, ld_beams,
+    return beam_stream_peek("nbasr_ctc_beam_stream_peek", false, false, nullptr, log_probs, chunk_lengths, state, ws, beams, scores, nullptr, beam_lens, ld_beams,
                             batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
 }
 
@@ -1014,8 +1139,18 @@ extern "C" int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const in
                                                 float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes,
                                                 int beam_width, int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream)
 {
-    return beam_stream_peek("nbasr_ctc_beam_stream_timed_peek", true, log_probs, chunk_lengths, state, ws, beams, scores, timesteps, beam_lens,
-                            ld_beams, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
+    return beam_stream_peek("nbasr_ctc_beam_stream_timed_peek", true, false, nullptr, log_probs, chunk_lengths, state, ws, beams, scores, timesteps,
+                            beam_lens, ld_beams, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes, stream);
+}
+
+extern "C" int nbasr_ctc_beam_stream_lm_peek(const float* log_probs, const int* chunk_lengths, const float* fusion, const void* state, void* ws,
+                                             int* beams, float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames,
+                                             int classes, int beam_width, int blank, int cutoff_top_n, int pool_nodes, int timed,
+                                             nbasr_stream_t stream)
+{
+    return beam_stream_peek("nbasr_ctc_beam_stream_lm_peek", timed != 0, true, fusion, log_probs, chunk_lengths, state, ws, beams, scores,
+                            timed ? timesteps : nullptr, beam_lens, ld_beams, batch, frames, classes, beam_width, blank, cutoff_top_n, pool_nodes,
+                            stream);
 }
 
 extern "C" int nbasr_token_error_counts(const int* hyp, const int* hyp_len, int ld_hyp, const int* ref, const int* ref_len, int ld_ref,

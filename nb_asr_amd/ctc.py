@@ -58,7 +58,59 @@ def _lengths(lengths, batch, device):
     return lengths.to(device=device, dtype=torch.int32).contiguous()
 
 
-def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n=40, *, return_timesteps=False):
+def bigram_lm(targets, targets_len, classes=49, blank=0, smoothing=1.0):
+    """The classical LM of a phoneme recogniser: a bigram estimated from transcripts.  ``targets`` (N, L) integer labels with their lengths
+    ``targets_len`` (N) (tensors or sequences; labels beyond a length are ignored, ``blank`` is never a label).  Returns a (classes, classes)
+    float32 tensor of ``log P(c | prev)`` on ``targets``' device, from add-``smoothing`` counts over the non-blank classes:
+    ``(count(prev, c) + smoothing) / (count(prev, .) + smoothing * (classes - 1))``.  Row ``blank`` is the distribution of first tokens (the
+    context of the empty prefix); column ``blank`` is filled with its row's minimum (a finite value; the search never reads it).
+    Plain torch, any device."""
+    targets = torch.as_tensor(targets).to(torch.int64)
+    if targets.dim() != 2:
+        raise ValueError(f'targets must be (transcripts, labels), got {tuple(targets.shape)}')
+    n, width = targets.shape
+    lens = torch.as_tensor(targets_len).to(device=targets.device, dtype=torch.int64).reshape(-1)
+    if lens.numel() != n:
+        raise ValueError(f'expected {n} lengths, got {lens.numel()}')
+    valid = torch.arange(width, device=targets.device)[None, :] < lens.clamp(0, width)[:, None]
+    if bool(((targets[valid] < 0) | (targets[valid] >= classes) | (targets[valid] == blank)).any()):
+        raise ValueError(f'labels must lie in [0, {classes}) and differ from blank={blank}')
+    prev = torch.cat([torch.full((n, 1), blank, dtype=torch.int64, device=targets.device), targets[:, :-1]], 1)
+    counts = torch.zeros(classes * classes, dtype=torch.float64, device=targets.device)
+    counts.index_add_(0, (prev * classes + targets)[valid], torch.ones(int(valid.sum()), dtype=torch.float64, device=targets.device))
+    counts = counts.view(classes, classes) + float(smoothing)
+    counts[:, blank] = 0.0
+    lm = torch.log(counts / counts.sum(1, keepdim=True))
+    lm[:, blank] = float('inf')
+    lm[:, blank] = lm.min(1).values
+    return lm.to(torch.float32)
+
+
+def fusion_table(lm, alpha=1.0, beta=0.0, device=None):
+    """The table the fused searches add (nbasr.h "bigram LM fusion"): ``W = alpha * lm + beta`` in float32, contiguous, on ``device``
+    (None: where ``lm`` is).  ``lm``: (C, C) ``log P(c | prev)`` with row ``blank`` for the start of an utterance, e.g. ``bigram_lm``;
+    ``alpha`` weighs the LM, ``beta`` is added per token (ctcdecode's alpha / beta).  Raises ``ValueError`` for anything but a square
+    matrix of at most 64 classes or for entries that are not finite: the one place that validates a table."""
+    lm = torch.as_tensor(lm)
+    if lm.dim() != 2 or lm.shape[0] != lm.shape[1] or not 1 <= lm.shape[0] <= 64:
+        raise ValueError(f'lm must be (classes, classes) with at most 64 classes, got {tuple(lm.shape)}')
+    table = lm.to(torch.float32) * torch.tensor(alpha, dtype=torch.float32) + torch.tensor(beta, dtype=torch.float32)
+    if not bool(torch.isfinite(table).all()):
+        raise ValueError('every entry of alpha * lm + beta must be finite (a forbidden transition is not supported)')
+    return table.to(device=lm.device if device is None else device).contiguous()
+
+
+def _fusion(lm, alpha, beta, classes, device):
+    """None without an LM, else the fusion table for a search over ``classes`` classes on ``device``."""
+    if lm is None:
+        return None
+    table = fusion_table(lm, alpha, beta, device)
+    if classes is not None and table.shape[0] != classes:
+        raise ValueError(f'lm has {table.shape[0]} classes, the log-probabilities {classes}')
+    return table
+
+
+def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n=40, *, return_timesteps=False, lm=None, alpha=1.0, beta=0.0):
     """CTC prefix beam search over log-probabilities (B, T', C), the reference's
     ``CTCBeamDecoder(vocab, beam_width=12, log_probs_input=True).decode(output, output_len)`` (trainer.py:71,237).
 
@@ -67,11 +119,18 @@ def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n
     are 0), scores (B, beam_width) = -log P (lower is better), out_len (B, beam_width) int32.  ``return_timesteps=True`` returns
     ctcdecode's four outputs in its order, ``(beams, scores, timesteps, out_len)``: timesteps (B, beam_width, T') int32, for
     every token the frame at which its class was most probable among the frames that extended into it (DESIGN.md §9 "Beam
-    decode"; 0 beyond ``out_len``).  The search is the same one, bit for bit."""
+    decode"; 0 beyond ``out_len``).  The search is the same one, bit for bit.
+
+    ``lm``: a (C, C) matrix of ``log P(c | previous token)`` (``bigram_lm``; row ``blank`` = start of the utterance) fused into the search
+    as ctcdecode's scorer is: every extension of a prefix ending in p by class c adds ``alpha * lm[p][c] + beta`` to the log score
+    (``fusion_table``; DESIGN.md §9 "Beam decode").  ``scores`` are then minus the fused log score.  None: no LM, today's search."""
     if log_probs.dim() != 3:
         raise ValueError(f'log_probs must be (batch, frames, classes), got {tuple(log_probs.shape)}')
-    return hip.ctc_beam_search(log_probs.contiguous(), _lengths(output_len, log_probs.shape[0], log_probs.device),
-                               beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps))
+    lengths = _lengths(output_len, log_probs.shape[0], log_probs.device)
+    if lm is None:
+        return hip.ctc_beam_search(log_probs.contiguous(), lengths, beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps))
+    return hip.ctc_beam_search(log_probs.contiguous(), lengths, beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps),
+                               fusion=_fusion(lm, alpha, beta, log_probs.shape[2], log_probs.device))
 
 
 class BeamSearchStream:
@@ -92,9 +151,13 @@ class BeamSearchStream:
     ``timesteps=True`` (``beam_decode(..., return_timesteps=True)`` fed chunk by chunk): ``push`` returns ``(committed, partial,
     committed_frames, partial_frames)`` -- lists of int32 CPU tensors aligned with the token lists, each token's frame counted per
     utterance from ``reset()`` across pushes; a committed token's frame is final -- and ``finish()`` returns
-    ``(beams, scores, timesteps, out_len)``."""
+    ``(beams, scores, timesteps, out_len)``.
 
-    def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None, timesteps=False):
+    ``lm``, ``alpha``, ``beta``: ``beam_decode``'s bigram fusion fed chunk by chunk.  The table is built once, here; ``push`` and ``peek``
+    use it, ``reset()`` keeps it, and every chunk must have the table's classes."""
+
+    def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None, timesteps=False, *, lm=None, alpha=1.0,
+                 beta=0.0):
         batch, beam_width = int(batch), int(beam_width)
         if batch < 1:
             raise ValueError(f'batch must be positive (got {batch})')
@@ -107,6 +170,7 @@ class BeamSearchStream:
             raise ValueError(f'the beam search runs on a HIP device (got {device}); this package has no CPU path')
         self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
         self.initial_pool_nodes = int(pool_nodes) if pool_nodes is not None else 1 + beam_width * 4 * 40
+        self.fusion = _fusion(lm, alpha, beta, None, self.device)          # the fusion table on the device, or None: no LM
         self.state = None
         self._peek_ws = None                      # peek's scratch pool, kept between peeks (reset() keeps it too)
         self.reset()
@@ -129,7 +193,7 @@ class BeamSearchStream:
         self.committed_frames = [[] for _ in range(self.batch)]       # with timesteps: aligned with committed / partial
         self.partial_frames = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
         self.frames = 0
-        self.classes = None
+        self.classes = None if self.fusion is None else self.fusion.shape[0]
         self.grown = 0
         self._finished = False
 
@@ -181,8 +245,9 @@ class BeamSearchStream:
         if need > self.pool_nodes:
             self._grow(need)
         chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
+        lm = {} if self.fusion is None else {'fusion': self.fusion}
         *rows_out, counts = hip.ctc_beam_stream_step(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes,
-                                                     self.blank, self.cutoff_top_n, self.timesteps)
+                                                     self.blank, self.cutoff_top_n, self.timesteps, **lm)
         committed, partial = rows_out[:2]
         counts = counts.cpu()
         if bool((counts[2] < 0).any()):
@@ -227,8 +292,9 @@ class BeamSearchStream:
         chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
         self.reserve_peek(n, c)
         ld = max(int(self.usage.max()) - 1 + n, 1)               # a frame lengthens a suffix by at most one token
+        lm = {} if self.fusion is None else {'fusion': self.fusion}
         outs = hip.ctc_beam_stream_peek(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes, ld, self.blank,
-                                        self.cutoff_top_n, self.timesteps, self._peek_ws)
+                                        self.cutoff_top_n, self.timesteps, self._peek_ws, **lm)
         return self._assemble(outs, self.frames + n)
 
     def reserve_peek(self, frames, classes=None):
@@ -284,11 +350,12 @@ def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):
     return counts[:, 0].float() / counts[:, 1].float()
 
 
-def decode_per(log_probs, output_len, targets, targets_len, beam_width=12, fold_to=39, num_classes=48):
+def decode_per(log_probs, output_len, targets, targets_len, beam_width=12, fold_to=39, num_classes=48, *, lm=None, alpha=1.0, beta=0.0):
     """``Trainer.decode`` (trainer.py:229-247): best beam and targets folded to ``fold_to`` phonemes, error rate per
     utterance, mean over the batch.  ``log_probs`` (B, T', num_classes + 1) on the device; targets (B, L) labels of the
-    ``num_classes`` set (0 = blank / padding).  Returns a 0-dim float32 device tensor."""
-    beams, _, beams_len = beam_decode(log_probs, output_len, beam_width=beam_width)
+    ``num_classes`` set (0 = blank / padding).  Returns a 0-dim float32 device tensor.  ``lm``, ``alpha``, ``beta``: ``beam_decode``'s."""
+    fused = {} if lm is None else {'lm': lm, 'alpha': alpha, 'beta': beta}
+    beams, _, beams_len = beam_decode(log_probs, output_len, beam_width=beam_width, **fused)
     table = fold_table(num_classes, fold_to).to(log_probs.device) if fold_to < num_classes else None
     per = error_rates(beams[:, 0].contiguous(), beams_len[:, 0].contiguous(), targets, targets_len, blank=0, table=table)
     return per.mean()

@@ -120,6 +120,9 @@ SIGNATURES = {
     'nbasr_ctc_beam_stream_peek_workspace_bytes': (ctypes.c_size_t, [_c_int] * 5),
     'nbasr_ctc_beam_stream_peek': (_c_int, [_c_float_p] * 2 + [ctypes.c_void_p] + [_c_float_p] * 4 + [_c_int] * 8 + [_c_stream]),
     'nbasr_ctc_beam_stream_timed_peek': (_c_int, [_c_float_p] * 2 + [ctypes.c_void_p] + [_c_float_p] * 5 + [_c_int] * 8 + [_c_stream]),
+    'nbasr_ctc_beam_search_lm': (_c_int, [_c_float_p] * 8 + [_c_int] * 7 + [_c_stream]),
+    'nbasr_ctc_beam_stream_lm_step': (_c_int, [_c_float_p] * 12 + [_c_int] * 8 + [_c_stream]),
+    'nbasr_ctc_beam_stream_lm_peek': (_c_int, [_c_float_p] * 3 + [ctypes.c_void_p] + [_c_float_p] * 5 + [_c_int] * 9 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -983,22 +986,40 @@ def _int_tensor(t, what, device, shape=None):
     return t
 
 
-def _beam_call(lib, name, timed_name, timesteps, args, timed_tensors=()):
+def _beam_call(lib, name, timed_name, timesteps, args, timed_tensors=(), fusion=None, lm_name=None):
     """One call of the beam entry point ``name``; with ``timesteps`` of its timed relative ``timed_name``, whose arguments are the same
-    with the pointers of ``timed_tensors`` = ((position in the TIMED argument list, tensor), ...), in ascending order, put in."""
-    if timesteps:
+    with the pointers of ``timed_tensors`` = ((position in the TIMED argument list, tensor), ...), in ascending order, put in.
+    ``fusion`` (a fusion table, ``_fusion``): the call goes to the fused relative ``lm_name`` instead, which takes the timed argument list
+    (NULL for the timed outputs of an untimed call) with the table third, after the lengths, and ``timed`` before the stream."""
+    if timesteps or fusion is not None:
         name, args = timed_name, list(args)
         for at, tensor in timed_tensors:
-            args.insert(at, tensor.data_ptr())
+            args.insert(at, None if tensor is None else tensor.data_ptr())
+    if fusion is not None:
+        args.insert(2, fusion.data_ptr())
+        args.insert(len(args) - 1, 1 if timesteps else 0)
+        name = lm_name
     _check(getattr(lib, name)(*args), name)
 
 
-def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False):
+def _fusion(fusion, classes, device):
+    """A fusion table as the fused entry points read it: contiguous float32 (classes, classes) on the device of the log-probabilities
+    (``ctc.fusion_table`` makes and validates one)."""
+    if (not isinstance(fusion, torch.Tensor) or fusion.dtype != torch.float32 or fusion.device != device or not fusion.is_contiguous()
+            or tuple(fusion.shape) != (classes, classes)):
+        raise HipError(f'fusion must be a contiguous float32 tensor ({classes}, {classes}) on {device} (ctc.fusion_table)')
+    return fusion
+
+
+def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False, fusion=None):
     """log_probs (B, T', C) float32 log-probabilities -> (beams (B, W, T') int32 best first, scores (B, W) = -log P,
     beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None.  ``timesteps``: the timed search
-    (nbasr_ctc_beam_search_timed) -> (beams, scores, timesteps (B, W, T') int32, beam_lens)."""
+    (nbasr_ctc_beam_search_timed) -> (beams, scores, timesteps (B, W, T') int32, beam_lens).  ``fusion``: a fusion table (C, C) float32 on
+    the device (nbasr.h "bigram LM fusion"): the fused search, nbasr_ctc_beam_search_lm, timed or not; None: the entry points above."""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
+    if fusion is not None:
+        _fusion(fusion, c, log_probs.device)
     if lengths is not None:
         _int_tensor(lengths, 'lengths', log_probs.device, (b,))
     dev = log_probs.device
@@ -1011,7 +1032,7 @@ def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_
     ws = torch.empty(max(ws_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
     _beam_call(lib, 'nbasr_ctc_beam_search', 'nbasr_ctc_beam_search_timed', timesteps,
                (log_probs.data_ptr(), None if lengths is None else lengths.data_ptr(), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
-                lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, _stream(log_probs)), [(5, steps)] if timesteps else ())
+                lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, _stream(log_probs)), [(5, steps)], fusion, 'nbasr_ctc_beam_search_lm')
     return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
 
 
@@ -1037,14 +1058,17 @@ def ctc_beam_stream_init(state, batch, beam_width, pool_nodes, timesteps=False):
     _check(getattr(lib, name)(_state(state), batch, beam_width, pool_nodes, _stream(state)), name)
 
 
-def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40, timesteps=False):
+def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40, timesteps=False, fusion=None):
     """One chunk of a streaming beam search (nbasr.h: nbasr_ctc_beam_stream_step): log_probs (B, n, C) float32, chunk_lengths (B)
     int32 device tensor or None.  Returns device tensors (committed (B, pool_nodes), partial (B, pool_nodes), counts (3, B) int32 =
     committed counts, partial counts, pool usage (-1: refused, the pool is too small for this chunk)).  ``timesteps`` (a state of the
-    timed family, nbasr_ctc_beam_stream_timed_step): (committed, partial, committed_frames, partial_frames, counts)."""
+    timed family, nbasr_ctc_beam_stream_timed_step): (committed, partial, committed_frames, partial_frames, counts).  ``fusion``: as
+    ``ctc_beam_search`` takes it (nbasr_ctc_beam_stream_lm_step, over a state of either family)."""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     dev = log_probs.device
+    if fusion is not None:
+        _fusion(fusion, c, dev)
     if chunk_lengths is not None:
         _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
     if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
@@ -1057,7 +1081,7 @@ def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes
     _beam_call(lib, 'nbasr_ctc_beam_stream_step', 'nbasr_ctc_beam_stream_timed_step', timesteps,
                (lp_ptr, len_ptr, _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(), counts[1].data_ptr(),
                 counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)),
-               [(5, out[2]), (8, out[3])] if timesteps else ())
+               [(5, out[2]), (8, out[3])] if timesteps else [(5, None), (8, None)], fusion, 'nbasr_ctc_beam_stream_lm_step')
     return (*out, counts)
 
 
@@ -1082,14 +1106,17 @@ def ctc_beam_stream_peek_workspace_bytes(batch, frames, classes, beam_width, poo
     return int(load_library().nbasr_ctc_beam_stream_peek_workspace_bytes(int(batch), int(frames), int(classes), int(beam_width), int(pool_nodes)))
 
 
-def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes, ld, blank=0, cutoff_top_n=40, timesteps=False, ws=None):
+def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes, ld, blank=0, cutoff_top_n=40, timesteps=False, ws=None,
+                         fusion=None):
     """What ``ctc_beam_stream_finish`` would return after a ``ctc_beam_stream_step`` of this chunk, with ``state`` only read (nbasr.h:
     nbasr_ctc_beam_stream_peek, ``timesteps``: nbasr_ctc_beam_stream_timed_peek): log_probs (B, n, C) float32, n >= 0; returns
     ``ctc_beam_stream_finish``'s tuple with suffixes (B, W, ld).  ``ws``: a device tensor of ``ctc_beam_stream_peek_workspace_bytes`` bytes
-    to use (None: one is allocated)."""
+    to use (None: one is allocated).  ``fusion``: as ``ctc_beam_search`` takes it (nbasr_ctc_beam_stream_lm_peek)."""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     dev = log_probs.device
+    if fusion is not None:
+        _fusion(fusion, c, dev)
     if chunk_lengths is not None:
         _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
     if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
@@ -1106,7 +1133,7 @@ def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes
     lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
     _beam_call(load_library(), 'nbasr_ctc_beam_stream_peek', 'nbasr_ctc_beam_stream_timed_peek', timesteps,
                (lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2], b, t, c,
-                beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)), [(6, steps)] if timesteps else ())
+                beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)), [(6, steps)], fusion, 'nbasr_ctc_beam_stream_lm_peek')
     return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
 
 

@@ -232,9 +232,11 @@ class _Peek:
 class StreamingSession:
     """Chunk-by-chunk forward of ``model`` for a lockstep batch of ``batch`` utterances (``ASRModel.stream``).  Owns its windows, LSTM
     state and packed weights (never a plan of ``model._plans``: plain ``model(x)`` calls in between keep working); every launch goes to
-    the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here."""
+    the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here.  ``lm``, ``alpha``,
+    ``beta``: the bigram fusion of ``ctc.beam_decode`` for the session's beam searches (``decode='beam'`` and ``'beam-timed'``); ``ASRModel.stream`` keeps its parameter list, so a session with an LM is made with this
+    constructor, which takes ``stream``'s arguments after the model."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, lm=None, alpha=1.0, beta=0.0):
         from .ops import PadConvRelu, Linear, Zero
         from .frontend import LogMelFrontend
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
@@ -251,6 +253,8 @@ class StreamingSession:
             raise ValueError(f'batch and max_chunk must be positive (got {batch}, {max_chunk})')
         self.model, self.batch, self.max_chunk, self.device = model, batch, max_chunk, p0.device
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
+        from .ctc import fusion_table
+        self._lm = {} if lm is None else {'lm': fusion_table(lm, alpha, beta, p0.device)}         # validated here; handed on as built
         self._beam = None                         # ctc.BeamSearchStream, made by the first push with decode='beam'
         self._beam_timed = None                   # ... with timesteps=True, by the first push with decode='beam-timed'
         self._peek = None                         # _Peek: scratch window and state copies, made by the first peek
@@ -562,7 +566,7 @@ class StreamingSession:
     def _beam_make(self, decode):
         if self._beam_decoder(decode) is None:
             from .ctc import BeamSearchStream
-            dec = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device, timesteps=decode == 'beam-timed')
+            dec = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device, timesteps=decode == 'beam-timed', **self._lm)
             if decode == 'beam-timed':
                 self._beam_timed = dec
             else:
