@@ -335,6 +335,16 @@ class BeamSearchStream:
         return outs[0].to(self.device), scores, out_len.to(self.device)
 
 
+def empty_beam_result(batch, beam_width, device, timesteps=False):
+    """``BeamSearchStream.finish()`` of a search that saw no frame, without a search or a launch: the empty prefix alone, at
+    -log P = -0.0; ``(beams (B, W, 0), scores, out_len)``, with ``timesteps`` ``(beams, scores, timesteps (B, W, 0), out_len)``."""
+    scores = torch.full((batch, beam_width), torch.finfo(torch.float32).max)
+    scores[:, 0] = -0.0
+    none = torch.zeros(batch, beam_width, 0, dtype=torch.int32).to(device)
+    lens = torch.zeros(batch, beam_width, dtype=torch.int32).to(device)
+    return (none, scores.to(device), none.clone(), lens) if timesteps else (none, scores.to(device), lens)
+
+
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):
     """Per-utterance token error rate, ``torch_edit_distance.compute_wer(hyp, ref, hyp_len, ref_len, blank, sep=[])``
     (trainer.py:245): Levenshtein distance / reference length, after mapping both sides through ``table`` (optional int32

@@ -31,6 +31,8 @@ utterance's true start / end, where the full forward's padding is the same zeros
 import torch
 
 from . import hip
+from .ctc import BeamSearchStream, empty_beam_result, fusion_table
+from .frontend import LogMelFrontend
 
 FEATURES = 80
 FILTERS = (600, 800, 1000, 1200)
@@ -207,25 +209,67 @@ class StreamPlanner:
             new = new // sp.stride + sp.right // sp.stride + 3
         return caps
 
+    def max_provisional_frames(self):
+        """The most output frames a peek can return (host only; a session sizes its beam peek workspace with it, once): the largest
+        ``output_frames(f + 2) - done[-1]`` after f single-frame steps, the 2 being a front-end's end frames.  The emitted count is a
+        function of the frames received alone and repeats with period 4 once frames are emitted, so the first lookahead + 32 show it."""
+        probe, most = StreamPlanner(self.specs), 1
+        for f in range(1, self.lookahead + 33):
+            probe.step(1)
+            total = f + 2
+            for sp in self.specs:
+                total = out_length(total, sp.stride)
+            most = max(most, total - probe.done[-1])
+        return most
 
-class _Peek:
-    """What ``StreamingSession.peek`` runs on instead of the session's carried state: a planner copy, a table of every stage's current
-    window (buffer, row pitch), copies of the LSTM state and of the greedy decoder's previous token.  A ping-pong pair can host ONE
-    uncommitted step (built in the other buffer, the pair not flipped).  A peek of an audio session is two: the front-end's end frames
-    as a push, then the final step, which would overwrite the window the push just built.  The final step's windows are consumed by
-    their own stage at once and never retained, so it builds all of them in one shared scratch window (sized for the largest stage
-    window).  Only a session with ``max_chunk`` 1 pushes its two end frames in two steps; it gets a third buffer per stage."""
 
-    def __init__(self):
-        self.planner = self.window = self.pushes = self.scratch_window = self.thirds = self.prev_token = self.c_state = self.h_state = None
-        self._lstm_started, self.max_frames = False, 1
+def node_names(cell):
+    """A SearchCell's nodes as ``stage_specs`` takes them: [[op name, identity flag per skip input...], ...]."""
+    from .ops import PadConvRelu, Linear, Zero
+    conv_names = {shape: name for name, shape in CONV_OPS.items()}
+    names = []
+    for node in cell.nodes:
+        op = node.op
+        if isinstance(op, PadConvRelu):
+            name = conv_names[(op.kernel_size, op.dilation)]
+        elif isinstance(op, Linear):
+            name = 'linear'
+        elif isinstance(op, Zero):
+            name = 'zero'
+        else:
+            raise ValueError(f'unsupported node operation {type(op).__name__}')
+        names.append([name] + [int(type(br).__name__ == 'Identity') for br in node.branch_ops])
+    return names
 
-    def destination(self, k, other):
-        """Where the step under way builds stage k's window: the final step in the scratch window, push 0 in the pair's other buffer,
-        push 1 (retained for the final step, so one per stage) in a third buffer."""
-        if self.pushes is None:
-            return self.scratch_window
-        return other if self.pushes == 0 else self.thirds[k]
+
+class _Carried:
+    """What a step reads and advances, and nothing else: the planner, per stage the current window as (buffer, row pitch), whether the
+    LSTM has started with its ``h`` / ``c`` tensors (None without the LSTM), the greedy decoder's previous token, the frame counters.
+    A session owns the committed one; its first ``peek`` makes a second with tensors of its own, and every peek steps on that one after
+    ``refresh`` -- which is why a peek leaves the session as it was."""
+
+    def __init__(self, planner, buffers, h, c, prev_token):
+        self.planner, self.h, self.c, self.prev_token = planner, h, c, prev_token
+        self.window = [(b, 0) for b in buffers]
+        self.reset()
+
+    def reset(self):
+        self.planner.reset()
+        self.window = [(b, 0) for b, _ in self.window]
+        self.lstm_started = False
+        self.frames_in = self.frames_out = 0
+        self.prev_token.fill_(-1)
+
+    def refresh(self, other):
+        """Take ``other``'s state: steps on this record then leave ``other`` alone."""
+        self.planner = other.planner.copy()
+        self.window = list(other.window)
+        self.lstm_started = other.lstm_started
+        self.frames_in, self.frames_out = other.frames_in, other.frames_out
+        self.prev_token.copy_(other.prev_token)
+        if other.lstm_started:                   # (the recurrence's cell_ws is in/out)
+            self.c.copy_(other.c)
+            self.h.copy_(other.h)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -233,12 +277,11 @@ class StreamingSession:
     """Chunk-by-chunk forward of ``model`` for a lockstep batch of ``batch`` utterances (``ASRModel.stream``).  Owns its windows, LSTM
     state and packed weights (never a plan of ``model._plans``: plain ``model(x)`` calls in between keep working); every launch goes to
     the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here.  ``lm``, ``alpha``,
-    ``beta``: the bigram fusion of ``ctc.beam_decode`` for the session's beam searches (``decode='beam'`` and ``'beam-timed'``); ``ASRModel.stream`` keeps its parameter list, so a session with an LM is made with this
-    constructor, which takes ``stream``'s arguments after the model."""
+    ``beta``: the bigram fusion of ``ctc.beam_decode`` for the session's beam searches (``decode='beam'`` and ``'beam-timed'``);
+    ``ASRModel.stream`` keeps its parameter list, so a session with an LM is made with this constructor, which takes ``stream``'s
+    arguments after the model."""
 
     def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, lm=None, alpha=1.0, beta=0.0):
-        from .ops import PadConvRelu, Linear, Zero
-        from .frontend import LogMelFrontend
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
         p0 = model.model[0].conv.weight
@@ -253,29 +296,15 @@ class StreamingSession:
             raise ValueError(f'batch and max_chunk must be positive (got {batch}, {max_chunk})')
         self.model, self.batch, self.max_chunk, self.device = model, batch, max_chunk, p0.device
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
-        from .ctc import fusion_table
         self._lm = {} if lm is None else {'lm': fusion_table(lm, alpha, beta, p0.device)}         # validated here; handed on as built
-        self._beam = None                         # ctc.BeamSearchStream, made by the first push with decode='beam'
-        self._beam_timed = None                   # ... with timesteps=True, by the first push with decode='beam-timed'
-        self._peek = None                         # _Peek: scratch window and state copies, made by the first peek
-        arch = [[type(n.op).__name__, *(int(type(br).__name__ == 'Identity') for br in n.branch_ops)] for n in model.model[2].nodes]
-        names = []
-        for (kind, *flags), node in zip(arch, model.model[2].nodes):
-            op = node.op
-            if isinstance(op, PadConvRelu):
-                name = {(5, 1): 'conv5', (5, 2): 'conv5d2', (7, 1): 'conv7', (7, 2): 'conv7d2'}[(op.kernel_size, op.dilation)]
-            elif isinstance(op, Linear):
-                name = 'linear'
-            elif isinstance(op, Zero):
-                name = 'zero'
-            else:
-                raise ValueError(f'unsupported node operation {kind}')
-            names.append([name] + flags)
+        self._beams = {}                          # decode value -> ctc.BeamSearchStream, made by the first push / peek that decodes so
+        self._peek = None                         # the _Carried a peek steps on; with its windows below, made by the first peek
+        self._peek_window = self._peek_thirds = self._peek_frames = None
+        names = node_names(model.model[2])
         self.specs = stage_specs(names, model.use_rnn, model.use_norm)
-        self.planner = StreamPlanner(self.specs)
-        self.lookahead_frames = self.planner.lookahead
-        caps = self.planner.capacities(max_chunk)
-        self.caps = caps
+        planner = StreamPlanner(self.specs)
+        self.lookahead_frames = planner.lookahead
+        self.caps = caps = planner.capacities(max_chunk)
         dev, B = self.device, batch
         self._bufs = []
 
@@ -284,34 +313,37 @@ class StreamingSession:
             self._bufs.append(t)
             return t
 
-        # ping-pong windows per stage (the head / LSTM input: one buffer, nothing is retained), scratch for outputs and node results
-        self.windows, self.turn = [], [0] * len(self.specs)
-        out_elems, node_elems = 0, 0
+        # a pair of windows per stage (the head / LSTM input: one buffer, nothing is retained), scratch for outputs and node results
+        self.windows = []
+        out_elems = node_elems = need_pw = 0
+        has_linear = any(n[0] == 'linear' for n in names)
         for sp, cap in zip(self.specs, caps):
-            n = B * sp.c_in * hip.round_up4(cap)
+            ld = hip.round_up4(cap)
+            n = B * sp.c_in * ld
             self.windows.append([buf(n), buf(n)] if sp.kind in ('dense', 'cell') else [buf(n)])
             if sp.kind in ('dense', 'cell'):
                 out_elems = max(out_elems, B * sp.c_out * hip.round_up4(out_length(cap, sp.stride)))
             if sp.kind == 'cell':
-                node_elems = max(node_elems, B * sp.c_out * hip.round_up4(cap))
+                node_elems = max(node_elems, B * sp.c_out * ld)
+            if sp.kind == 'lstm' or (sp.kind == 'cell' and has_linear):
+                need_pw = max(need_pw, hip.load_library().nbasr_pointwise_workspace_bytes(B, sp.c_in, ld))
         self.scratch = buf(out_elems)
         self.node_scratch = [buf(node_elems), buf(node_elems)]
         self.absmax = buf(B)[:B]
-        self.pointwise_ws = None
-        need_pw = 0
-        for sp, cap in zip(self.specs, caps):
-            if sp.kind == 'lstm' or (sp.kind == 'cell' and any(n[0] == 'linear' for n in names)):
-                need_pw = max(need_pw, hip.load_library().nbasr_pointwise_workspace_bytes(B, sp.c_in, hip.round_up4(cap)))
-        if need_pw:
-            self.pointwise_ws = buf(need_pw, torch.uint8)
+        self.pointwise_ws = buf(need_pw, torch.uint8) if need_pw else None
+        h = c = None
         if model.use_rnn:
             lstm_cap = caps[[sp.kind for sp in self.specs].index('lstm')]
             self.gates = buf(lstm_cap * B * 4 * LSTM_HIDDEN)
             self.h_out = buf(B * lstm_cap * LSTM_HIDDEN)
-            self.h_state = buf(B * LSTM_HIDDEN)
-            self.c_state = buf(B * LSTM_HIDDEN)
+            h, c = buf(B * LSTM_HIDDEN), buf(B * LSTM_HIDDEN)
             self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
-        self.prev_token = buf(B, torch.int32)[:B]
+        self._carried = _Carried(planner, [bufs[0] for bufs in self.windows], h, c, buf(B, torch.int32)[:B])
+        # per stage kind (its body -- the function: bound methods would make the session hold itself --, whether it builds a window)
+        cls = StreamingSession
+        bodies = {'dense': (cls._dense, True), 'cell': (cls._cell, True), 'lstm': (cls._lstm, True),
+                  'head': (cls._head_of_lstm, False) if model.use_rnn else (cls._head, True)}
+        self._bodies = [bodies[sp.kind] for sp in self.specs]
         # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
         self._frontend, self.lookahead_samples = None, None
         if frontend is not None:
@@ -362,29 +394,27 @@ class StreamingSession:
             raise ValueError('the model\'s parameters changed after the session packed its weights: create a new session')
 
     # ---- public ----------------------------------------------------------------------------------------------------------------
+    frames_in = property(lambda self: self._carried.frames_in, doc='input frames taken in this utterance')
+    frames_out = property(lambda self: self._carried.frames_out, doc='logit frames returned in this utterance')
+    prev_token = property(lambda self: self._carried.prev_token, doc='(batch) int32: the greedy decoder\'s last argmax, -1 at the start')
+
     @property
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
         front-end its sample tails and the staging buffer, and from the first ``peek`` on the peek's scratch window, state copies and
         beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
-                + sum(d.state_bytes + d.peek_bytes for d in (self._beam, self._beam_timed) if d is not None)
+                + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0))
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
-        self.planner.reset()
-        self.frames_in = 0
-        self.frames_out = 0
+        self._carried.reset()
         self._flushed = False
-        self._lstm_started = False
-        self._ld_prev = [0] * len(self.specs)     # row pitch of every stage's current window
-        self.prev_token.fill_(-1)
         self._beam_frames = 0                    # logit frames fed to the beam search in this utterance
         self._beam_mode = None                   # 'beam' or 'beam-timed': the decoder that has seen this utterance's frames
-        for dec in (self._beam, self._beam_timed):
-            if dec is not None:
-                dec.reset()
+        for mode in sorted(self._beams):         # ('beam' before 'beam-timed')
+            self._beams[mode].reset()
         self._fed = None                         # 'features' (push) or 'audio' (push_audio): one utterance takes one of them
         if self._frontend is not None:
             self._frontend.reset()
@@ -405,23 +435,11 @@ class StreamingSession:
             raise ValueError(f'the chunk must be float32 on {self.device} (got {chunk.dtype} on {chunk.device})')
         if self._fed == 'audio':
             raise ValueError('push after push_audio: an utterance is fed features or samples, not both (reset() starts the next one)')
-        self._check_params()
-        if decode in BEAM_DECODES:
-            self._beam_ready(decode)
+        self._begin(decode)
         self._fed = 'features'
         chunk = chunk.detach().contiguous()
-        outs, n = [], chunk.shape[2]
-        for off in range(0, n, self.max_chunk):
-            outs.append(self._step(chunk, off, min(self.max_chunk, n - off), False))
-        if not outs:
-            outs.append(self._step(None, 0, 0, False))
-        return self._pushed(outs, decode)
-
-    def _pushed(self, outs, decode):
-        logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
-        if decode in BEAM_DECODES:
-            return (logits,) + self._beam_push(logits, decode)
-        return (logits, self._decode(logits)) if decode else logits
+        outs = [self._commit(chunk, off, n) for off, n in self._cuts(chunk.shape[2])] or [self._commit(None, 0, 0)]
+        return self._result(outs, decode)
 
     def push_audio(self, wave_chunk, decode=False):
         """Feed (batch, n) float32 samples of the waveform (a session made with ``frontend=``): the front-end's stream turns them into the
@@ -437,13 +455,10 @@ class StreamingSession:
                 or wave_chunk.dtype != torch.float32 or wave_chunk.device != self.device):
             raise ValueError(f'expected a ({self.batch}, samples) float32 chunk on {self.device}, got {tuple(getattr(wave_chunk, "shape", ()))} '
                              f'{getattr(wave_chunk, "dtype", None)} on {getattr(wave_chunk, "device", None)}')
-        self._check_params()
-        if decode in BEAM_DECODES:
-            self._beam_ready(decode)
+        self._begin(decode)
         self._fed = 'audio'
-        outs = [self._step(self._staging if k else None, 0, k, False)
-                for k in self._frontend.push_tiled(wave_chunk, self._staging, self.max_chunk)]
-        return self._pushed(outs, decode)
+        outs = [self._commit(self._staging if k else None, 0, k) for k in self._frontend.push_tiled(wave_chunk, self._staging, self.max_chunk)]
+        return self._result(outs, decode)
 
     def flush(self, decode=False):
         """End the utterance: the remaining logits, computed with the full forward's zero right-padding.  ``decode='beam'`` returns
@@ -451,21 +466,14 @@ class StreamingSession:
         ``decode='beam-timed'`` ``(logits, (beams, scores, timesteps, out_len))``, its ``return_timesteps=True`` form."""
         if self._flushed:
             raise ValueError('flush called twice: call reset() to start the next utterance')
-        self._check_params()
-        if decode in BEAM_DECODES:
-            self._beam_ready(decode)
-        last = []
+        self._begin(decode)
+        outs = []
         if self._fed == 'audio':                 # the front-end's last 1 or 2 frames first, as a push of features
             m = self._frontend.flush(out=(self._staging, 0)).shape[2]
-            last = [self._step(self._staging, off, min(self.max_chunk, m - off), False) for off in range(0, m, self.max_chunk)]
-        logits = self._step(None, 0, 0, True)
-        if last:
-            logits = torch.cat(last + [logits], 1)
+            outs = [self._commit(self._staging, off, n) for off, n in self._cuts(m)]
+        outs.append(self._commit(None, 0, 0, final=True))
         self._flushed = True
-        if decode in BEAM_DECODES:
-            self._beam_push(logits, decode)
-            return logits, self._beam_decoder(decode).finish()
-        return (logits, self._decode(logits)) if decode else logits
+        return self._result(outs, decode, final=True)
 
     def peek(self, decode=False):
         """What ``flush(decode)`` would return now, without ending anything: the provisional logits (batch, m, 49) of the output frames
@@ -479,77 +487,41 @@ class StreamingSession:
         self._check_params()
         if decode in BEAM_DECODES:
             self._beam_check(decode)
-        B, classes = self.batch, self.model.model[self.specs[-1].layer].out_features
         if self.frames_in == 0:                  # (with a front-end: at most win // 2 samples so far, too few to end an utterance)
-            logits = torch.empty(B, 0, classes, device=self.device, dtype=torch.float32)
-            if decode in BEAM_DECODES:           # the empty prefix alone, at -log P = -0.0: finish() of a search that saw no frame
-                W = self.beam_width
-                scores = torch.full((B, W), torch.finfo(torch.float32).max)
-                scores[:, 0] = -0.0
-                none, lens = torch.zeros(B, W, 0, dtype=torch.int32).to(self.device), torch.zeros(B, W, dtype=torch.int32).to(self.device)
-                return logits, ((none, scores.to(self.device), none.clone(), lens) if decode == 'beam-timed' else (none, scores.to(self.device), lens))
-            return (logits, [torch.zeros(0, dtype=torch.int32) for _ in range(B)]) if decode else logits
-        pk = self._peek_begin()
+            logits = self._logits(0)
+            if decode in BEAM_DECODES:
+                return logits, empty_beam_result(self.batch, self.beam_width, self.device, decode == 'beam-timed')
+            return (logits, [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]) if decode else logits
+        pk = self._peek_record()
         outs = []
-        if self._fed == 'audio':                 # the front-end's end frames as an uncommitted push, then the final step
+        if self._fed == 'audio':                 # the front-end's end frames as uncommitted pushes, then the final step
             m = self._frontend.peek(out=(self._staging, 0)).shape[2]
-            for off in range(0, m, self.max_chunk):
-                outs.append(self._step(self._staging, off, min(self.max_chunk, m - off), False, pk))
-                pk.pushes += 1
-        pk.pushes = None
-        outs.append(self._step(None, 0, 0, True, pk))
+            places = (self._place_other, lambda k, current: self._peek_thirds[k])
+            outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(self._cuts(m))]
+        outs.append(self._step(pk, None, 0, 0, True, lambda k, current: self._peek_window))
         logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
         if decode in BEAM_DECODES:
-            self._beam_make(decode)
-            dec = self._beam_decoder(decode)
-            dec.reserve_peek(pk.max_frames, classes)
-            return logits, dec.peek(hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits)
-        if decode:
-            pk.prev_token.copy_(self.prev_token)
-            tokens, counts = hip.ctc_greedy_stream(logits, pk.prev_token)
-            tokens, counts = tokens.cpu(), counts.cpu()
-            return logits, [tokens[i, : int(counts[i])] for i in range(B)]
-        return logits
+            dec = self._decoder(decode)
+            dec.reserve_peek(self._peek_frames, logits.shape[2])
+            return logits, dec.peek(self._log_probs(logits))
+        return (logits, self._greedy(pk, logits)) if decode else logits
 
-    def _peek_begin(self):
-        """The peek context (``_Peek``), armed with the session's present state; its buffers are allocated by the first peek."""
+    def _peek_record(self):
+        """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
+        builds: the scratch window (sized for the largest stage window) and, for a session that pushes the front-end's two end frames
+        in two steps (``max_chunk`` 1), a third buffer per stage."""
         if self._peek is None:
-            B, pk = self.batch, _Peek()
-            n = max(B * sp.c_in * hip.round_up4(cap) for sp, cap in zip(self.specs, self.caps))
-            numels = [n]
             if self._frontend is not None and self.max_chunk < 2:
-                pk.thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
-                self._bufs.extend(pk.thirds)
-            if self.model.use_rnn:
-                numels += [B * LSTM_HIDDEN] * 2
-            bufs = [torch.empty(max(k, 4), device=self.device, dtype=torch.float32) for k in numels] + [torch.empty(max(B, 4), device=self.device, dtype=torch.int32)]
-            self._bufs.extend(bufs)
-            pk.prev_token = bufs.pop()[:B]
-            if self.model.use_rnn:
-                pk.c_state, pk.h_state = bufs.pop(), bufs.pop()
-            pk.scratch_window = bufs.pop()
-            # the most output frames a peek can return (its beam workspace is sized once): the emitted count is a function of frames_in alone
-            # and repeats with period 4 once frames are emitted, so the first lookahead + 32 input frames (+ 2 front-end end frames) show it
-            probe, pk.max_frames = StreamPlanner(self.specs), 1
-            for f in range(1, self.lookahead_frames + 33):
-                probe.step(1)
-                total = f + 2
-                for sp in self.specs:
-                    total = out_length(total, sp.stride)
-                pk.max_frames = max(pk.max_frames, total - probe.done[-1])
-            self._peek = pk
-        pk = self._peek
-        pk.planner = self.planner.copy()
-        pk.window = [(bufs[t], ld) for bufs, t, ld in zip(self.windows, self.turn, self._ld_prev)]
-        pk.pushes = 0
-        pk._lstm_started = self._lstm_started
-        if self.model.use_rnn and self._lstm_started:
-            pk.c_state.copy_(self.c_state)
-            pk.h_state.copy_(self.h_state)
-        return pk
-
-    def _beam_decoder(self, decode):
-        return self._beam_timed if decode == 'beam-timed' else self._beam
+                self._peek_thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
+                self._bufs.extend(self._peek_thirds)
+            self._peek_window = torch.empty(max(bufs[0].numel() for bufs in self.windows), device=self.device, dtype=torch.float32)
+            h, c = (None if t is None else torch.empty_like(t) for t in (self._carried.h, self._carried.c))
+            prev_token = torch.empty(max(self.batch, 4), device=self.device, dtype=torch.int32)
+            self._bufs.extend(t for t in (self._peek_window, h, c, prev_token) if t is not None)
+            self._peek_frames = self._carried.planner.max_provisional_frames()      # the beam peek workspace is sized once, for these
+            self._peek = _Carried(self._carried.planner.copy(), [], h, c, prev_token[:self.batch])
+        self._peek.refresh(self._carried)
+        return self._peek
 
     def _beam_check(self, decode):
         if self._beam_mode not in (None, decode):
@@ -558,138 +530,152 @@ class StreamingSession:
         if self._beam_frames != self.frames_out:
             raise ValueError(f"decode={decode!r} must see every logit frame of the utterance: use it from the first push on (or reset())")
 
-    def _beam_ready(self, decode):
-        self._beam_check(decode)
-        self._beam_mode = decode
-        self._beam_make(decode)
+    def _begin(self, decode):
+        """Before a push or flush moves a frame: refuse stale weights, and what its beam search could not do."""
+        self._check_params()
+        if decode in BEAM_DECODES:
+            self._beam_check(decode)
+            self._beam_mode = decode
+            self._decoder(decode)
 
-    def _beam_make(self, decode):
-        if self._beam_decoder(decode) is None:
-            from .ctc import BeamSearchStream
-            dec = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device, timesteps=decode == 'beam-timed', **self._lm)
-            if decode == 'beam-timed':
-                self._beam_timed = dec
-            else:
-                self._beam = dec
+    def _decoder(self, decode):
+        if decode not in self._beams:
+            self._beams[decode] = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device,
+                                                   timesteps=decode == 'beam-timed', **self._lm)
+        return self._beams[decode]
 
-    def _beam_push(self, logits, decode):
-        log_probs = hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits
-        self._beam_frames += logits.shape[1]
-        return self._beam_decoder(decode).push(log_probs)
+    @staticmethod
+    def _log_probs(logits):
+        return hip.ctc_postprocess(logits, None, True, False)[0] if logits.shape[1] else logits
 
-    def _decode(self, logits):
-        tokens, counts = hip.ctc_greedy_stream(logits, self.prev_token)
+    def _greedy(self, rec, logits):
+        """The greedy tokens of ``logits``, repeats collapsed against (and carried on in) ``rec.prev_token``."""
+        tokens, counts = hip.ctc_greedy_stream(logits, rec.prev_token)
         tokens, counts = tokens.cpu(), counts.cpu()
         return [tokens[i, : int(counts[i])] for i in range(self.batch)]
 
+    def _result(self, outs, decode, final=False):
+        """What push / push_audio / flush return for their steps' logits."""
+        logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+        if decode in BEAM_DECODES:
+            dec = self._decoder(decode)
+            self._beam_frames += logits.shape[1]
+            pushed = dec.push(self._log_probs(logits))
+            return (logits, dec.finish()) if final else (logits,) + pushed
+        return (logits, self._greedy(self._carried, logits)) if decode else logits
+
     # ---- one step ----------------------------------------------------------------------------------------------------------------
-    def _window(self, k, plan, peek=None):
-        """Rebuild stage k's window [a, b) into its other buffer; returns the window view.  ``peek``: an uncommitted step -- the pair is not
-        flipped, and only the first such step may use the other buffer (``_Peek.destination``)."""
+    # Where a step builds stage k's new window is all that tells a committed step from the steps of a peek: ``place(k, current)``,
+    # ``current`` the buffer that holds the stage's window now.  A committed step and a peek's first push: the pair's other buffer
+    # (``_place_other``).  A peek's second push (``max_chunk`` 1 with a front-end), whose window the final step still reads: the stage's
+    # third buffer.  A peek's final step, whose windows are consumed by their own stage at once and never retained: the scratch window.
+    def _place_other(self, k, current):
+        bufs = self.windows[k]                   # (a one-buffer stage retains nothing: it rebuilds in place)
+        return bufs[0] if current is bufs[-1] else bufs[-1]
+
+    def _cuts(self, n):
+        """(first frame, frames) of the steps that take n frames."""
+        return [(off, min(self.max_chunk, n - off)) for off in range(0, n, self.max_chunk)]
+
+    def _logits(self, frames):
+        return torch.empty(self.batch, frames, self.model.model[self.specs[-1].layer].out_features, device=self.device, dtype=torch.float32)
+
+    def _commit(self, chunk, off, n, final=False):
+        return self._step(self._carried, chunk, off, n, final, self._place_other)
+
+    def _window(self, rec, k, plan, src, place):
+        """Build stage k's window [a, b) from the retained frames of its current one and the new frames at ``src`` = (tensor, first
+        column), in the buffer ``place`` names; returns (the window view, its frames)."""
         sp, B = self.specs[k], self.batch
         n_w = plan.b - plan.a
         if n_w > self.caps[k]:
             raise RuntimeError(f'stage {k}: window of {n_w} frames exceeds its capacity {self.caps[k]} (planner bound)')
-        ld = hip.round_up4(n_w)
-        bufs = self.windows[k]
-        if len(bufs) == 1 and plan.n_hist:
+        if len(self.windows[k]) == 1 and plan.n_hist:
             raise RuntimeError(f'stage {k} ({sp.kind}) has no context but retains {plan.n_hist} frames')
-        if peek is None:
-            old, ld_old = bufs[self.turn[k]], self._ld_prev[k]
-            if len(bufs) == 2:
-                self.turn[k] ^= 1
-            new = bufs[self.turn[k]]
-            self._ld_prev[k] = ld
-        else:
-            old, ld_old = peek.window[k]
-            new = peek.destination(k, bufs[len(bufs) - 1 - self.turn[k]])
-            peek.window[k] = (new, ld)
+        ld = hip.round_up4(n_w)
+        old, ld_old = rec.window[k]
+        new = place(k, old)
+        rec.window[k] = (new, ld)
         dst = new[: B * sp.c_in * ld].view(B, sp.c_in, ld)
-        hist = None
-        if plan.n_hist:
-            hist = old[: B * sp.c_in * ld_old].view(B, sp.c_in, ld_old)
-        src, src_off = self._src
+        hist = old[: B * sp.c_in * ld_old].view(B, sp.c_in, ld_old) if plan.n_hist else None
         absmax = self.absmax if (sp.kind == 'dense' and sp.blk > 0) else None
-        hip.stream_window(hist, plan.hist_off, plan.n_hist, src, src_off, plan.n_new, dst, absmax)
+        hip.stream_window(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst, absmax)
         return dst, n_w
 
-    def _step(self, chunk, off, n, final, peek=None):
-        """One step of the planner on the device; returns its logits.  ``peek`` (a ``_Peek``): the step is not committed -- it runs on the
-        peek's planner copy, window table and LSTM state copies, and no field of the session moves."""
+    def _step(self, rec, chunk, off, n, final, place):
+        """One step of ``rec``'s planner on the device, ``rec`` advanced by it, every new window built where ``place`` says; returns the
+        step's logits."""
+        plans = rec.planner.step(n, final)
+        rec.frames_in += n
+        out = (chunk, off)                       # (tensor, first column) of the frames the next stage appends to its window
+        for k, (sp, plan, (body, windowed)) in enumerate(zip(self.specs, plans, self._bodies)):
+            if plan is None:                     # nothing arrives, nothing is released (a later stage may still release at flush)
+                out = (None, 0)
+                continue
+            window = self._window(rec, k, plan, out, place) if windowed else out
+            out = body(self, rec, k, sp, plan, window) if plan.compute else (None, 0)      # (not: only the window moves)
+        logits = out if isinstance(out, torch.Tensor) else self._logits(0)
+        rec.frames_out += logits.shape[1]
+        return logits
+
+    # the stage bodies: (record, stage index, spec, plan, (window view, its frames)) -> (tensor, first column) of the outputs kept, or the logits
+    def _dense(self, rec, k, sp, plan, window):
+        win, n_w = window
+        m, B = self.model.model, self.batch
+        conv, norm = m[sp.layer], m[sp.layer + 1]
+        t_out = out_length(n_w, sp.stride)
+        ld = hip.round_up4(t_out)
+        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
+        scheme, packed = self._packed[sp.layer]
+        hip.dense_conv1d_fused_packed(win, n_w, packed, sp.c_out, conv.kernel_size, conv.conv.bias.detach(), (), out, conv.strides,
+                                      None, scheme, self.absmax if scheme == 'f16x2' else None)
+        hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, t_out, norm.eps)
+        return out, plan.c - plan.a // sp.stride
+
+    def _cell(self, rec, k, sp, plan, window):
         from .executor import node_into
         from .walk import fused_cell
-        plans = (self.planner if peek is None else peek.planner).step(n, final)
-        m, B = self.model.model, self.batch
-        if peek is None:
-            self.frames_in += n
-        self._src = (chunk, off)                 # (tensor, first column) of the frames the next stage appends to its window
-        logits = None
-        for k, (sp, plan) in enumerate(zip(self.specs, plans)):
-            if plan is None:                     # nothing arrives, nothing is released (a later stage may still release at flush)
-                self._src = (None, 0)
-                continue
-            if sp.kind == 'head' and self.model.use_rnn:
-                head = m[sp.layer]
-                h = self._src[0]
-                logits = torch.empty(B, h.shape[1], head.out_features, device=self.device, dtype=torch.float32)
-                hip.linear_head(h, head.weight.detach(), head.bias.detach(), logits)
-                break
-            win, n_w = self._window(k, plan, peek)
-            if not plan.compute:
-                self._src = (None, 0)
-                continue
-            k0 = plan.c - plan.a // sp.stride
-            if sp.kind == 'dense':
-                conv, norm = m[sp.layer], m[sp.layer + 1]
-                t_out = out_length(n_w, sp.stride)
-                ld = hip.round_up4(t_out)
-                out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-                scheme, packed = self._packed[sp.layer]
-                hip.dense_conv1d_fused_packed(win, n_w, packed, sp.c_out, conv.kernel_size, conv.conv.bias.detach(), (), out, conv.strides,
-                                              None, scheme, self.absmax if scheme == 'f16x2' else None)
-                hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, t_out, norm.eps)
-                self._src = (out, k0)
-            elif sp.kind == 'cell':
-                cell = m[sp.layer]
-                ld = win.shape[2]
-                out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-                nodes = cell.nodes
-                groups = getattr(nodes[-1].op, 'groups', 0)
-                fused, mask = fused_cell(cell, ld)
-                if fused:                        # the executor's one-launch cell (bit-identical to the three node launches)
-                    specs = [(self._packed[id(nd.op)], nd.op.conv.bias.detach(), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
-                    hip.grouped_cell_fused(win, specs, mask, out, n_w, groups)
-                else:
-                    lin_ctx = (lambda lin: self._packed[id(lin)], lambda c_in, ld_: self.pointwise_ws)
-                    outs = [win]
-                    for j, node in enumerate(nodes):
-                        dst = out if j == len(nodes) - 1 else self.node_scratch[j % 2][: B * sp.c_out * ld].view(B, sp.c_out, ld)
-                        outs.append(node_into(node, outs, n_w, dst, None, None, lin_ctx, 0))
-                if cell.use_norm:
-                    norm = cell.norm_layer
-                    hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, n_w, norm.eps)
-                self._src = (out, k0)
-            elif sp.kind == 'lstm':              # no context: the window holds exactly the new frames
-                lstm = m[sp.layer]
-                nf = n_w
-                gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
-                hip.lstm_input_projection_packed(win, nf, self._packed['w_ih'], lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), gates,
-                                                 LSTM_HIDDEN, self.pointwise_ws)
-                h = self.h_out[: B * nf * LSTM_HIDDEN].view(B, nf, LSTM_HIDDEN)
-                carried = self if peek is None else peek             # (a peek runs from copies: cell_ws is in/out)
-                h_state, c_state, cont = carried.h_state[: B * LSTM_HIDDEN], carried.c_state[: B * LSTM_HIDDEN], carried._lstm_started
-                hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], c_state, h, self.xcd_ws,
-                                                   h_state if cont else None, hip.LSTM_CONTINUE if cont else 0)
-                carried._lstm_started = True
-                # h_n = the last frame's h becomes the next call's h0 (h_out seen as one row of nf * H floats per utterance)
-                hip.stream_window(None, 0, 0, h.view(B, 1, nf * LSTM_HIDDEN), (nf - 1) * LSTM_HIDDEN, LSTM_HIDDEN, h_state.view(B, 1, LSTM_HIDDEN))
-                self._src = (h, 0)
-            else:                                # head of a model without the LSTM: reads the encoder output's pitched rows
-                head = m[sp.layer]
-                logits = torch.empty(B, n_w, head.out_features, device=self.device, dtype=torch.float32)
-                hip.linear_head_bct(win, n_w, head.weight.detach(), head.bias.detach(), logits)
-        if logits is None:
-            logits = torch.empty(B, 0, m[self.specs[-1].layer].out_features, device=self.device, dtype=torch.float32)
-        if peek is None:
-            self.frames_out += logits.shape[1]
-        return logits
+        win, n_w = window
+        cell, B = self.model.model[sp.layer], self.batch
+        ld = win.shape[2]
+        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
+        nodes = cell.nodes
+        groups = getattr(nodes[-1].op, 'groups', 0)
+        fused, mask = fused_cell(cell, ld)
+        if fused:                                # the executor's one-launch cell (bit-identical to the three node launches)
+            specs = [(self._packed[id(nd.op)], nd.op.conv.bias.detach(), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
+            hip.grouped_cell_fused(win, specs, mask, out, n_w, groups)
+        else:
+            lin_ctx = (lambda lin: self._packed[id(lin)], lambda c_in, ld_: self.pointwise_ws)
+            outs = [win]
+            for j, node in enumerate(nodes):
+                dst = out if j == len(nodes) - 1 else self.node_scratch[j % 2][: B * sp.c_out * ld].view(B, sp.c_out, ld)
+                outs.append(node_into(node, outs, n_w, dst, None, None, lin_ctx, 0))
+        if cell.use_norm:
+            norm = cell.norm_layer
+            hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, n_w, norm.eps)
+        return out, plan.c - plan.a
+
+    def _lstm(self, rec, k, sp, plan, window):
+        win, nf = window                         # no context: the window holds exactly the new frames
+        lstm, B = self.model.model[sp.layer], self.batch
+        gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
+        hip.lstm_input_projection_packed(win, nf, self._packed['w_ih'], lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), gates,
+                                         LSTM_HIDDEN, self.pointwise_ws)
+        h = self.h_out[: B * nf * LSTM_HIDDEN].view(B, nf, LSTM_HIDDEN)
+        h_state, c_state, cont = rec.h[: B * LSTM_HIDDEN], rec.c[: B * LSTM_HIDDEN], rec.lstm_started
+        hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], c_state, h, self.xcd_ws,
+                                           h_state if cont else None, hip.LSTM_CONTINUE if cont else 0)
+        rec.lstm_started = True
+        # h_n = the last frame's h becomes the next call's h0 (h_out seen as one row of nf * H floats per utterance)
+        hip.stream_window(None, 0, 0, h.view(B, 1, nf * LSTM_HIDDEN), (nf - 1) * LSTM_HIDDEN, LSTM_HIDDEN, h_state.view(B, 1, LSTM_HIDDEN))
+        return h, 0
+
+    def _head_of_lstm(self, rec, k, sp, plan, source):
+        head, h = self.model.model[sp.layer], source[0]              # the LSTM's (batch, frames, hidden) rows, no window
+        return hip.linear_head(h, head.weight.detach(), head.bias.detach(), self._logits(h.shape[1]))
+
+    def _head(self, rec, k, sp, plan, window):
+        win, n_w = window                        # without the LSTM: reads the encoder output's pitched rows
+        head = self.model.model[sp.layer]
+        return hip.linear_head_bct(win, n_w, head.weight.detach(), head.bias.detach(), self._logits(n_w))

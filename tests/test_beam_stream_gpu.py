@@ -270,10 +270,10 @@ def test_session_memory_and_reset():
         for i in range(0, 300, 64):
             plain.push(x[:, :, i:i + 64])
         plain.flush()
-    assert plain.buffer_bytes == before and plain._beam is None        # no beam pushes: no beam state
+    assert plain.buffer_bytes == before and not plain._beams            # no beam pushes: no beam state
     sess = m.stream(batch=2, max_chunk=64)
     _, _, first = _session_decode(sess, x, [64] * 5)
-    assert sess.buffer_bytes == before + sess._beam.state_bytes > before
+    assert sess.buffer_bytes == before + sess._beams['beam'].state_bytes > before
     sess.reset()
     _, _, again = _session_decode(sess, y, [50] * 6)
     _, _, fresh = _session_decode(m.stream(batch=2, max_chunk=64), y, [50] * 6)

@@ -184,7 +184,7 @@ def test_session_peek_decodes_like_flush(decode):
     sess, plain, twin = (m.stream(batch=b, max_chunk=64) for _ in range(3))
     with torch.no_grad():
         assert same(sess.peek(decode=decode), twin.flush(decode=decode))           # before any frame: the empty hypotheses
-        assert sess._beam is None and sess._beam_timed is None and sess._beam_mode is None
+        assert not sess._beams and sess._beam_mode is None
         for i, p in enumerate(pieces):
             assert same(sess.push(p, decode=decode), plain.push(p, decode=decode)), i
             mode = sess._beam_mode
@@ -336,5 +336,5 @@ def test_peek_memory_is_allocated_once_and_only_by_a_peek():
                 marks[i] = (sess.buffer_bytes, torch.cuda.memory_allocated(DEV))
     assert sess.frames_out > 0
     assert marks[2] == marks[29]
-    assert never.buffer_bytes == start + never._beam.state_bytes and never._peek is None and never._beam.peek_bytes == 0
+    assert never.buffer_bytes == start + never._beams['beam'].state_bytes and never._peek is None and never._beams['beam'].peek_bytes == 0
     assert sess.buffer_bytes > never.buffer_bytes

@@ -63,6 +63,31 @@ def test_planner_peek_is_a_flush_that_did_not_happen(arch, use_rnn, sizes):
         peeked.peek()
 
 
+@pytest.mark.parametrize('use_rnn', [True, False])
+@pytest.mark.parametrize('arch,most', [('A', 127), ('D', 127), ('M', 45)])
+def test_max_provisional_frames_is_the_brute_force_maximum(arch, use_rnn, most):
+    """What sizes a session's beam peek workspace: the most frames a peek returns over the first lookahead + 600 single-frame steps, each
+    peek counted on a throw-away planner -- the front-end's two end frames as a push, then the final step -- and without the end frames."""
+    planner = streaming.StreamPlanner(streaming.stage_specs(cases.ARCHS[arch], use_rnn))
+    before = planner_state(planner)
+    got = planner.max_provisional_frames()
+    assert planner_state(planner) == before
+    with_end_frames = without = 0
+    for _ in range(planner.lookahead + 600):
+        planner.step(1)
+        for end_frames in (2, 0):
+            twin = planner.copy()
+            twin.step(end_frames)
+            twin.step(0, final=True)
+            frames = twin.done[-1] - planner.done[-1]
+            assert frames == hip.output_frames(planner.have[0] + end_frames) - planner.done[-1]
+            if end_frames:
+                with_end_frames = max(with_end_frames, frames)
+            else:
+                without = max(without, frames)
+    assert got == with_end_frames == without == most
+
+
 def _declaration(name):
     code = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
     m = re.search(r'(\w+)\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
