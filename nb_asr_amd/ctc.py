@@ -127,10 +127,16 @@ def beam_decode(log_probs, output_len=None, beam_width=12, blank=0, cutoff_top_n
     if log_probs.dim() != 3:
         raise ValueError(f'log_probs must be (batch, frames, classes), got {tuple(log_probs.shape)}')
     lengths = _lengths(output_len, log_probs.shape[0], log_probs.device)
-    if lm is None:
-        return hip.ctc_beam_search(log_probs.contiguous(), lengths, beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps))
     return hip.ctc_beam_search(log_probs.contiguous(), lengths, beam_width, blank, cutoff_top_n, timesteps=bool(return_timesteps),
                                fusion=_fusion(lm, alpha, beta, log_probs.shape[2], log_probs.device))
+
+
+def _cut_rows(host, at, n_c, counts):
+    """One track of a step's rows on the host, its committed rows from column ``at`` and its partial rows ``n_c`` columns on, cut into
+    per-utterance tensors by ``counts`` = (committed counts, partial counts, ...) -> (committed rows, partial rows)."""
+    batch = range(host.shape[0])
+    return ([host[i, at: at + int(counts[0, i])].clone() for i in batch],
+            [host[i, at + n_c: at + n_c + int(counts[1, i])].clone() for i in batch])
 
 
 class BeamSearchStream:
@@ -239,39 +245,38 @@ class BeamSearchStream:
         n, c, rows = self._chunk(log_probs, lengths)
         self.classes = c
         if n == 0:
-            none = [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]
-            return (none, list(self.partial), list(none), list(self.partial_frames)) if self.timesteps else (none, list(self.partial))
+            return self._pushed([[torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)] for _ in self._tracks()])
         need = int(self.usage.max()) + self.beam_width * n + 1
         if need > self.pool_nodes:
             self._grow(need)
         chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
-        lm = {} if self.fusion is None else {'fusion': self.fusion}
         *rows_out, counts = hip.ctc_beam_stream_step(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes,
-                                                     self.blank, self.cutoff_top_n, self.timesteps, **lm)
-        committed, partial = rows_out[:2]
+                                                     self.blank, self.cutoff_top_n, self.timesteps, self.fusion)
         counts = counts.cpu()
         if bool((counts[2] < 0).any()):
             raise hip.HipError('ctc_beam_stream_step: the token pool was too small for the chunk')
         self.usage = counts[2].to(torch.int64)
         n_c, n_p = int(counts[0].max()), int(counts[1].max())
-        parts = [committed[:, :n_c], partial[:, :n_p]]
-        if self.timesteps:
-            parts += [rows_out[2][:, :n_c], rows_out[3][:, :n_p]]
-        host = torch.cat(parts, 1).cpu()
-        new_c = [host[i, : int(counts[0, i])].clone() for i in range(self.batch)]
-        self.partial = [host[i, n_c: n_c + int(counts[1, i])].clone() for i in range(self.batch)]
-        for i in range(self.batch):
-            self.committed[i].append(new_c[i])
+        # one copy for all rows: per track its committed rows cut to n_c columns, then its partial rows cut to n_p
+        host = torch.cat([r[:, :k] for r, k in zip(rows_out, (n_c, n_p) * len(self._tracks()))], 1).cpu()
+        new = []
+        for k, (committed, partial) in enumerate(self._tracks()):
+            more, now = _cut_rows(host, k * (n_c + n_p), n_c, counts)
+            setattr(self, partial, now)
+            for i in range(self.batch):
+                getattr(self, committed)[i].append(more[i])
+            new.append(more)
         self.ended |= rows < n
         self.frames += n
-        if not self.timesteps:
-            return new_c, list(self.partial)
-        at = n_c + n_p
-        new_f = [host[i, at: at + int(counts[0, i])].clone() for i in range(self.batch)]
-        self.partial_frames = [host[i, at + n_c: at + n_c + int(counts[1, i])].clone() for i in range(self.batch)]
-        for i in range(self.batch):
-            self.committed_frames[i].append(new_f[i])
-        return new_c, list(self.partial), new_f, list(self.partial_frames)
+        return self._pushed(new)
+
+    def _tracks(self):
+        """The attributes that hold what a push cuts its rows into, (committed lists, partial list): the tokens and, with timesteps, their frames."""
+        return (('committed', 'partial'), ('committed_frames', 'partial_frames'))[: 2 if self.timesteps else 1]
+
+    def _pushed(self, new):
+        """What a push returns: per track the rows committed by it (``new``), then the partial rows as they now stand."""
+        return tuple(rows for more, (_, partial) in zip(new, self._tracks()) for rows in (more, list(getattr(self, partial))))
 
     def finish(self):
         """End the utterances: ``(beams (B, W, T) int32, scores (B, W), out_len (B, W) int32)`` on the device, ``beam_decode``'s layout
@@ -292,9 +297,8 @@ class BeamSearchStream:
         chunk_lengths = None if lengths is None else rows.to(device=self.device, dtype=torch.int32)
         self.reserve_peek(n, c)
         ld = max(int(self.usage.max()) - 1 + n, 1)               # a frame lengthens a suffix by at most one token
-        lm = {} if self.fusion is None else {'fusion': self.fusion}
         outs = hip.ctc_beam_stream_peek(log_probs.contiguous(), chunk_lengths, self.state, self.beam_width, self.pool_nodes, ld, self.blank,
-                                        self.cutoff_top_n, self.timesteps, self._peek_ws, **lm)
+                                        self.cutoff_top_n, self.timesteps, self._peek_ws, self.fusion)
         return self._assemble(outs, self.frames + n)
 
     def reserve_peek(self, frames, classes=None):
@@ -311,12 +315,8 @@ class BeamSearchStream:
 
     def _assemble(self, outs, frames):
         """Committed heads + the live suffixes of a finish / peek launch -> ``beam_decode``'s layout over ``frames`` frames."""
-        if self.timesteps:
-            suffix, scores, suffix_t, lens = outs
-            tails = [(suffix.cpu(), self.committed), (suffix_t.cpu(), self.committed_frames)]
-        else:
-            suffix, scores, lens = outs
-            tails = [(suffix.cpu(), self.committed)]
+        suffix, scores, *suffix_t, lens = outs
+        tails = [(tail.cpu(), getattr(self, heads)) for tail, (heads, _) in zip((suffix, *suffix_t), self._tracks())]
         lens = lens.cpu()
         outs = [torch.zeros(self.batch, self.beam_width, frames, dtype=torch.int32) for _ in tails]
         live = lens >= 0                                         # (B, W): beyond the live prefixes there is no beam: length 0, padded with 0
@@ -330,9 +330,8 @@ class BeamSearchStream:
                 w = min(tail.shape[2], frames - at)               # a beam holds at most one token per frame: every suffix ends by `frames`
                 keep = torch.arange(w)[None, :] < lens[i][:, None]
                 out[i, :, at: at + w] = torch.where(keep, tail[i, :, :w], 0)
-        if self.timesteps:
-            return outs[0].to(self.device), scores, outs[1].to(self.device), out_len.to(self.device)
-        return outs[0].to(self.device), scores, out_len.to(self.device)
+        beams, timesteps = [out.to(self.device) for out in outs] + [None] * (2 - len(outs))
+        return hip.beam_result(beams, scores, timesteps, out_len.to(self.device))
 
 
 def empty_beam_result(batch, beam_width, device, timesteps=False):
@@ -342,7 +341,7 @@ def empty_beam_result(batch, beam_width, device, timesteps=False):
     scores[:, 0] = -0.0
     none = torch.zeros(batch, beam_width, 0, dtype=torch.int32).to(device)
     lens = torch.zeros(batch, beam_width, dtype=torch.int32).to(device)
-    return (none, scores.to(device), none.clone(), lens) if timesteps else (none, scores.to(device), lens)
+    return hip.beam_result(none, scores.to(device), none.clone() if timesteps else None, lens)
 
 
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):
@@ -364,8 +363,7 @@ def decode_per(log_probs, output_len, targets, targets_len, beam_width=12, fold_
     """``Trainer.decode`` (trainer.py:229-247): best beam and targets folded to ``fold_to`` phonemes, error rate per
     utterance, mean over the batch.  ``log_probs`` (B, T', num_classes + 1) on the device; targets (B, L) labels of the
     ``num_classes`` set (0 = blank / padding).  Returns a 0-dim float32 device tensor.  ``lm``, ``alpha``, ``beta``: ``beam_decode``'s."""
-    fused = {} if lm is None else {'lm': lm, 'alpha': alpha, 'beta': beta}
-    beams, _, beams_len = beam_decode(log_probs, output_len, beam_width=beam_width, **fused)
+    beams, _, beams_len = beam_decode(log_probs, output_len, beam_width=beam_width, lm=lm, alpha=alpha, beta=beta)
     table = fold_table(num_classes, fold_to).to(log_probs.device) if fold_to < num_classes else None
     per = error_rates(beams[:, 0].contiguous(), beams_len[:, 0].contiguous(), targets, targets_len, blank=0, table=table)
     return per.mean()

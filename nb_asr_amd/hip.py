@@ -8,6 +8,7 @@ door (walk.py: the forward; backward.py: the dense and LSTM gradients).  There i
 library or a tensor off the HIP device fails loudly (build with ``python -m nb_asr_amd.build``).
 """
 import ctypes
+import operator
 import os
 import threading
 import pathlib
@@ -986,20 +987,40 @@ def _int_tensor(t, what, device, shape=None):
     return t
 
 
-def _beam_call(lib, name, timed_name, timesteps, args, timed_tensors=(), fusion=None, lm_name=None):
-    """One call of the beam entry point ``name``; with ``timesteps`` of its timed relative ``timed_name``, whose arguments are the same
-    with the pointers of ``timed_tensors`` = ((position in the TIMED argument list, tensor), ...), in ascending order, put in.
-    ``fusion`` (a fusion table, ``_fusion``): the call goes to the fused relative ``lm_name`` instead, which takes the timed argument list
-    (NULL for the timed outputs of an untimed call) with the table third, after the lengths, and ``timed`` before the stream."""
-    if timesteps or fusion is not None:
-        name, args = timed_name, list(args)
-        for at, tensor in timed_tensors:
-            args.insert(at, None if tensor is None else tensor.data_ptr())
-    if fusion is not None:
-        args.insert(2, fusion.data_ptr())
-        args.insert(len(args) - 1, 1 if timesteps else 0)
-        name = lm_name
-    _check(getattr(lib, name)(*args), name)
+# The beam entry points.  Per operation: the name of its entry points -- {} = '' plain, '_timed', '_lm' fused (only where the list has
+# ``fusion``) -- and its widest argument list, in the order of include/nbasr.h.  The fused entry point takes the whole list; the timed
+# one all but ``fusion`` and ``timed``; the plain one drops the timed-only outputs as well.
+_BEAM_OPS = {
+    'search': ('nbasr_ctc_beam_search{}',
+               'log_probs lengths fusion ws beams scores timesteps beam_lens batch frames classes beam_width blank cutoff_top_n timed stream'),
+    'step': ('nbasr_ctc_beam_stream{}_step', 'log_probs chunk_lengths fusion state ws committed committed_frames committed_counts partial '
+             'partial_frames partial_counts usage batch frames classes beam_width blank cutoff_top_n pool_nodes timed stream'),
+    'peek': ('nbasr_ctc_beam_stream{}_peek', 'log_probs chunk_lengths fusion state ws beams scores timesteps beam_lens ld_beams batch frames '
+             'classes beam_width blank cutoff_top_n pool_nodes timed stream'),
+    'finish': ('nbasr_ctc_beam_stream{}_finish', 'state beams scores timesteps beam_lens ld_beams batch beam_width pool_nodes stream'),
+    'init': ('nbasr_ctc_beam_stream{}_init', 'state batch beam_width pool_nodes stream'),
+}
+# (operation, timed, fused) -> (entry point, the names of its arguments in order): every beam call the binding can make
+BEAM_ENTRY_POINTS = {}
+for _op, (_name, _args) in _BEAM_OPS.items():
+    _unfused = [n for n in _args.split() if n not in ('fusion', 'timed')]
+    BEAM_ENTRY_POINTS[_op, False, False] = (_name.format(''), [n for n in _unfused if n not in ('timesteps', 'committed_frames', 'partial_frames')])
+    BEAM_ENTRY_POINTS[_op, True, False] = (_name.format('_timed'), _unfused)
+    if 'fusion' in _args.split():
+        BEAM_ENTRY_POINTS[_op, False, True] = BEAM_ENTRY_POINTS[_op, True, True] = (_name.format('_lm'), _args.split())
+# the same, ready for a call: the picker of the arguments is built once, here
+_BEAM_PICKERS = {key: (name, operator.itemgetter(*names)) for key, (name, names) in BEAM_ENTRY_POINTS.items()}
+
+
+def _beam_call(lib, op, timesteps, fused, values):
+    """One call of the entry point of ``BEAM_ENTRY_POINTS`` for (op, timesteps, fused), its arguments picked from ``values`` by name (a
+    fused, untimed call passes NULL for the timed-only outputs)."""
+    name, pick = _BEAM_PICKERS[op, bool(timesteps), fused]
+    _check(getattr(lib, name)(*pick(values)), name)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 def _fusion(fusion, classes, device):
@@ -1011,29 +1032,56 @@ def _fusion(fusion, classes, device):
     return fusion
 
 
-def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False, fusion=None):
-    """log_probs (B, T', C) float32 log-probabilities -> (beams (B, W, T') int32 best first, scores (B, W) = -log P,
-    beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None.  ``timesteps``: the timed search
-    (nbasr_ctc_beam_search_timed) -> (beams, scores, timesteps (B, W, T') int32, beam_lens).  ``fusion``: a fusion table (C, C) float32 on
-    the device (nbasr.h "bigram LM fusion"): the fused search, nbasr_ctc_beam_search_lm, timed or not; None: the entry points above."""
+def _check_chunk(log_probs, lengths, fusion, lengths_name='lengths'):
+    """The one check of a chunk of log-probabilities (B, n, C) float32 with its int32 lengths (B) or None and its fusion table or None.
+    -> (B, n, C, the device)"""
     _dev(log_probs, 'log_probs')
     b, t, c = log_probs.shape
     if fusion is not None:
         _fusion(fusion, c, log_probs.device)
     if lengths is not None:
-        _int_tensor(lengths, 'lengths', log_probs.device, (b,))
-    dev = log_probs.device
-    beams = torch.empty(b, beam_width, t, dtype=torch.int32, device=dev)
-    scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
-    lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
+        _int_tensor(lengths, lengths_name, log_probs.device, (b,))
+    return b, t, c, log_probs.device
+
+
+def _check_stream_chunk(who, log_probs, chunk_lengths, fusion, state, beam_width, pool_nodes, timesteps):
+    """``_check_chunk`` for the streaming wrapper ``who``, and that ``state`` is one of its family's size on the same device."""
+    b, t, c, dev = _check_chunk(log_probs, chunk_lengths, fusion, 'chunk_lengths')
+    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
+        raise HipError(f'{who}: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
+    return b, t, c, dev
+
+
+def _beam_outputs(batch, beam_width, ld, timesteps, device):
+    """The outputs of a search, a finish or a peek, allocated: (beams (B, W, ld), scores, timesteps like beams | None, beam_lens)."""
+    beams = torch.empty(batch, beam_width, ld, dtype=torch.int32, device=device)
+    scores = torch.empty(batch, beam_width, dtype=torch.float32, device=device)
+    lens = torch.empty(batch, beam_width, dtype=torch.int32, device=device)
+    steps = torch.empty_like(beams) if timesteps else None
+    return beams, scores, steps, lens
+
+
+def beam_result(beams, scores, timesteps, beam_lens):
+    """The four slots of a beam result as the public tuple: ``(beams, scores, timesteps, beam_lens)``, without time steps (None)
+    ``(beams, scores, beam_lens)``."""
+    return (beams, scores, beam_lens) if timesteps is None else (beams, scores, timesteps, beam_lens)
+
+
+def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_n=40, timesteps=False, fusion=None):
+    """log_probs (B, T', C) float32 log-probabilities -> (beams (B, W, T') int32 best first, scores (B, W) = -log P,
+    beam_lens (B, W) int32).  ``lengths``: int32 device tensor (B) of valid output frames, or None.  ``timesteps``: the timed search
+    (nbasr_ctc_beam_search_timed) -> (beams, scores, timesteps (B, W, T') int32, beam_lens).  ``fusion``: a fusion table (C, C) float32 on
+    the device (nbasr.h "bigram LM fusion"): the fused search, nbasr_ctc_beam_search_lm, timed or not; None: the entry points above."""
+    b, t, c, dev = _check_chunk(log_probs, lengths, fusion)
+    beams, scores, steps, lens = outs = _beam_outputs(b, beam_width, t, timesteps, dev)
     lib = load_library()
-    steps = torch.empty(b, beam_width, t, dtype=torch.int32, device=dev) if timesteps else None
     ws_bytes = lib.nbasr_ctc_beam_timed_workspace_bytes if timesteps else lib.nbasr_ctc_beam_workspace_bytes
     ws = torch.empty(max(ws_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
-    _beam_call(lib, 'nbasr_ctc_beam_search', 'nbasr_ctc_beam_search_timed', timesteps,
-               (log_probs.data_ptr(), None if lengths is None else lengths.data_ptr(), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(),
-                lens.data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, _stream(log_probs)), [(5, steps)], fusion, 'nbasr_ctc_beam_search_lm')
-    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
+    _beam_call(lib, 'search', timesteps, fusion is not None, {
+        'log_probs': log_probs.data_ptr(), 'lengths': _ptr(lengths), 'fusion': _ptr(fusion), 'ws': ws.data_ptr(), 'beams': beams.data_ptr(),
+        'scores': scores.data_ptr(), 'timesteps': _ptr(steps), 'beam_lens': lens.data_ptr(), 'batch': b, 'frames': t, 'classes': c,
+        'beam_width': beam_width, 'blank': blank, 'cutoff_top_n': cutoff_top_n, 'timed': 1 if timesteps else 0, 'stream': _stream(log_probs)})
+    return beam_result(*outs)
 
 
 def ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes, timesteps=False):
@@ -1053,9 +1101,8 @@ def ctc_beam_stream_init(state, batch, beam_width, pool_nodes, timesteps=False):
     """Every utterance of ``state`` (a device tensor of ``ctc_beam_stream_state_bytes`` bytes) to the empty prefix."""
     if state.numel() * state.element_size() < ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes, timesteps):
         raise HipError('ctc_beam_stream_init: state tensor too small (ctc_beam_stream_state_bytes)')
-    lib = load_library()
-    name = 'nbasr_ctc_beam_stream_timed_init' if timesteps else 'nbasr_ctc_beam_stream_init'
-    _check(getattr(lib, name)(_state(state), batch, beam_width, pool_nodes, _stream(state)), name)
+    _beam_call(load_library(), 'init', timesteps, False,
+               {'state': _state(state), 'batch': batch, 'beam_width': beam_width, 'pool_nodes': pool_nodes, 'stream': _stream(state)})
 
 
 def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes, blank=0, cutoff_top_n=40, timesteps=False, fusion=None):
@@ -1064,40 +1111,30 @@ def ctc_beam_stream_step(log_probs, chunk_lengths, state, beam_width, pool_nodes
     committed counts, partial counts, pool usage (-1: refused, the pool is too small for this chunk)).  ``timesteps`` (a state of the
     timed family, nbasr_ctc_beam_stream_timed_step): (committed, partial, committed_frames, partial_frames, counts).  ``fusion``: as
     ``ctc_beam_search`` takes it (nbasr_ctc_beam_stream_lm_step, over a state of either family)."""
-    _dev(log_probs, 'log_probs')
-    b, t, c = log_probs.shape
-    dev = log_probs.device
-    if fusion is not None:
-        _fusion(fusion, c, dev)
-    if chunk_lengths is not None:
-        _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
-    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
-        raise HipError('ctc_beam_stream_step: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
-    lib = load_library()
-    out = torch.empty(4 if timesteps else 2, b, pool_nodes, dtype=torch.int32, device=dev)
+    b, t, c, dev = _check_stream_chunk('ctc_beam_stream_step', log_probs, chunk_lengths, fusion, state, beam_width, pool_nodes, timesteps)
+    rows = torch.empty(4 if timesteps else 2, b, pool_nodes, dtype=torch.int32, device=dev).unbind(0)
     counts = torch.empty(3, b, dtype=torch.int32, device=dev)
+    lib = load_library()
     ws = torch.empty(max(lib.nbasr_ctc_beam_stream_workspace_bytes(b, t, c, pool_nodes), 8) // 4 + 1, dtype=torch.int32, device=dev)
-    lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
-    _beam_call(lib, 'nbasr_ctc_beam_stream_step', 'nbasr_ctc_beam_stream_timed_step', timesteps,
-               (lp_ptr, len_ptr, _state(state), ws.data_ptr(), out[0].data_ptr(), counts[0].data_ptr(), out[1].data_ptr(), counts[1].data_ptr(),
-                counts[2].data_ptr(), b, t, c, beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)),
-               [(5, out[2]), (8, out[3])] if timesteps else [(5, None), (8, None)], fusion, 'nbasr_ctc_beam_stream_lm_step')
-    return (*out, counts)
+    count_ptr = counts.data_ptr()                              # its rows: committed counts, partial counts, usage, 4 * b bytes each
+    _beam_call(lib, 'step', timesteps, fusion is not None, {
+        'log_probs': log_probs.data_ptr() if t else None, 'chunk_lengths': _ptr(chunk_lengths), 'fusion': _ptr(fusion), 'state': _state(state),
+        'ws': ws.data_ptr(), 'committed': rows[0].data_ptr(), 'committed_frames': rows[2].data_ptr() if timesteps else None,
+        'committed_counts': count_ptr, 'partial': rows[1].data_ptr(), 'partial_frames': rows[3].data_ptr() if timesteps else None,
+        'partial_counts': count_ptr + 4 * b, 'usage': count_ptr + 8 * b, 'batch': b, 'frames': t, 'classes': c, 'beam_width': beam_width,
+        'blank': blank, 'cutoff_top_n': cutoff_top_n, 'pool_nodes': pool_nodes, 'timed': 1 if timesteps else 0, 'stream': _stream(log_probs)})
+    return (*rows, counts)
 
 
 def ctc_beam_stream_finish(state, batch, beam_width, pool_nodes, ld, timesteps=False):
     """The live prefixes' uncommitted suffixes (nbasr.h: nbasr_ctc_beam_stream_finish): (suffixes (B, W, ld) int32, scores (B, W),
     suffix lengths (B, W) int32, -1 beyond the live prefixes).  ``timesteps`` (nbasr_ctc_beam_stream_timed_finish): (suffixes, scores,
     the suffix tokens' frames (B, W, ld) int32, suffix lengths)."""
-    dev = state.device
-    beams = torch.empty(batch, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
-    scores = torch.empty(batch, beam_width, dtype=torch.float32, device=dev)
-    lens = torch.empty(batch, beam_width, dtype=torch.int32, device=dev)
-    steps = torch.empty_like(beams) if timesteps else None
-    _beam_call(load_library(), 'nbasr_ctc_beam_stream_finish', 'nbasr_ctc_beam_stream_timed_finish', timesteps,
-               (_state(state), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2], batch, beam_width, pool_nodes, _stream(state)),
-               [(3, steps)] if timesteps else ())
-    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
+    beams, scores, steps, lens = outs = _beam_outputs(batch, beam_width, max(int(ld), 1), timesteps, state.device)
+    _beam_call(load_library(), 'finish', timesteps, False, {
+        'state': _state(state), 'beams': beams.data_ptr(), 'scores': scores.data_ptr(), 'timesteps': _ptr(steps), 'beam_lens': lens.data_ptr(),
+        'ld_beams': beams.shape[2], 'batch': batch, 'beam_width': beam_width, 'pool_nodes': pool_nodes, 'stream': _stream(state)})
+    return beam_result(*outs)
 
 
 def ctc_beam_stream_peek_workspace_bytes(batch, frames, classes, beam_width, pool_nodes):
@@ -1112,29 +1149,19 @@ def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes
     nbasr_ctc_beam_stream_peek, ``timesteps``: nbasr_ctc_beam_stream_timed_peek): log_probs (B, n, C) float32, n >= 0; returns
     ``ctc_beam_stream_finish``'s tuple with suffixes (B, W, ld).  ``ws``: a device tensor of ``ctc_beam_stream_peek_workspace_bytes`` bytes
     to use (None: one is allocated).  ``fusion``: as ``ctc_beam_search`` takes it (nbasr_ctc_beam_stream_lm_peek)."""
-    _dev(log_probs, 'log_probs')
-    b, t, c = log_probs.shape
-    dev = log_probs.device
-    if fusion is not None:
-        _fusion(fusion, c, dev)
-    if chunk_lengths is not None:
-        _int_tensor(chunk_lengths, 'chunk_lengths', dev, (b,))
-    if state.device != dev or state.numel() * state.element_size() < ctc_beam_stream_state_bytes(b, beam_width, pool_nodes, timesteps):
-        raise HipError('ctc_beam_stream_peek: state must be a tensor of ctc_beam_stream_state_bytes bytes on the device of log_probs')
+    b, t, c, dev = _check_stream_chunk('ctc_beam_stream_peek', log_probs, chunk_lengths, fusion, state, beam_width, pool_nodes, timesteps)
     need = ctc_beam_stream_peek_workspace_bytes(b, t, c, beam_width, pool_nodes)
     if ws is None:
         ws = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
     elif ws.device != dev or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
         raise HipError(f'ctc_beam_stream_peek: the workspace must be a contiguous tensor of {need} bytes on {dev}')
-    beams = torch.empty(b, beam_width, max(int(ld), 1), dtype=torch.int32, device=dev)
-    scores = torch.empty(b, beam_width, dtype=torch.float32, device=dev)
-    lens = torch.empty(b, beam_width, dtype=torch.int32, device=dev)
-    steps = torch.empty_like(beams) if timesteps else None
-    lp_ptr, len_ptr = log_probs.data_ptr() if t else None, None if chunk_lengths is None else chunk_lengths.data_ptr()
-    _beam_call(load_library(), 'nbasr_ctc_beam_stream_peek', 'nbasr_ctc_beam_stream_timed_peek', timesteps,
-               (lp_ptr, len_ptr, _state(state), ws.data_ptr(), beams.data_ptr(), scores.data_ptr(), lens.data_ptr(), beams.shape[2], b, t, c,
-                beam_width, blank, cutoff_top_n, pool_nodes, _stream(log_probs)), [(6, steps)], fusion, 'nbasr_ctc_beam_stream_lm_peek')
-    return (beams, scores, steps, lens) if timesteps else (beams, scores, lens)
+    beams, scores, steps, lens = outs = _beam_outputs(b, beam_width, max(int(ld), 1), timesteps, dev)
+    _beam_call(load_library(), 'peek', timesteps, fusion is not None, {
+        'log_probs': log_probs.data_ptr() if t else None, 'chunk_lengths': _ptr(chunk_lengths), 'fusion': _ptr(fusion), 'state': _state(state),
+        'ws': ws.data_ptr(), 'beams': beams.data_ptr(), 'scores': scores.data_ptr(), 'timesteps': _ptr(steps), 'beam_lens': lens.data_ptr(),
+        'ld_beams': beams.shape[2], 'batch': b, 'frames': t, 'classes': c, 'beam_width': beam_width, 'blank': blank,
+        'cutoff_top_n': cutoff_top_n, 'pool_nodes': pool_nodes, 'timed': 1 if timesteps else 0, 'stream': _stream(log_probs)})
+    return beam_result(*outs)
 
 
 def token_error_counts(hyp, hyp_len, ref, ref_len, table=None, blank=0):

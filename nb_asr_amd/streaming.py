@@ -296,7 +296,7 @@ class StreamingSession:
             raise ValueError(f'batch and max_chunk must be positive (got {batch}, {max_chunk})')
         self.model, self.batch, self.max_chunk, self.device = model, batch, max_chunk, p0.device
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
-        self._lm = {} if lm is None else {'lm': fusion_table(lm, alpha, beta, p0.device)}         # validated here; handed on as built
+        self._lm = None if lm is None else fusion_table(lm, alpha, beta, p0.device)              # validated here; handed on as built
         self._beams = {}                          # decode value -> ctc.BeamSearchStream, made by the first push / peek that decodes so
         self._peek = None                         # the _Carried a peek steps on; with its windows below, made by the first peek
         self._peek_window = self._peek_thirds = self._peek_frames = None
@@ -541,7 +541,7 @@ class StreamingSession:
     def _decoder(self, decode):
         if decode not in self._beams:
             self._beams[decode] = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device,
-                                                   timesteps=decode == 'beam-timed', **self._lm)
+                                                   timesteps=decode == 'beam-timed', lm=self._lm)
         return self._beams[decode]
 
     @staticmethod

@@ -1,5 +1,5 @@
-"""Plain-Python model of the prefix beam search AS THE KERNEL DEFINES IT, with per-token time steps (helper of
-test_beam_timesteps_host.py and test_beam_timesteps_gpu.py; no tests here).
+"""Plain-Python model of the prefix beam search AS THE KERNEL DEFINES IT, with per-token time steps and bigram LM fusion (helper of
+test_beam_timesteps_host.py, test_beam_timesteps_gpu.py, test_beam_lm_host.py and test_beam_lm_gpu.py; no tests here).
 
 Not a trie: a list of live prefixes (what the lanes of ``beam_frame`` hold) plus a list of token nodes ``[parent, class, frame, best]``
 (the pool).  Prefix identity is the token string (the kernel's 64-bit hash), candidates are ordered like ``beam_key`` (score descending,
@@ -11,6 +11,9 @@ tokens and scores equal the oracle's (test_beam_timesteps_host.py anchors that f
    and lp_t[c] > best (strictly), its OWN node's record becomes (t, lp_t[c]) -- whether or not the parent contributes probability;
 3. re-creation: a prefix that dropped out and is spelled again gets a new node with a fresh record; beams built on the old node keep it;
 4. t is the utterance's own 0-based frame index.
+
+``fusion`` is the table W of include/nbasr.h "bigram LM fusion", one line per rule of its contract (marked below).  Staying on blank and
+repeating the last class get nothing, -FLT_MAX stays -FLT_MAX, and the time-step records look at ``lp`` only.
 
 ``dtype=np.float64`` accumulates the scores in float64 (same inputs): the tests use seeds at which that changes no beam, so a device whose
 exp / log differ in the last bit is not expected to break a tie differently.
@@ -38,11 +41,12 @@ class _Live:
         self.b, self.nb, self.score, self.last, self.node, self.tokens = b, nb, score, last, node, tokens
 
 
-def beam_search(log_probs, beam_width=12, blank=0, cutoff_top_n=40, dtype=np.float32, stats=None):
+def beam_search(log_probs, beam_width=12, blank=0, cutoff_top_n=40, dtype=np.float32, stats=None, fusion=None):
     """log_probs (T, C) float32 of ONE utterance -> [(tokens, -score, timesteps)], best first, at most ``beam_width`` entries.
     ``stats`` (dict): counts 'updates' (rule 2 moved a record) and 'recreated_under_live' (rule 3: a prefix got a second node while a
-    live prefix was still built on its first one)."""
+    live prefix was still built on its first one).  ``fusion``: the table W, (classes, classes) float32, of the fused search."""
     F = dtype
+    W = None if fusion is None else np.asarray(fusion, dtype=np.float32)
     lp_all = np.asarray(log_probs, dtype=np.float32)
     n_cls = lp_all.shape[1] if lp_all.ndim == 2 else 0
     nodes = [[-1, -1, 0, NEG]]                                     # the root
@@ -76,6 +80,8 @@ def beam_search(log_probs, beam_width=12, blank=0, cutoff_top_n=40, dtype=np.flo
                         add = F(lp_last + par.b) if par.b > NEG else F(NEG)
                     else:
                         add = F(lp_last + par.score)
+                    if W is not None and add > NEG:                # fusion: the mass a live prefix absorbs from its live parent
+                        add = F(add + F(W[par.last if par.last >= 0 else blank][p.last]))
                     n_nb = _lse(n_nb, add, F)
             n_score = _lse(n_b, n_nb, F)
             stay.append((n_b, n_nb, n_score))
@@ -88,6 +94,8 @@ def beam_search(log_probs, beam_width=12, blank=0, cutoff_top_n=40, dtype=np.flo
                     v = F(lp[c] + p.b) if p.b > NEG else F(NEG)
                 else:
                     v = F(lp[c] + p.score)
+                if W is not None and v > NEG:                      # fusion: a candidate, live prefix p + class c
+                    v = F(v + F(W[p.last if p.last >= 0 else blank][c]))
                 cands.append((v, c + 1, i * LANES + c, i, c))
         cands.sort(key=lambda k: (-float(k[0]), k[1], k[2]))
         nxt = []
@@ -139,6 +147,11 @@ ORACLE_SHAPES = [(3, 40, 49, 12, 40, 2.0), (2, 60, 49, 12, 40, 0.5), (2, 25, 5, 
                  (2, 12, 3, 12, 40, 1.0), (1, 30, 64, 8, 10, 1.0), (2, 1, 49, 12, 40, 1.0), (1, 16, 2, 3, 1, 1.0)]
 TIMED_SHAPES = [(3, 40, 49, 12, 40, 2.0), (2, 25, 5, 4, 40, 1.0), (2, 30, 49, 1, 40, 3.0), (1, 30, 64, 8, 10, 1.0), (2, 1, 49, 12, 40, 1.0),
                 (1, 16, 2, 3, 1, 1.0)]
+
+
+def fusion_table(classes, seed_offset=5):
+    """The table of the tie-freedom test and of the device comparison: W = (default_rng(5 + C).normal(size=(C, C)) - 0.5) in float32."""
+    return (np.random.default_rng(seed_offset + classes).normal(size=(classes, classes)) - 0.5).astype(np.float32)
 
 
 def shape_input(shape):

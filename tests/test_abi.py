@@ -1,13 +1,12 @@
-"""The C-ABI library loads and exports exactly what include/nbasr.h declares (no GPU needed)."""
+"""The C-ABI library loads and exports exactly what include/nbasr.h declares, and hip.py binds every entry point with the header's
+types (no GPU needed)."""
 import ctypes
-import pathlib
 import re
 
 import pytest
 
 from nb_asr_amd import hip
-
-HEADER = pathlib.Path(__file__).resolve().parent.parent / 'include' / 'nbasr.h'
+from nbasr_header import HEADER, SCALARS, declarations, parameter_ctype
 
 
 def declared_symbols():
@@ -18,7 +17,30 @@ def declared_symbols():
 def test_header_and_binding_agree():
     names = declared_symbols()
     assert len(names) >= 12
-    assert sorted(hip.SIGNATURES) == names
+    assert sorted(hip.SIGNATURES) == sorted(declarations()) == names
+
+
+def test_every_symbol_is_bound_with_the_header_signature():
+    """Argument count, return type and each argument's type, for all of ``hip.SIGNATURES``."""
+    for name, (restype, argtypes) in hip.SIGNATURES.items():
+        ret, params = declarations()[name]
+        assert restype is SCALARS[ret], name
+        assert len(argtypes) == len(params), (name, params)
+        for param, ct in zip(params, argtypes):
+            assert ct is parameter_ctype(name, param), (name, param, ct)
+        assert getattr(hip.load_library(), name).argtypes == argtypes, name
+
+
+def test_beam_binding_passes_every_entry_point_its_parameters_in_the_header_order():
+    """For every (operation, timed, fused) the binding can select: the names it picks its arguments by, in order, are the parameter names
+    of that entry point in the header.  A misordered list would hand a kernel its pointers in the wrong order."""
+    ops = ('search', 'step', 'peek', 'finish', 'init')
+    assert set(hip.BEAM_ENTRY_POINTS) == ({(op, timed, False) for op in ops for timed in (False, True)}
+                                          | {(op, timed, True) for op in ops[:3] for timed in (False, True)})
+    for (op, timed, fused), (name, names) in hip.BEAM_ENTRY_POINTS.items():
+        assert names == [re.search(r'(\w+)$', p).group(1) for p in declarations()[name][1]], (op, timed, fused, name)
+        assert len(names) == len(hip.SIGNATURES[name][1]), name
+        assert ('_lm' in name) == fused and (fused or ('_timed' in name) == timed), (op, timed, fused, name)
 
 
 def test_library_exports_every_declared_symbol(built_library):

@@ -1,18 +1,19 @@
 """Bigram LM fusion of the beam search on the device (ctc.beam_decode(lm=...), ctc.BeamSearchStream(lm=...), StreamingSession(lm=...),
-ctc.decode_per(lm=...)): the fused search returns the beams, lengths and time steps of the plain-Python model (beam_lm_model.py, anchored
+ctc.decode_per(lm=...)): the fused search returns the beams, lengths and time steps of the plain-Python model (beam_timesteps_model.py, anchored
 on exhaustive enumeration by test_beam_lm_host.py, which also asserts that the seeds used here hold no float32 tie), an all-zero table is
-the unfused search bit for bit, and streaming, peek and the session equal the whole fused search bit for bit."""
+the unfused search bit for bit, and streaming, peek and the session equal the whole fused search bit for bit.  Last, the binding: each
+(timed, fused) combination calls exactly its plain, ``_timed`` or ``_lm`` entry points (that their arguments go by the header's names, in
+its order, is test_abi.py's host check)."""
 import functools
 
 import numpy as np
 import pytest
 import torch
 
-import beam_lm_model as lm_model
 import beam_timesteps_model as model
 import cases
 import nb_asr_amd as nb
-from nb_asr_amd import ctc, streaming
+from nb_asr_amd import ctc, hip, streaming
 from nb_asr_amd.weights import keyed_fill_, keyed_input
 
 pytestmark = pytest.mark.gpu
@@ -42,7 +43,7 @@ def _assert_is_model(shape, W, blank=0, **lm):
     for key, lp, _, _ in model.utterances(shape):
         _, kind, i = key
         rows = _rows(whole if kind == 'whole' else ragged, i)
-        want = lm_model.beam_search(lp, width, blank=blank, cutoff_top_n=top_n, fusion=W)
+        want = model.beam_search(lp, width, blank=blank, cutoff_top_n=top_n, fusion=W)
         for r, (tok, score, steps) in enumerate(want):
             g_tok, g_score, g_steps = rows[r]
             assert g_tok == tok, (key, r, g_tok, tok)
@@ -58,7 +59,7 @@ def _assert_is_model(shape, W, blank=0, **lm):
 
 @pytest.mark.parametrize('shape', model.TIMED_SHAPES)
 def test_fused_search_equals_the_model_at_the_shapes(shape):
-    W = lm_model.fusion_table(shape[2])
+    W = model.fusion_table(shape[2])
     _assert_is_model(shape, W, lm=torch.from_numpy(W))
 
 
@@ -70,7 +71,7 @@ def test_alpha_and_beta_scale_and_shift_the_table():
 
 def test_the_blank_row_is_the_start_context_wherever_blank_is():
     shape = (2, 25, 5, 4, 40, 1.0)
-    W = lm_model.fusion_table(5, seed_offset=9)
+    W = model.fusion_table(5, seed_offset=9)
     _assert_is_model(shape, W, blank=2, lm=torch.from_numpy(W))
 
 
@@ -78,7 +79,7 @@ def test_the_blank_row_is_the_start_context_wherever_blank_is():
 def test_a_zero_table_is_the_unfused_search_and_timed_equals_untimed_bit_for_bit(shape):
     b, frames, classes, width, top_n, _ = shape
     lp = model.shape_input(shape).to(DEV)
-    zero, W = torch.zeros(classes, classes), torch.from_numpy(lm_model.fusion_table(classes))
+    zero, W = torch.zeros(classes, classes), torch.from_numpy(model.fusion_table(classes))
     for lengths in (None, model.lengths_of(b, frames)):
         for timed in (False, True):
             want = ctc.beam_decode(lp, lengths, beam_width=width, cutoff_top_n=top_n, return_timesteps=timed)
@@ -136,7 +137,7 @@ def _assert_committed_starts_every_finite_beam(result, tokens, what):
 @pytest.mark.parametrize('b,frames,classes,width', [(2, 40, 49, 12), (2, 40, 4, 3)])
 def test_fused_streaming_equals_the_whole_fused_search_bit_for_bit(b, frames, classes, width, timed):
     lp = _log_probs((b, frames, classes), 31 * frames + width, 2.0 if classes > 5 else 1.0).to(DEV)
-    W = torch.from_numpy(lm_model.fusion_table(classes))
+    W = torch.from_numpy(model.fusion_table(classes))
     saw_commit = False
     for total in (None, [frames, frames // 2]):                   # the second utterance ends early
         want = ctc.beam_decode(lp, total, beam_width=width, return_timesteps=timed, lm=W)
@@ -155,7 +156,7 @@ def test_fused_streaming_equals_the_whole_fused_search_bit_for_bit(b, frames, cl
 def test_fused_stream_grows_its_pool_and_reset_keeps_the_table():
     b, frames, classes, width = 2, 40, 49, 12
     lp = _log_probs((b, frames, classes), 31 * frames + width).to(DEV)
-    W = torch.from_numpy(lm_model.fusion_table(classes))
+    W = torch.from_numpy(model.fusion_table(classes))
     want = ctc.beam_decode(lp, None, beam_width=width, lm=W)
     dec = ctc.BeamSearchStream(b, beam_width=width, device=DEV, pool_nodes=1 + 2 * width, lm=W)
     table = dec.fusion
@@ -176,7 +177,7 @@ def test_fused_stream_grows_its_pool_and_reset_keeps_the_table():
 def test_fused_peek_is_push_and_finish_on_a_twin_and_leaves_the_state(timed):
     b, classes, width = 3, 49, 12
     lp = _log_probs((b, 17 + 33, classes), 19).to(DEV)
-    W = torch.from_numpy(lm_model.fusion_table(classes))
+    W = torch.from_numpy(model.fusion_table(classes))
     first, nxt, lengths = lp[:, :17], lp[:, 17:], [33, 0, 20]
     dec, twin = (ctc.BeamSearchStream(b, beam_width=width, device=DEV, timesteps=timed, lm=W) for _ in range(2))
     dec.push(first, [17, 9, 17])
@@ -211,7 +212,7 @@ def test_session_decodes_with_the_lm(decode):
     m = _session_model()
     b, t = 2, 200
     x = keyed_input(b, t, seed=5).to(DEV)
-    W = torch.from_numpy(lm_model.fusion_table(49))
+    W = torch.from_numpy(model.fusion_table(49))
     sess = streaming.StreamingSession(m, batch=b, max_chunk=40, lm=W, alpha=0.7, beta=0.2)      # what model.stream builds, with the LM
     logits, tokens = [], [[] for _ in range(b)]
     with torch.no_grad():
@@ -243,3 +244,53 @@ def test_decode_per_with_the_lm_is_the_error_rate_of_the_fused_best_beam():
     assert torch.equal(got, want)
     plain = ctc.beam_decode(lp, output_len)
     assert not torch.equal(plain[0][:, 0], beams[:, 0])           # with this alpha the LM moves the best beam
+
+
+# ---- the binding: which entry points a combination calls ---------------------------------------------------------------------------------
+
+def _entry_points(timed, fused):
+    """What a search, then a stream's init, step, peek, step and finish call: a fused search, step or peek is ``_lm`` whether timed or not;
+    init and finish have no fused form and go by the state's family."""
+    chunk, state = '_lm' if fused else '_timed' if timed else '', '_timed' if timed else ''
+    return [f'nbasr_ctc_beam_search{chunk}', f'nbasr_ctc_beam_stream{state}_init', f'nbasr_ctc_beam_stream{chunk}_step',
+            f'nbasr_ctc_beam_stream{chunk}_peek', f'nbasr_ctc_beam_stream{chunk}_step', f'nbasr_ctc_beam_stream{state}_finish']
+
+
+@pytest.mark.parametrize('fused', [False, True], ids=['unfused', 'fused'])
+@pytest.mark.parametrize('timed', [False, True], ids=['plain', 'timed'])
+def test_each_combination_calls_its_entry_points_and_returns_the_models_beams(timed, fused):
+    """Batch 2, 6 frames, 5 classes, width 3; the second utterance ends inside the last chunk.  The input holds no float32 tie."""
+    lengths, first, last = [6, 5], [4, 4], [2, 1]
+    lp = model.log_probs((2, 6, 5), 1, 1.0)
+    W = model.fusion_table(5) if fused else None
+    lm = None if W is None else torch.from_numpy(W)
+    want = [model.beam_search(lp[i, :n].numpy(), 3, fusion=W) for i, n in enumerate(lengths)]
+    for i, n in enumerate(lengths):
+        assert model.same_beams(want[i], model.beam_search(lp[i, :n].numpy(), 3, fusion=W, dtype=np.float64)), i
+    assert not fused or any(not model.same_beams(w, model.beam_search(lp[i, :n].numpy(), 3)) for i, (w, n) in enumerate(zip(want, lengths)))
+    dev, entries = lp.to(DEV), []
+    hip.start_tape(entries)
+    try:
+        whole = ctc.beam_decode(dev, lengths, beam_width=3, return_timesteps=timed, lm=lm)
+        dec = ctc.BeamSearchStream(2, beam_width=3, device=DEV, timesteps=timed, lm=lm)
+        dec.push(dev[:, :4], first)
+        peeked = dec.peek(dev[:, 4:], last)
+        dec.push(dev[:, 4:], last)
+        finished = dec.finish()
+    finally:
+        hip.stop_tape()
+    assert dec.grown == 0 and [fn.__name__ for fn, _ in entries] == _entry_points(timed, fused)
+    for fn, args in entries:
+        assert len(args) == len(hip.SIGNATURES[fn.__name__][1]), fn.__name__
+        if '_lm' in fn.__name__:
+            assert args[-2] == int(timed) and type(args[-2]) is int, (fn.__name__, args[-2])
+    _assert_same(peeked, whole, 'peek')                             # streaming is the whole search, bit for bit
+    _assert_same(finished, whole, 'finish')
+    assert len(whole) == (4 if timed else 3)
+    beams, steps, lens = whole[0].cpu(), whole[2].cpu() if timed else None, whole[-1].cpu()
+    for i, rows in enumerate(want):
+        for r, (tok, _, ts) in enumerate(rows):
+            n = int(lens[i, r])
+            assert beams[i, r, :n].tolist() == tok and torch.all(beams[i, r, n:] == 0), (i, r)
+            assert not timed or (steps[i, r, :n].tolist() == ts and torch.all(steps[i, r, n:] == 0)), (i, r)
+        assert torch.all(lens[i, len(rows):] == 0)

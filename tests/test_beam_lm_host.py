@@ -1,21 +1,18 @@
-"""Bigram LM fusion of the beam search, the part that needs no GPU: the plain-Python model (beam_lm_model.py) is the unfused model
-without a table and with a zero table, its fused scores are log P_ctc + sum W by exhaustive enumeration, the seeds of the device
+"""Bigram LM fusion of the beam search, the part that needs no GPU: the plain-Python model (beam_timesteps_model.py) with a zero table is
+the model without one, its fused scores are log P_ctc + sum W by exhaustive enumeration, the seeds of the device
 comparison hold no float32 tie, ``ctc.bigram_lm`` / ``ctc.fusion_table`` compute what they say, and the three new entry points are declared,
 bound and refuse bad arguments on the host."""
 import inspect
-import pathlib
-import re
 
 import numpy as np
 import pytest
 import torch
 
-import beam_lm_model as lm_model
 import beam_timesteps_model as model
 from nb_asr_amd import ctc, hip, streaming
+from nbasr_header import declarations
 from oracle import decode_oracle as oracle
 
-HEADER = pathlib.Path(__file__).resolve().parent.parent / 'include' / 'nbasr.h'
 NAMES = ('nbasr_ctc_beam_search_lm', 'nbasr_ctc_beam_stream_lm_step', 'nbasr_ctc_beam_stream_lm_peek')
 FLT_MAX = float(np.finfo(np.float32).max)
 
@@ -26,9 +23,8 @@ FLT_MAX = float(np.finfo(np.float32).max)
 def test_model_without_a_table_and_with_a_zero_table_is_the_unfused_model(shape):
     classes = shape[2]
     for key, lp, width, top_n in model.utterances(shape):
-        want = model.beam_search(lp, width, cutoff_top_n=top_n)
-        assert lm_model.beam_search(lp, width, cutoff_top_n=top_n, fusion=None) == want, key
-        assert lm_model.beam_search(lp, width, cutoff_top_n=top_n, fusion=np.zeros((classes, classes), np.float32)) == want, key
+        want = model.beam_search(lp, width, cutoff_top_n=top_n)             # without a table: anchored on the oracle by test_beam_timesteps_host.py
+        assert model.beam_search(lp, width, cutoff_top_n=top_n, fusion=np.zeros((classes, classes), np.float32)) == want, key
 
 
 def test_fused_scores_are_the_exhaustive_ctc_scores_plus_the_bigram_sums():
@@ -41,7 +37,7 @@ def test_fused_scores_are_the_exhaustive_ctc_scores_plus_the_bigram_sums():
         rng = np.random.default_rng(seed)
         lp = torch.log_softmax(torch.from_numpy(1.5 * rng.normal(size=(frames, classes))), dim=1).to(torch.float32).numpy()
         W = rng.normal(size=(classes, classes)).astype(np.float32)
-        got = [(tok, score) for tok, score, _ in lm_model.beam_search(lp, 32, fusion=W) if score < 0.99 * FLT_MAX]
+        got = [(tok, score) for tok, score, _ in model.beam_search(lp, 32, fusion=W) if score < 0.99 * FLT_MAX]
         want = []
         for lab, log_p in oracle.ctc_labelling_log_probs(lp).items():
             prev, total = 0, float(log_p)
@@ -63,10 +59,10 @@ def test_fused_model_beams_do_not_hang_on_float32_ties():
     """A condition of the device comparison (test_beam_lm_gpu.py): at every utterance it uses, accumulating in float64 changes no beam."""
     changed = 0
     for shape in model.TIMED_SHAPES:
-        W = lm_model.fusion_table(shape[2])
+        W = model.fusion_table(shape[2])
         for key, lp, width, top_n in model.utterances(shape):
-            f32 = lm_model.beam_search(lp, width, cutoff_top_n=top_n, fusion=W)
-            assert model.same_beams(f32, lm_model.beam_search(lp, width, cutoff_top_n=top_n, fusion=W, dtype=np.float64)), key
+            f32 = model.beam_search(lp, width, cutoff_top_n=top_n, fusion=W)
+            assert model.same_beams(f32, model.beam_search(lp, width, cutoff_top_n=top_n, fusion=W, dtype=np.float64)), key
             changed += not model.same_beams(f32, model.beam_search(lp, width, cutoff_top_n=top_n))
     assert changed >= 10                                           # the table matters: a search that ignored it could not pass
 
@@ -143,24 +139,12 @@ def test_python_interface_takes_the_lm_last_and_by_keyword():
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
 
-def _declaration(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
-    assert m, name
-    return m.group(1), [a.strip() for a in m.group(2).split(',')]
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_symbols_are_declared_and_bound_with_the_header_signature(name):
-    ret, args = _declaration(name)
+    """That the binding's types are the header's is test_abi.py's check of every symbol."""
+    ret, args = declarations()[name]
     restype, argtypes = hip.SIGNATURES[name]
     assert ret == 'int' and restype is hip.ctypes.c_int
-    assert len(argtypes) == len(args), (name, args)
-    for decl, ct in zip(args, argtypes):
-        if '*' in decl or 'nbasr_stream_t' in decl:
-            assert ct is hip.ctypes.c_void_p, (name, decl)
-        else:
-            assert ct is hip.ctypes.c_int, (name, decl)
     assert any('fusion' in a for a in args) and args[-2] == 'int timed'
     assert getattr(hip.load_library(), name).argtypes == argtypes
     assert hip.load_library().nbasr_version() == 6

@@ -1,40 +1,21 @@
 """Streaming beam decode without a GPU: the C ABI of nbasr_ctc_beam_stream_* (bound with the header's signatures, arguments refused on
 the host), and the committed-prefix argument it rests on, checked on the CPU oracle independently of the kernel: the longest common
 token prefix of the live beams after frame t is a prefix of every beam after every later frame."""
-import pathlib
-import re
-
 import pytest
 import torch
 
 from nb_asr_amd import hip
+from nbasr_header import declarations
 from oracle import decode_oracle as oracle
 
-HEADER = pathlib.Path(__file__).resolve().parent.parent / 'include' / 'nbasr.h'
 NAMES = ('nbasr_ctc_beam_stream_state_bytes', 'nbasr_ctc_beam_stream_workspace_bytes', 'nbasr_ctc_beam_stream_init',
          'nbasr_ctc_beam_stream_step', 'nbasr_ctc_beam_stream_finish')
 
 
-def _declaration(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
-    assert m, name
-    return m.group(1), [a.strip() for a in m.group(2).split(',')]
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_symbols_are_bound_with_the_header_signature(name):
-    ret, args = _declaration(name)
-    restype, argtypes = hip.SIGNATURES[name]
-    assert len(argtypes) == len(args), (name, args)
-    assert (restype is hip.ctypes.c_size_t) == (ret == 'size_t')
-    for decl, ct in zip(args, argtypes):
-        if '*' in decl or 'nbasr_stream_t' in decl:
-            assert ct is hip.ctypes.c_void_p, (name, decl)
-        else:
-            assert ct is hip.ctypes.c_int, (name, decl)
-    lib = hip.load_library()
-    assert getattr(lib, name).argtypes == argtypes
+    """Declared, and loaded with the binding's types; that those are the header's is test_abi.py's check of every symbol."""
+    assert name in declarations() and getattr(hip.load_library(), name).argtypes == hip.SIGNATURES[name][1]
 
 
 def _err(lib):

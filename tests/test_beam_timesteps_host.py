@@ -2,17 +2,15 @@
 (beam_timesteps_model.py) is anchored on the decode oracle, the properties of its time steps are checked (the GPU tests compare the
 device against this model), and the new C entry points are bound with the header's signatures and refuse bad arguments on the host."""
 import inspect
-import pathlib
-import re
 
 import numpy as np
 import pytest
 
 import beam_timesteps_model as model
 from nb_asr_amd import ctc, hip
+from nbasr_header import declarations
 from oracle import decode_oracle as oracle
 
-HEADER = pathlib.Path(__file__).resolve().parent.parent / 'include' / 'nbasr.h'
 NAMES = ('nbasr_ctc_beam_timed_workspace_bytes', 'nbasr_ctc_beam_search_timed', 'nbasr_ctc_beam_stream_timed_state_bytes',
          'nbasr_ctc_beam_stream_timed_init', 'nbasr_ctc_beam_stream_timed_step', 'nbasr_ctc_beam_stream_timed_finish')
 
@@ -85,25 +83,10 @@ def test_model_width_one_on_peaked_input_gives_the_first_frame_of_every_argmax_r
 
 # ---- interface -------------------------------------------------------------------------------------------------------------------
 
-def _declaration(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
-    assert m, name
-    return m.group(1), [a.strip() for a in m.group(2).split(',')]
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_symbols_are_bound_with_the_header_signature(name):
-    ret, args = _declaration(name)
-    restype, argtypes = hip.SIGNATURES[name]
-    assert len(argtypes) == len(args), (name, args)
-    assert (restype is hip.ctypes.c_size_t) == (ret == 'size_t')
-    for decl, ct in zip(args, argtypes):
-        if '*' in decl or 'nbasr_stream_t' in decl:
-            assert ct is hip.ctypes.c_void_p, (name, decl)
-        else:
-            assert ct is hip.ctypes.c_int, (name, decl)
-    assert getattr(hip.load_library(), name).argtypes == argtypes
+    """Declared, and loaded with the binding's types; that those are the header's is test_abi.py's check of every symbol."""
+    assert name in declarations() and getattr(hip.load_library(), name).argtypes == hip.SIGNATURES[name][1]
 
 
 def _err(lib):

@@ -2,15 +2,13 @@
 buffers, the three nbasr_ctc_beam_stream_*peek* entry points are declared, bound and exported and refuse bad arguments before any HIP
 call, and the front-end's peek count is the flush's."""
 import copy
-import pathlib
-import re
 
 import pytest
 
 import cases
 from nb_asr_amd import frontend, hip, streaming
+from nbasr_header import declarations
 
-HEADER = pathlib.Path(__file__).resolve().parent.parent / 'include' / 'nbasr.h'
 NAMES = ('nbasr_ctc_beam_stream_peek_workspace_bytes', 'nbasr_ctc_beam_stream_peek', 'nbasr_ctc_beam_stream_timed_peek')
 FIELDS = ('a', 'b', 'c', 'd', 'hist_off', 'n_hist', 'n_new', 'compute')
 STATE = ('have', 'done', 'start', 'next_start', 'finished')
@@ -88,23 +86,12 @@ def test_max_provisional_frames_is_the_brute_force_maximum(arch, use_rnn, most):
     assert got == with_end_frames == without == most
 
 
-def _declaration(name):
-    code = re.sub(r'/\*.*?\*/', '', HEADER.read_text(), flags=re.S)
-    m = re.search(r'(\w+)\s+' + name + r'\s*\(([^)]*)\)\s*;', code)
-    assert m, name
-    return m.group(1), [a.strip() for a in m.group(2).split(',')]
-
-
 @pytest.mark.parametrize('name', NAMES)
 def test_peek_symbols_are_declared_bound_and_exported(name):
-    ret, args = _declaration(name)
-    restype, argtypes = hip.SIGNATURES[name]
-    assert len(argtypes) == len(args), (name, args)
-    assert (restype is hip.ctypes.c_size_t) == (ret == 'size_t')
-    for decl, ct in zip(args, argtypes):
-        assert ct is (hip.ctypes.c_void_p if '*' in decl or 'nbasr_stream_t' in decl else hip.ctypes.c_int), (name, decl)
+    """That the binding's types are the header's is test_abi.py's check of every symbol."""
+    ret, args = declarations()[name]
     lib = hip.load_library()
-    assert getattr(lib, name).argtypes == argtypes
+    assert getattr(lib, name).argtypes == hip.SIGNATURES[name][1]
     assert lib.nbasr_version() == 6
     if ret == 'int':
         state = args[2]
