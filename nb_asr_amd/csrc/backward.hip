@@ -693,7 +693,8 @@ extern "C" int nbasr_lstm_backward_step(const float* dh_out, const float* w_hh_t
         // loop); replayed as one cached graph where the same buffers recur (common.h)
         struct Ctx { hipStream_t s; const float* dh; const float* w; float* dc; const float* acts; const float* cells; float* dpre; int hidden, frames, batch, ldb; };
         Ctx ctx{as_stream(stream), dh_out, w_hh_t, dc, acts, cells, dpre, hidden, frames, batch, ldb};
-        const ChainKey key{{dh_out, w_hh_t, dc, acts, dpre}, {hidden, frames, batch, ldb, -32}};
+        // (every pointer the lambda reads is named in the key: a replayed graph bakes them all in, and `cells` is allocated afresh per call)
+        const ChainKey key{{dh_out, w_hh_t, dc, acts, cells, dpre}, {hidden, frames, batch, ldb, -32}};
         return replay_chain(ctx.s, key, "nbasr_lstm_backward_step", [](void* p) {
             const Ctx& c = *static_cast<const Ctx*>(p);
             for (int u = c.frames - 1; u >= 0; --u)
