@@ -709,6 +709,40 @@ int nbasr_frontend_stream_step(const float* tail_in, int tail_len, long long tai
                                const float* inv_scale, float* feats, int ld_feats, int col0, int first_frame, int n_frames,
                                long long total_len, int final, int batch, int win, int hop, int bins, int n_mels, nbasr_stream_t stream);
 
+/* ---- resampler ahead of the front-end (nb_asr_amd/frontend.py Resampler / ResamplerStream) ----------------------------
+ * Band-limited sinc interpolation with a Hann window, in absolute sample indices.  With g = gcd(orig_freq, new_freq),
+ * o = orig_freq / g, n = new_freq / g, base = 0.99 min(o, n), and x zero outside [0, length):
+ *     y[j] = sum_m x[m] (base / o) sinc(pi t) cos^2(pi t / 12),   t = (m / o - j / n) base,   sinc(0) = 1,
+ * over the integers m of the SUPPORT |m n - j o| <= reach, reach the largest integer with reach * min(o, n) * 99 < 600 o n (that is
+ * |t| < 6, decided in integers); j runs over [0, ceil(n length / o)).  Refused (NBASR_EINVAL): rates <= 0, o > 1024, n > 1024, a
+ * support of more than 48 taps.
+ *   table: n rows of pitch (taps | 1) floats, taps = the largest support over the phases p = j mod n; element i of row p is the
+ *   coefficient of m = (j / n) o + lo(p) + i, lo(p) = ceil((p o - reach) / n), and zero beyond row p's support.  The CALLER computes
+ *   it (float64, rounded once to float32).
+ *   Every output is one fp32 fma chain in ascending m over the samples of its support inside [0, length): the same bits whatever the
+ *   step sizes, col0 or the batch.
+ * nbasr_resample_stream_step: one push of a stream, as ONE launch; the contract of nbasr_frontend_stream_step.  The CALLER decides
+ * which outputs a step computes (frontend.py: resample_final / resample_total / resample_retain_from); the step refuses outputs whose
+ * samples the stream does not hold.
+ *   state: two tails of round_up4(tail_capacity) floats per utterance (nbasr_resample_state_bytes), used in turn.
+ *   tail_in(batch, round_up4(tail_capacity)): the retained samples [tail_first, tail_first + tail_len) (NULL when tail_len == 0);
+ *   wave(batch, n_new) with row pitch ld_wave: this step's samples (NULL when n_new == 0);
+ *   total_len = tail_first + tail_len + n_new: samples of the stream so far (the utterance's length when final != 0).
+ *   out(batch, ld_out): outputs first_out .. first_out + n_out - 1 are written to columns col0 ..; no other column is touched.
+ *   final == 0: every output's whole support must lie below total_len; final != 0: outputs up to ceil(n total_len / o) - 1.
+ *   tail_out, != tail_in, 16-byte aligned: receives samples tail_first + tail_out_first_rel .. total_len - 1 (at most
+ *   round_up4(tail_capacity); the rest of each row is zeroed).  NULL, or final != 0: nothing is retained.
+ * nbasr_resample: whole utterances, wave(batch, samples) with row pitch ld_wave -> out(batch, n_out), n_out = ceil(n samples / o).
+ *   lengths(batch) int32 device memory or NULL: utterance b has lengths[b] <= samples samples (the caller's to keep); nothing at or
+ *   beyond them is read, and its outputs at or beyond ceil(n lengths[b] / o) are written as zero. */
+size_t nbasr_resample_state_bytes(int batch, int tail_capacity);
+int nbasr_resample_stream_step(const float* tail_in, int tail_len, long long tail_first, const float* wave, int n_new, int ld_wave,
+                               float* tail_out, int tail_out_first_rel, int tail_capacity, const float* table, int orig_freq, int new_freq,
+                               float* out, int ld_out, int col0, long long first_out, int n_out, long long total_len, int final, int batch,
+                               nbasr_stream_t stream);
+int nbasr_resample(const float* wave, int ld_wave, int samples, const int* lengths, const float* table, int orig_freq, int new_freq,
+                   float* out, int ld_out, int n_out, int batch, nbasr_stream_t stream);
+
 /* ---- optimisation step (reference training/torch/trainer.py:221-225 Trainer.step and :84 Trainer.train) ----------
  * The rest of the reference's training step after loss.backward(), over a whole parameter set in three launches (reduce, finalise,
  * apply), stream-ordered, without host synchronisation, read-back or floating-point atomics:

@@ -81,6 +81,99 @@ def retain_from(frames_emitted, hop=160, win=400):
     return max(0, hop * frames_emitted - win // 2 - 1)
 
 
+# ---- the resampler's geometry (pure python, integers only; DESIGN.md 9 "Resampler") ---------------------------------------------------
+# o = orig / gcd, n = new / gcd.  Output j sums the samples m with |m n - j o| <= reach: the integer form of |t| < 6 for
+# t = (m / o - j / n) 0.99 min(o, n).  Everything below follows from that one rule, so host, model and kernel agree on the support.
+RESAMPLE_MAX_RATIO = 1024          # the kernel's limits (include/nbasr.h): reduced rates, and taps of the largest support
+RESAMPLE_MAX_TAPS = 48
+
+
+def resample_ratio(orig_freq, new_freq):
+    """(o, n): the two rates with their common factor taken out."""
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f'sample rates must be positive (got {orig_freq} -> {new_freq})')
+    g = math.gcd(orig_freq, new_freq)
+    return orig_freq // g, new_freq // g
+
+
+def resample_reach(o, n):
+    """The largest |m n - j o| inside the support: the largest integer d with d min(o, n) 99 < 600 o n."""
+    return (600 * o * n - 1) // (99 * min(o, n))
+
+
+def resample_support(j, o, n):
+    """(first, last) sample of output j's support (before clipping to the utterance)."""
+    d = resample_reach(o, n)
+    return -((d - j * o) // n), (j * o + d) // n
+
+
+def resample_taps(o, n):
+    """Taps of the largest support over the n phases (the support of output j + n is that of j moved by o samples)."""
+    return max(hi - lo + 1 for lo, hi in (resample_support(p, o, n) for p in range(n)))
+
+
+def resample_total(samples, o, n):
+    """Outputs of an utterance of ``samples`` samples: ceil(n samples / o)."""
+    return -(-n * samples // o)
+
+
+def resample_final(samples, o, n):
+    """Outputs that can no longer change after ``samples`` samples, while the end is unknown: those whose last supported sample has
+    arrived, (j o + reach) // n < samples.  Per output, not per block of o samples."""
+    return max(0, (samples * n - resample_reach(o, n) - 1) // o + 1)
+
+
+def resample_peek(samples, o, n):
+    """Outputs a peek returns after ``samples`` samples: those a flush would emit now."""
+    return resample_total(samples, o, n) - resample_final(samples, o, n)
+
+
+def resample_retain_from(outputs_emitted, o, n):
+    """First sample a stream must keep once ``outputs_emitted`` outputs are out: the first of the next output's support."""
+    return max(0, resample_support(outputs_emitted, o, n)[0])
+
+
+def _resample_states(o, n):
+    """Sample counts that show every state of a stream: samples -> samples + o moves every count by n outputs and every support by o
+    samples, so one period is all there is once the next output's support no longer starts before sample 0 (the support is
+    2 reach / n samples wide)."""
+    return range(0, 2 * resample_reach(o, n) // n + 2 * o + 2)
+
+
+def resample_tail_capacity(o, n):
+    """The most samples a stream retains: the largest ``samples - resample_retain_from(resample_final(samples))``."""
+    return max(s - resample_retain_from(resample_final(s, o, n), o, n) for s in _resample_states(o, n))
+
+
+def resample_max_pending(o, n):
+    """The most outputs a flush or a peek returns (the outputs still pending at an arbitrary cut)."""
+    return max(resample_peek(s, o, n) for s in _resample_states(o, n))
+
+
+def resample_lookahead(o, n):
+    """Samples an output waits for beyond its own instant j o / n: ceil(reach / n)."""
+    return -(-resample_reach(o, n) // n)
+
+
+def resample_table(o, n):
+    """(n, taps | 1) float64 coefficients: row p, element i belongs to sample lo(p) + i of output p (and to lo(p) + i + k o of output
+    p + k n); zero beyond the row's support.  The odd pitch is the kernel's (LDS banks)."""
+    taps, base = resample_taps(o, n), 0.99 * min(o, n)
+    table = np.zeros((n, taps | 1))
+    for p in range(n):
+        lo, hi = resample_support(p, o, n)
+        t = (np.arange(lo, hi + 1) * n - p * o).astype(np.float64) * (base / (o * n))      # (m / o - p / n) base, the difference exact
+        table[p, :hi - lo + 1] = (base / o) * np.sinc(t) * np.cos(math.pi * t / 12.0) ** 2
+    return table
+
+
+def end_frames_bound(pending=0, hop=160, win=400):
+    """The most frames the front-end emits for the end of an utterance when up to ``pending`` more samples arrive with it (a
+    resampler's flush): the largest ``frames_total(s + pending) - frames_final(s)``.  2 without a resampler."""
+    return (hop - 1 + win // 2 + pending) // hop
+
+
 class LogMelFrontend:
     """``frontend(wave, lengths=None) -> (B, n_mels, T)`` float32 on ``wave``'s HIP device, ``T = L // hop + 1``.
 
@@ -227,15 +320,22 @@ class FrontendStream:
         self._flushed = True
         return view
 
-    def peek(self, out=None):
+    def peek(self, out=None, extra=None):
         """The frames ``flush()`` would return now (``frames_peek``: 1 or 2, none in the utterance's first ``win // 2`` samples), with the
-        stream left as it was: the launch that ends an utterance retains nothing, and nothing advances."""
+        stream left as it was: the launch that ends an utterance retains nothing, and nothing advances.  ``extra``: (batch, n)
+        uncommitted samples, taken as if pushed and then ended -- the frames ``push(extra)`` and ``flush()`` would return together."""
         if self._flushed:
             raise ValueError('peek after flush: call reset() to start the next utterance')
-        m = frames_peek(self.samples_in, self.hop, self.win)          # (== frames_total - frames_out: a push emits every final frame)
+        if extra is None or extra.shape[-1] == 0:
+            extra = None
+            m = frames_peek(self.samples_in, self.hop, self.win)      # (== frames_total - frames_out: a push emits every final frame)
+        else:
+            extra = self._admit(extra)
+            total = self.samples_in + extra.shape[1]
+            m = 0 if total <= self.win // 2 else frames_total(total, self.hop, self.win) - self.frames_out
         feats, col0, view = self._destination(out, m)
         if m:
-            self._step(None, m, feats, col0, self.frames_out, False, True)
+            self._step(extra, m, feats, col0, self.frames_out, False, True)
         return view
 
     # ---- one launch ------------------------------------------------------------------------------------------------------------
@@ -287,3 +387,153 @@ class FrontendStream:
                 self._turn ^= 1
                 self._tail_first = new_first
                 self._tail_len = self.samples_in - new_first
+
+
+class Resampler:
+    """``resampler(wave, lengths=None) -> (resampled, out_lengths)``: (B, L) float32 samples at ``orig_freq`` on a HIP device to
+    (B, ceil(n L / o)) samples at ``new_freq``, by band-limited sinc interpolation with a Hann window (the formula of DESIGN.md 9:
+    torchaudio.functional.resample's defaults, written in absolute sample indices).  With ``lengths`` every utterance is resampled as
+    if alone: nothing at or beyond its length is read and its outputs beyond ``out_len(length)`` are zero.  ``out_lengths``: a list.
+
+    All arithmetic runs in libnbasr_hip.so (resample.hip); there is no CPU path.  Refused: rates that are not positive, and pairs whose
+    reduced rates or support exceed the kernel's limits (``RESAMPLE_MAX_RATIO``, ``RESAMPLE_MAX_TAPS``)."""
+
+    def __init__(self, orig_freq, new_freq=16000, device='cuda:0'):
+        self.o, self.n = resample_ratio(orig_freq, new_freq)
+        self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        if max(self.o, self.n) > RESAMPLE_MAX_RATIO:
+            raise ValueError(f'{orig_freq} -> {new_freq} reduces to {self.o} : {self.n}: the limit is {RESAMPLE_MAX_RATIO} on either side')
+        self.taps = resample_taps(self.o, self.n)
+        if self.taps > RESAMPLE_MAX_TAPS:
+            raise ValueError(f'{orig_freq} -> {new_freq} has a support of {self.taps} taps: the limit is {RESAMPLE_MAX_TAPS}')
+        self.device = torch.device(device)
+        self.tail_capacity = resample_tail_capacity(self.o, self.n)
+        self.max_pending = resample_max_pending(self.o, self.n)
+        self.lookahead_samples = resample_lookahead(self.o, self.n)
+        self._table = None
+
+    def table(self):
+        """The (n, taps | 1) coefficient table on the device: float64 on the host, rounded once to float32.  Made by the first use."""
+        if self._table is None:
+            self._table = torch.from_numpy(resample_table(self.o, self.n).astype(np.float32)).to(self.device).contiguous()
+        return self._table
+
+    def out_len(self, samples):
+        return resample_total(int(samples), self.o, self.n)
+
+    def stream(self, batch):
+        """A ``ResamplerStream``: this resampler push by push for a lockstep batch of ``batch`` waveform streams."""
+        return ResamplerStream(self, batch)
+
+    def __call__(self, wave, lengths=None):
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.dtype != torch.float32 or not wave.is_cuda:
+            raise hip.HipError('wave must be a (batch, samples) float32 tensor on a HIP device; this package has no CPU path')
+        b, samples = wave.shape
+        if samples and (wave.stride(1) != 1 or (b > 1 and wave.stride(0) < samples)):
+            wave = wave.contiguous()
+        out_lengths = [self.out_len(samples)] * b
+        if lengths is not None:
+            host = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+            if len(host) != b or min(host, default=0) < 0 or max(host, default=0) > samples:
+                raise ValueError(f'lengths must be {b} values in [0, {samples}]')
+            out_lengths = [self.out_len(v) for v in host]
+            lengths = torch.tensor(host, dtype=torch.int32).to(wave.device)
+        out = torch.empty(b, self.out_len(samples), device=wave.device)
+        hip.resample(wave, lengths, self.table(), self.orig_freq, self.new_freq, out)
+        return out, out_lengths
+
+
+class ResamplerStream:
+    """``Resampler`` push by push (``Resampler.stream``): one HIP launch per push, state carried in two sample tails.
+
+        rs = resampler.stream(batch=B)
+        for chunk in waveform_chunks:              # (B, n) float32 on the device, any n >= 0
+            y = rs.push(chunk)                     # (B, m): the outputs that are final now (resample_final)
+        last = rs.flush()                          # (B, m): the outputs that needed the utterance's end
+        # rs.peek() at any point before: the outputs flush() would return then, the stream left as it was
+        # torch.cat([*pushes, last], 1) is resampler(whole waveform)[0]; the bits do not depend on the chunking
+
+    ``FrontendStream``'s contract: the batch is lockstep, ``flush`` twice or ``push`` after ``flush`` raises.  ``state_bytes``: the two
+    tails of ``resampler.tail_capacity`` samples per lane (the table belongs to the resampler)."""
+
+    def __init__(self, resampler, batch):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        self.resampler, self.batch, self.device = resampler, batch, resampler.device
+        self.o, self.n = resampler.o, resampler.n
+        self.lookahead_samples = resampler.lookahead_samples
+        self._table = resampler.table()
+        self._tails = torch.zeros(2, batch, hip.round_up4(resampler.tail_capacity), device=self.device)
+        self.state_bytes = self._tails.numel() * self._tails.element_size()
+        assert self.state_bytes == hip.resample_state_bytes(batch, resampler.tail_capacity)
+        self.reset()
+
+    def reset(self):
+        """Start the next batch of utterances; the tails are re-used."""
+        self.samples_in = 0
+        self.samples_out = 0
+        self._tail_first = 0
+        self._tail_len = 0
+        self._turn = 0
+        self._flushed = False
+
+    @property
+    def pending(self):
+        """Outputs a flush or a peek would return now."""
+        return resample_total(self.samples_in, self.o, self.n) - self.samples_out
+
+    def push(self, wave_chunk):
+        """Feed (batch, n) samples; returns the (batch, m) outputs that became final, m = resample_final(samples_in) - samples_out."""
+        wave = self._admit(wave_chunk)
+        m = resample_final(self.samples_in + wave.shape[1], self.o, self.n) - self.samples_out
+        return self._step(wave, m, True, False)
+
+    def flush(self):
+        """End the utterance: its last outputs, with zeros beyond its end."""
+        if self._flushed:
+            raise ValueError('flush called twice: call reset() to start the next utterance')
+        out = self._step(None, resample_total(self.samples_in, self.o, self.n) - self.samples_out, True, True)
+        self._flushed = True
+        return out
+
+    def peek(self):
+        """The outputs ``flush()`` would return now (``resample_peek``), with the stream left as it was."""
+        if self._flushed:
+            raise ValueError('peek after flush: call reset() to start the next utterance')
+        return self._step(None, resample_total(self.samples_in, self.o, self.n) - self.samples_out, False, True)
+
+    def _admit(self, wave):
+        if self._flushed:
+            raise ValueError('push after flush: call reset() to start the next utterance')
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.batch:
+            raise ValueError(f'expected a ({self.batch}, samples) chunk, got {tuple(getattr(wave, "shape", ()))}')
+        if wave.dtype != torch.float32 or wave.device != self.device:
+            raise ValueError(f'the chunk must be float32 on {self.device} (got {wave.dtype} on {wave.device})')
+        wave = wave.detach()
+        if wave.shape[1] and (wave.stride(1) != 1 or (self.batch > 1 and wave.stride(0) < wave.shape[1])):
+            wave = wave.contiguous()
+        return wave
+
+    def _step(self, wave, m, commit, final):
+        """Outputs samples_out .. samples_out + m - 1 from the tail and ``wave``; ``commit``: retain and advance."""
+        r = self.resampler
+        n = 0 if wave is None else wave.shape[1]
+        out = torch.empty(self.batch, m, device=self.device)
+        tail_in, tail_out, rel = self._tails[self._turn], None, 0
+        new_first = self._tail_first
+        if commit and not final and n:                       # (an empty push leaves the tail where it is: nothing to copy)
+            new_first = resample_retain_from(self.samples_out + m, self.o, self.n)
+            rel = new_first - self._tail_first
+            tail_out = self._tails[self._turn ^ 1]
+        if m or tail_out is not None:
+            hip.resample_stream_step(tail_in, self._tail_len, self._tail_first, wave if n else None, tail_out, rel, r.tail_capacity,
+                                     self._table, r.orig_freq, r.new_freq, out, 0, self.samples_out, m, final)
+        if commit:
+            self.samples_in += n
+            self.samples_out += m
+            if tail_out is not None:
+                self._turn ^= 1
+                self._tail_first = new_first
+                self._tail_len = self.samples_in - new_first
+        return out

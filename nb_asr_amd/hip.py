@@ -133,6 +133,12 @@ SIGNATURES = {
     'nbasr_frontend_stream_state_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_frontend_stream_step': (_c_int, [_c_float_p, _c_int, ctypes.c_longlong, _c_float_p, _c_int, _c_int, _c_float_p, _c_int] + [_c_float_p] * 5
                                    + [_c_int] * 4 + [ctypes.c_longlong] + [_c_int] * 6 + [_c_stream]),
+    # resampler
+    'nbasr_resample_state_bytes': (ctypes.c_size_t, [_c_int] * 2),
+    'nbasr_resample_stream_step': (_c_int, [_c_float_p, _c_int, ctypes.c_longlong, _c_float_p, _c_int, _c_int, _c_float_p, _c_int, _c_int, _c_float_p,
+                                            _c_int, _c_int, _c_float_p, _c_int, _c_int, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_int, _c_int,
+                                            _c_stream]),
+    'nbasr_resample': (_c_int, [_c_float_p, _c_int, _c_int, ctypes.c_void_p, _c_float_p, _c_int, _c_int, _c_float_p] + [_c_int] * 3 + [_c_stream]),
     # optimisation step
     'nbasr_optim_table_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_optim_workspace_bytes': (ctypes.c_size_t, [_c_int] * 2),
@@ -907,6 +913,60 @@ def frontend_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out
         _dev(inv_scale, 'inv_scale'), _dev(feats, 'feats') if n_frames else None, ld_feats, int(col0), int(first_frame), int(n_frames),
         int(tail_first) + int(tail_len) + n_new, int(bool(final)), b, win, hop, bins, n_mels, _stream(tail_in)), 'nbasr_frontend_stream_step')
     return feats
+
+
+def resample_state_bytes(batch, tail_capacity):
+    """Bytes of the two sample tails of a resampler stream (nbasr.h: nbasr_resample_state_bytes); 0 for bad sizes."""
+    return int(load_library().nbasr_resample_state_bytes(batch, tail_capacity))
+
+
+def _wave_rows(wave, b, device, who):
+    """(samples, row pitch) of a (b, samples) float32 chunk whose rows are contiguous and do not overlap."""
+    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != b or wave.device != device:
+        raise HipError(f'{who}: wave must be a ({b}, samples) tensor on {device}')
+    n = wave.shape[1]
+    if n and wave.dtype != torch.float32:
+        raise HipError(f'{who}: wave must be float32 (got {wave.dtype})')
+    if n and (wave.stride(1) != 1 or (b > 1 and wave.stride(0) < n)):
+        raise HipError(f'{who}: the samples of an utterance must be contiguous, the utterances must not overlap')
+    return n, (max(wave.stride(0), n) if n else 0)
+
+
+def resample_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out_first_rel, tail_capacity, table, orig_freq, new_freq, out,
+                         col0, first_out, n_out, final):
+    """One step of a resampler stream (nbasr.h: nbasr_resample_stream_step).  ``tail_in`` / ``tail_out``: (B, round_up4(tail_capacity))
+    float32 tails (``tail_out`` None: retain nothing); ``wave`` (B, n) float32 or None; ``out`` (B, ld) receives outputs ``first_out`` ..
+    at columns ``col0`` .. (None when ``n_out`` is 0).  Returns ``out``."""
+    b, tail_ld = tail_in.shape
+    if tail_ld != round_up4(tail_capacity) or (tail_out is not None and tuple(tail_out.shape) != (b, tail_ld)):
+        raise HipError(f'resample_stream_step: the tails must be ({b}, {round_up4(tail_capacity)}) tensors')
+    n_new, ld_wave = (0, 0) if wave is None else _wave_rows(wave, b, tail_in.device, 'resample_stream_step')
+    ld_out = 0
+    if n_out:
+        if out.dim() != 2 or out.shape[0] != b or out.device != tail_in.device:
+            raise HipError(f'resample_stream_step: out must be a ({b}, ld) tensor on {tail_in.device}')
+        ld_out = out.shape[1]
+    _check(load_library().nbasr_resample_stream_step(
+        _dev(tail_in, 'tail_in'), int(tail_len), int(tail_first), wave.data_ptr() if n_new else None, n_new, ld_wave,
+        _opt(tail_out, 'tail_out'), int(tail_out_first_rel), int(tail_capacity), _dev(table, 'table'), int(orig_freq), int(new_freq),
+        _dev(out, 'out') if n_out else None, ld_out, int(col0), int(first_out), int(n_out), int(tail_first) + int(tail_len) + n_new,
+        int(bool(final)), b, _stream(tail_in)), 'nbasr_resample_stream_step')
+    return out
+
+
+def resample(wave, lengths, table, orig_freq, new_freq, out):
+    """Whole utterances (nbasr.h: nbasr_resample): ``wave`` (B, samples) float32 -> ``out`` (B, ceil(n samples / o)); ``lengths`` an int32
+    device tensor of B sample counts or None.  Returns ``out``."""
+    b = wave.shape[0] if isinstance(wave, torch.Tensor) and wave.dim() == 2 else 0
+    samples, ld_wave = _wave_rows(wave, b, table.device, 'resample')
+    if out.dim() != 2 or out.shape[0] != b or out.device != wave.device:
+        raise HipError(f'resample: out must be a ({b}, outputs) tensor on {wave.device}')
+    if lengths is not None and (lengths.dtype != torch.int32 or lengths.device != wave.device or lengths.numel() != b or not lengths.is_contiguous()):
+        raise HipError(f'resample: lengths must be {b} contiguous int32 values on {wave.device}')
+    _check(load_library().nbasr_resample(
+        wave.data_ptr() if samples else None, ld_wave, samples, None if lengths is None else lengths.data_ptr(), _dev(table, 'table'),
+        int(orig_freq), int(new_freq), _dev(out, 'out') if out.numel() else None, out.shape[1], out.shape[1], b, _stream(table)), 'nbasr_resample')
+    return out
 
 
 def linear_head(h, weight, bias, logits):

@@ -277,7 +277,9 @@ class ASRModel(nn.Module):
         that have become final, ``sess.flush()`` the rest; together they are ``model(x)`` of the concatenated chunks (to fp32 round-off).
         ``push(chunk, decode='beam')`` also runs ``ctc.beam_decode``'s search with ``beam_width`` and ``cutoff_top_n`` as the frames arrive.
         ``frontend``: a ``frontend.LogMelFrontend`` on the model's device; the session then also takes the waveform,
-        ``sess.push_audio(wave_chunk)`` with (batch, n) float32 samples, and ``flush`` ends the front-end's stream first."""
+        ``sess.push_audio(wave_chunk)`` with (batch, n) float32 samples, and ``flush`` ends the front-end's stream first.  Samples at
+        another rate than the front-end's, like an LM for the session's beam searches, are arguments of the constructor:
+        ``streaming.StreamingSession(model, batch, ..., frontend=fe, input_rate=48000)``."""
         from .streaming import StreamingSession
         return StreamingSession(self, batch, max_chunk, beam_width, cutoff_top_n, frontend)
 

@@ -16,6 +16,7 @@
 
     sess = model.eval().stream(batch=B, frontend=fe)                   # fe: frontend.LogMelFrontend on the model's device
     logits = sess.push_audio(wave_chunk)         # (B, n) float32 samples: the front-end's stream (frontend.FrontendStream), then push
+    sess = StreamingSession(model.eval(), B, frontend=fe, input_rate=48000)      # push_audio takes samples at 48 kHz (frontend.Resampler)
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -32,7 +33,7 @@ import torch
 
 from . import hip
 from .ctc import BeamSearchStream, empty_beam_result, fusion_table
-from .frontend import LogMelFrontend
+from .frontend import LogMelFrontend, Resampler, end_frames_bound, frames_final
 
 FEATURES = 80
 FILTERS = (600, 800, 1000, 1200)
@@ -209,14 +210,17 @@ class StreamPlanner:
             new = new // sp.stride + sp.right // sp.stride + 3
         return caps
 
-    def max_provisional_frames(self):
+    def max_provisional_frames(self, end_frames=2):
         """The most output frames a peek can return (host only; a session sizes its beam peek workspace with it, once): the largest
-        ``output_frames(f + 2) - done[-1]`` after f single-frame steps, the 2 being a front-end's end frames.  The emitted count is a
-        function of the frames received alone and repeats with period 4 once frames are emitted, so the first lookahead + 32 show it."""
+        ``output_frames(f + end_frames) - done[-1]`` after f single-frame steps (f = 0 included: a peek before any frame is in),
+        ``end_frames`` being a front-end's end frames (``frontend.end_frames_bound``: 2, more behind a resampler with many pending
+        outputs).  The emitted count is a function of the frames received alone and repeats with period 4 once frames are emitted, so
+        the first lookahead + 32 show it."""
         probe, most = StreamPlanner(self.specs), 1
-        for f in range(1, self.lookahead + 33):
-            probe.step(1)
-            total = f + 2
+        for f in range(0, self.lookahead + 33):
+            if f:
+                probe.step(1)
+            total = f + end_frames
             for sp in self.specs:
                 total = out_length(total, sp.stride)
             most = max(most, total - probe.done[-1])
@@ -279,11 +283,16 @@ class StreamingSession:
     the caller's current stream.  Memory depends on (batch, max_chunk, architecture) only and is allocated here.  ``lm``, ``alpha``,
     ``beta``: the bigram fusion of ``ctc.beam_decode`` for the session's beam searches (``decode='beam'`` and ``'beam-timed'``);
     ``ASRModel.stream`` keeps its parameter list, so a session with an LM is made with this constructor, which takes ``stream``'s
-    arguments after the model."""
+    arguments after the model.  ``input_rate``: the sample rate of what ``push_audio`` is given, when it is not the front-end's
+    (``frontend.Resampler``: a HIP resampler ahead of the front-end's stream; DESIGN.md 9 "Resampler").  ``None`` or the front-end's own
+    rate is the session without the argument, launch for launch.  ``lookahead_samples`` is then in samples at the input rate."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, lm=None, alpha=1.0, beta=0.0):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, lm=None, alpha=1.0,
+                 beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
+        resampler = self.resampler_for(frontend, input_rate, getattr(frontend, 'device', None))
+        self.end_frames = self.check_max_chunk(max_chunk, frontend, resampler)
         p0 = model.model[0].conv.weight
         if p0.dtype != torch.float32:
             raise ValueError(f'streaming runs float32 models only (this one is {p0.dtype})')
@@ -345,7 +354,7 @@ class StreamingSession:
                   'head': (cls._head_of_lstm, False) if model.use_rnn else (cls._head, True)}
         self._bodies = [bodies[sp.kind] for sp in self.specs]
         # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
-        self._frontend, self.lookahead_samples = None, None
+        self._frontend, self._resampler, self.lookahead_samples = None, None, None
         if frontend is not None:
             if frontend.device != dev:
                 raise ValueError(f'the front-end lives on {frontend.device}, the model on {dev}')
@@ -355,8 +364,39 @@ class StreamingSession:
             ld = hip.round_up4(max_chunk)
             self._staging = buf(B * FEATURES * ld).view(B, FEATURES, ld)
             self.lookahead_samples = self._frontend.lookahead_samples + frontend.hop_length * self.lookahead_frames
+            if resampler is not None:            # in samples at the input rate: the front-end's share converted, plus the resampler's own
+                self._resampler = resampler.stream(B)
+                self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
         self._pack()
         self.reset()
+
+    @staticmethod
+    def resampler_for(frontend, input_rate, device):
+        """The ``Resampler`` of a session fed samples at ``input_rate``; None when they arrive at the front-end's own rate (``None`` or
+        that rate: exactly the session without the argument)."""
+        if input_rate is None:
+            return None
+        if frontend is None:
+            raise ValueError('input_rate needs a front-end: model.stream(..., frontend=LogMelFrontend(...), input_rate=...)')
+        if int(input_rate) == frontend.sample_rate:
+            return None
+        return Resampler(input_rate, frontend.sample_rate, device=device)
+
+    @staticmethod
+    def check_max_chunk(max_chunk, frontend, resampler):
+        """The most frames the front-end emits for an utterance's end (``frontend.end_frames_bound``; 2 without a resampler).  Behind a
+        resampler a peek takes them in two steps ahead of the final one, as flush does -- the frames the resampler's pending outputs
+        complete, then the front-end's end frames -- and has two places to build their windows, so each must be ONE step: a
+        ``max_chunk`` below the bound is refused."""
+        if frontend is None:
+            return 2
+        if resampler is None:
+            return end_frames_bound(0, frontend.hop_length, frontend.n_fft)
+        bound = end_frames_bound(resampler.max_pending, frontend.hop_length, frontend.n_fft)
+        if int(max_chunk) < bound:
+            raise ValueError(f'max_chunk={max_chunk} is below the {bound} frames that end an utterance resampled from {resampler.orig_freq} Hz '
+                             f'({resampler.max_pending} outputs can be pending): a peek has no place for more steps')
+        return bound
 
     # ---- weights ---------------------------------------------------------------------------------------------------------------
     def _pack(self):
@@ -405,7 +445,8 @@ class StreamingSession:
         beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
-                + (self._frontend.state_bytes if self._frontend is not None else 0))
+                + (self._frontend.state_bytes if self._frontend is not None else 0)
+                + (self._resampler.state_bytes if self._resampler is not None else 0))
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -418,6 +459,8 @@ class StreamingSession:
         self._fed = None                         # 'features' (push) or 'audio' (push_audio): one utterance takes one of them
         if self._frontend is not None:
             self._frontend.reset()
+        if self._resampler is not None:
+            self._resampler.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
@@ -457,6 +500,8 @@ class StreamingSession:
                              f'{getattr(wave_chunk, "dtype", None)} on {getattr(wave_chunk, "device", None)}')
         self._begin(decode)
         self._fed = 'audio'
+        if self._resampler is not None:          # samples at the input rate: the outputs that are final now go on as the push
+            wave_chunk = self._resampler.push(wave_chunk)
         outs = [self._commit(self._staging if k else None, 0, k) for k in self._frontend.push_tiled(wave_chunk, self._staging, self.max_chunk)]
         return self._result(outs, decode)
 
@@ -469,8 +514,15 @@ class StreamingSession:
         self._begin(decode)
         outs = []
         if self._fed == 'audio':                 # the front-end's last 1 or 2 frames first, as a push of features
+            if self._resampler is not None:      # (ahead of them the resampler's last outputs, as a push of samples)
+                ahead = self._frontend.samples_in + self._resampler.pending
+                if ahead <= self._frontend.win // 2:         # refused as the front-end's flush refuses it, before anything moves
+                    raise ValueError(f'reflect padding needs more than {self._frontend.win // 2} samples (the utterance has {ahead} at '
+                                     f'{self._frontend.frontend.sample_rate} Hz)')
+                last = self._resampler.flush()
+                outs = [self._commit(self._staging if k else None, 0, k) for k in self._frontend.push_tiled(last, self._staging, self.max_chunk)]
             m = self._frontend.flush(out=(self._staging, 0)).shape[2]
-            outs = [self._commit(self._staging, off, n) for off, n in self._cuts(m)]
+            outs += [self._commit(self._staging, off, n) for off, n in self._cuts(m)]
         outs.append(self._commit(None, 0, 0, final=True))
         self._flushed = True
         return self._result(outs, decode, final=True)
@@ -481,22 +533,32 @@ class StreamingSession:
         zero padding in place of the right context that has not arrived.  ``decode`` as ``flush``: ``True`` -> ``(logits, tokens)``,
         ``'beam'`` -> ``(logits, (beams, scores, out_len))``, ``'beam-timed'`` -> ``(logits, (beams, scores, timesteps, out_len))`` over
         all the utterance's frames so far.  The session is left exactly as it was (DESIGN.md 9 "Peek"): every later push / flush / peek
-        returns the bits it would have returned without this call.  Before any frame: (batch, 0, 49) and empty hypotheses, no launch."""
+        returns the bits it would have returned without this call.  Before any frame: (batch, 0, 49) and empty hypotheses, no launch
+        (behind a resampler: unless its pending outputs would carry the front-end past ``win // 2`` samples, as they would at a flush)."""
         if self._flushed:
             raise ValueError('peek after flush: call reset() to start the next utterance')
         self._check_params()
         if decode in BEAM_DECODES:
             self._beam_check(decode)
-        if self.frames_in == 0:                  # (with a front-end: at most win // 2 samples so far, too few to end an utterance)
+        resampled = self._resampler is not None and self._fed == 'audio'
+        # behind a resampler its pending outputs come with the end: they can carry the front-end past win // 2 before any frame is in
+        endable = resampled and self._frontend.samples_in + self._resampler.pending > self._frontend.win // 2
+        if self.frames_in == 0 and not endable:  # (with a front-end: at most win // 2 samples so far, too few to end an utterance)
             logits = self._logits(0)
             if decode in BEAM_DECODES:
                 return logits, empty_beam_result(self.batch, self.beam_width, self.device, decode == 'beam-timed')
             return (logits, [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]) if decode else logits
         pk = self._peek_record()
         outs = []
-        if self._fed == 'audio':                 # the front-end's end frames as uncommitted pushes, then the final step
+        places = (self._place_other, lambda k, current: self._peek_thirds[k])
+        if resampled:                            # flush's steps: the frames the resampler's last outputs complete, then the end frames
+            fs, extra = self._frontend, self._resampler.peek()
+            m = fs.peek(out=(self._staging, 0), extra=extra).shape[2]
+            first = frames_final(fs.samples_in + extra.shape[1], fs.hop, fs.win) - fs.frames_out
+            cuts = [(off, n) for off, n in ((0, first), (first, m - first)) if n]          # (each at most end_frames <= max_chunk)
+            outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(cuts)]
+        elif self._fed == 'audio':               # the front-end's end frames as uncommitted pushes, then the final step
             m = self._frontend.peek(out=(self._staging, 0)).shape[2]
-            places = (self._place_other, lambda k, current: self._peek_thirds[k])
             outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(self._cuts(m))]
         outs.append(self._step(pk, None, 0, 0, True, lambda k, current: self._peek_window))
         logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
@@ -511,14 +573,14 @@ class StreamingSession:
         builds: the scratch window (sized for the largest stage window) and, for a session that pushes the front-end's two end frames
         in two steps (``max_chunk`` 1), a third buffer per stage."""
         if self._peek is None:
-            if self._frontend is not None and self.max_chunk < 2:
+            if self._frontend is not None and (self.max_chunk < 2 or self._resampler is not None):
                 self._peek_thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
                 self._bufs.extend(self._peek_thirds)
             self._peek_window = torch.empty(max(bufs[0].numel() for bufs in self.windows), device=self.device, dtype=torch.float32)
             h, c = (None if t is None else torch.empty_like(t) for t in (self._carried.h, self._carried.c))
             prev_token = torch.empty(max(self.batch, 4), device=self.device, dtype=torch.int32)
             self._bufs.extend(t for t in (self._peek_window, h, c, prev_token) if t is not None)
-            self._peek_frames = self._carried.planner.max_provisional_frames()      # the beam peek workspace is sized once, for these
+            self._peek_frames = self._carried.planner.max_provisional_frames(self.end_frames)      # the beam peek workspace is sized once, for these
             self._peek = _Carried(self._carried.planner.copy(), [], h, c, prev_token[:self.batch])
         self._peek.refresh(self._carried)
         return self._peek
