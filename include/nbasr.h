@@ -532,6 +532,39 @@ int nbasr_ctc_beam_stream_lm_peek(const float* log_probs, const int* chunk_lengt
                                   float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes,
                                   int beam_width, int blank, int cutoff_top_n, int pool_nodes, int timed, nbasr_stream_t stream);
 
+/* ---- endpointing: when has an utterance ended? (nb_asr_amd/ctc.py endpoint / EndpointStream; DESIGN.md 9 "Endpoint") ---------------
+ * No reference counterpart (the reference decodes whole utterances); the rules are the shape of Kaldi's online endpoint rules.  The
+ * definition is integer-exact after one float32 compare per frame, so whole = chunked = peeked = a row alone, bit for bit.
+ *   x(batch, frames, classes) float32, contiguous: logits or log-probabilities (the rule is invariant to a shift of a frame);
+ *   lengths(batch) int32 or NULL: row b takes its first lengths[b] <= frames frames; nothing at or beyond them is read;
+ *   the speech set S: bit c of speech_lo (c < 64) or bit c - 64 of speech_hi names class c, passed by value (the bit patterns of two
+ *   unsigned 64-bit words); margin: float32 >= 0;
+ *   rules(n_rules, 3) int32 device memory, 1 <= n_rules <= 8: rows (min_speech, min_trailing, min_frames), every entry >= 0 (the
+ *   caller's to keep: device memory is not inspected).
+ * State: one row of 8 int32 per utterance (nbasr_ctc_endpoint_state_bytes = 32 batch): frames, speech_frames, first_speech, last_speech,
+ *   endpoint_frame, endpoint_rule, 0, 0.  A fresh row is (0, 0, -1, -1, -1, -1).
+ * Each frame of a row, with global index g = frames:
+ *   1. ms = max of x[c] over c in S, mn = max over c not in S: each starts at -inf and is taken with `if (x[c] > m) m = x[c]` in
+ *      ascending c (a NaN is never taken);
+ *   2. the frame is SPEECH iff ms > mn + margin (one float32 add, one compare);
+ *   3. if speech: speech_frames += 1, last_speech = g, and first_speech = g if it was -1;
+ *   4. n_seen = g + 1; trailing = g - last_speech, or n_seen while last_speech == -1;
+ *   5. if endpoint_frame == -1: the lowest r with speech_frames >= min_speech[r], trailing >= min_trailing[r] and n_seen >= min_frames[r]
+ *      sets endpoint_frame = g, endpoint_rule = r.  The endpoint is latched; the counters go on counting after it;
+ *   6. frames += 1.
+ * nbasr_ctc_endpoint_step: one launch over the frames of a chunk (or of whole utterances).
+ *   state_in == NULL: the rows start fresh.  state_out == state_in: the step is committed in place.  state_out != state_in: a peek --
+ *   state_in is only read and state_out receives what a commit would have left.  frames == 0 succeeds and still copies state_in (or
+ *   fresh rows) to a different state_out.
+ *   mask_out(batch, frames) bytes or NULL: 1 where the frame is speech, 0 elsewhere and in the columns at or beyond a row's length.
+ *   Refused on the host before any device work: negative sizes, classes outside [2, 128], n_rules outside [1, 8], a margin that is
+ *   negative or NaN, mask bits at or above `classes`, an empty S, an S of every class (NBASR_EINVAL); x (with frames > 0), state_out or
+ *   rules NULL (NBASR_ENULL). */
+size_t nbasr_ctc_endpoint_state_bytes(int batch);
+int nbasr_ctc_endpoint_step(const float* x, const int* lengths, const int* state_in, int* state_out, const int* rules, int n_rules,
+                            long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out, int batch, int frames, int classes,
+                            nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

@@ -7,7 +7,8 @@ third-party C++, not in the reference's tree), ``PhonemeEncoder.fold_encoded(., 
 ``torch_edit_distance.compute_wer`` and the mean.  All of it runs on the device: ``beam_decode`` (prefix beam search),
 ``fold_table`` (the 48 -> 39 label table, with the reference's relabelling order), ``error_rates`` (label table + blank
 removal + Levenshtein distance) and ``decode_per`` = the whole of ``Trainer.decode``.  ``greedy_decode`` is the cheap
-width-1 relative (per-frame argmax, collapse, drop blank).
+width-1 relative (per-frame argmax, collapse, drop blank).  Beside the decoders, with no reference counterpart: ``forced_align``
+(which frames belong to which phoneme) and ``endpoint`` / ``EndpointStream`` (when has the utterance ended).
 """
 import collections
 import inspect
@@ -342,6 +343,250 @@ def empty_beam_result(batch, beam_width, device, timesteps=False):
     none = torch.zeros(batch, beam_width, 0, dtype=torch.int32).to(device)
     lens = torch.zeros(batch, beam_width, dtype=torch.int32).to(device)
     return hip.beam_result(none, scores.to(device), none.clone() if timesteps else None, lens)
+
+
+# ---- endpointing: when has an utterance ended? (nbasr.h "endpointing"; DESIGN.md §9 "Endpoint") ---------------------------------------
+NON_SPEECH_PHONEMES = ('sil', 'cl', 'vcl', 'epi')        # of the 48-set: silence, the two closures, the epenthetic silence
+MAX_ENDPOINT_RULES = 8
+MAX_ENDPOINT_CLASSES = 128
+
+
+def default_speech_classes():
+    """The classes that count as speech for the model's 49 outputs: every class except the blank (0) and the 48-set's ``sil``, ``cl``,
+    ``vcl`` and ``epi`` -- indices 0, 10, 17, 38 and 44 of ``phonemes.vocab(48, inc_blank=True)``.  A sorted tuple of ints."""
+    from .phonemes import vocab
+    return tuple(i for i, name in enumerate(vocab(48, inc_blank=True)) if i != 0 and name not in NON_SPEECH_PHONEMES)
+
+
+class EndpointRules:
+    """What the endpointer decides with: the speech classes, the margin, and up to 8 rules ``(min_speech, min_trailing, min_frames)`` in
+    output frames (40 ms each, ``FRAME_SECONDS``).  A frame is speech iff its largest value over ``speech_classes`` exceeds its largest
+    value over the other classes by more than ``margin`` (logits and log-probabilities give the same answer); a rule holds at a frame
+    when the utterance has at least ``min_speech`` speech frames, ``min_trailing`` frames since the last one (all frames, while there
+    is none) and ``min_frames`` frames in all; the first frame at which a rule holds is the endpoint, the lowest such rule its rule.
+
+    The defaults read: 5 s of silence with nothing said; 1 s of silence after speech; 20 s in all -- Kaldi's online-endpoint rules 1, 3
+    and 5 in 40 ms frames.  They are UNTUNED for this model: starting points, not recommendations.
+
+    Validates as the C side does (``ValueError``): 2..128 classes, a speech set that is neither empty nor every class and names no
+    class outside them, 1..8 rules of three non-negative int32 values, a margin that is a number >= 0.  Owns the device table of the
+    rules, made once, by the first step that needs it (``device`` None: the current HIP device)."""
+
+    def __init__(self, rules=((0, 125, 0), (1, 25, 0), (0, 0, 500)), speech_classes=None, margin=0.0, classes=49, device=None):
+        classes = int(classes)
+        if not 2 <= classes <= MAX_ENDPOINT_CLASSES:
+            raise ValueError(f'classes must lie in [2, {MAX_ENDPOINT_CLASSES}] (got {classes})')
+        if speech_classes is None:
+            if classes != 49:
+                raise ValueError(f'speech_classes must be given for {classes} classes (the default is for the 48-set and the blank)')
+            speech_classes = default_speech_classes()
+        given = [int(c) for c in speech_classes]
+        speech = sorted(set(given))
+        if len(speech) != len(given):
+            raise ValueError('speech_classes names a class twice')
+        if not speech:
+            raise ValueError('speech_classes is empty')
+        if speech[0] < 0 or speech[-1] >= classes:
+            raise ValueError(f'speech_classes must lie in [0, {classes}) (got {speech[0]}..{speech[-1]})')
+        if len(speech) == classes:
+            raise ValueError('speech_classes is every class: no class is left for non-speech')
+        rules = tuple(tuple(rule) for rule in rules)
+        if not 1 <= len(rules) <= MAX_ENDPOINT_RULES:
+            raise ValueError(f'there must be 1 to {MAX_ENDPOINT_RULES} rules (got {len(rules)})')
+        for rule in rules:
+            if len(rule) != 3 or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 31 for v in rule):
+                raise ValueError(f'a rule is (min_speech, min_trailing, min_frames), non-negative int32 frame counts (got {rule})')
+        margin = float(margin)
+        if not margin >= 0.0:
+            raise ValueError(f'margin must be a number >= 0 (got {margin})')
+        self.rules = tuple(tuple(int(v) for v in rule) for rule in rules)
+        self.speech_classes, self.margin, self.classes = tuple(speech), margin, classes
+        word = sum(1 << c for c in speech)
+        self.speech_lo, self.speech_hi = word & (2 ** 64 - 1), word >> 64
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise ValueError(f'the endpointer runs on a HIP device (got {self.device}); this package has no CPU path')
+        self._table = None
+
+    @staticmethod
+    def frames_for(seconds):
+        """Seconds -> frames: the seconds to the millisecond, then the smallest frame count that covers them (1.0 -> 25, 0.05 -> 2)."""
+        ms, frame_ms = round(float(seconds) * 1000), round(FRAME_SECONDS * 1000)
+        if ms < 0:
+            raise ValueError(f'a duration must not be negative (got {seconds} s)')
+        return -(-ms // frame_ms)
+
+    @classmethod
+    def from_seconds(cls, rules=((0.0, 5.0, 0.0), (0.04, 1.0, 0.0), (0.0, 0.0, 20.0)), **kwargs):
+        """The rules given as ``(min_speech, min_trailing, min_total)`` in seconds (``frames_for`` converts each); the other arguments
+        are the constructor's.  The defaults are the constructor's."""
+        return cls(tuple(tuple(cls.frames_for(v) for v in rule) for rule in rules), **kwargs)
+
+    def table_on(self, device):
+        """The rules as an (n_rules, 3) int32 tensor on ``device``, made by the first call; a rule set lives on one device."""
+        if self.device is not None and self.device.index is not None and self.device != device:
+            raise ValueError(f'the rules live on {self.device}, not on {device}')
+        if self._table is None:
+            self.device = device
+            self._table = torch.tensor(self.rules, dtype=torch.int32).to(device).contiguous()
+        return self._table
+
+    @property
+    def table(self):
+        """The device table (``device`` None or without an index: on the current HIP device)."""
+        if self.device is None or self.device.index is None:
+            return self.table_on(torch.device('cuda', torch.cuda.current_device()))
+        return self.table_on(self.device)
+
+    def __repr__(self):
+        return f'EndpointRules(rules={self.rules}, speech_classes={self.speech_classes}, margin={self.margin}, classes={self.classes})'
+
+
+class EndpointResult:
+    """The endpointer's view of a batch: int32 device tensors (B) ``frames`` (frames seen), ``speech_frames``, ``first_speech`` and
+    ``last_speech`` (frame indices, -1: none yet), ``endpoint_frame`` (the frame at which the first rule held, -1: no endpoint yet)
+    and ``rule`` (that rule's index, -1).  Nothing here reads the device: ``bool((r.endpoint_frame >= 0).any())`` is the caller's
+    synchronisation.  The tensors are columns of the state record they were made from: a stream's ``result`` shows its committed
+    record and moves with the next ``push`` or ``reset()``, a peek's shows the peek record until the next ``peek``; ``clone()`` keeps one."""
+
+    FIELDS = ('frames', 'speech_frames', 'first_speech', 'last_speech', 'endpoint_frame', 'rule')
+
+    def __init__(self, state):
+        self.state = state                       # (B, 8) int32
+        for k, name in enumerate(self.FIELDS):
+            setattr(self, name, state[:, k])
+
+    def clone(self):
+        """A copy that no later step changes (one device copy)."""
+        return EndpointResult(self.state.clone())
+
+    def seconds(self):
+        """(``endpoint_frame``, ``first_speech``, ``last_speech``) as float32 device tensors of seconds from the utterance's start:
+        the START of each frame, ``frame * FRAME_SECONDS``; -1 frames stay -1.0."""
+        return tuple(torch.where(t >= 0, t.to(torch.float32) * FRAME_SECONDS, -1.0) for t in (self.endpoint_frame, self.first_speech, self.last_speech))
+
+    def __repr__(self):
+        return 'EndpointResult(' + ', '.join(f'{name}={getattr(self, name).tolist()}' for name in self.FIELDS) + ')'
+
+
+def _endpoint_chunk(x, rules, batch=None):
+    if not isinstance(rules, EndpointRules):
+        raise ValueError(f'rules must be an EndpointRules (got {type(rules).__name__})')
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or (batch is not None and x.shape[0] != batch):
+        raise ValueError(f'expected ({"batch" if batch is None else batch}, frames, classes) logits or log-probabilities, got '
+                         f'{tuple(getattr(x, "shape", ()))}')
+    if x.shape[2] != rules.classes:
+        raise ValueError(f'the rules are for {rules.classes} classes, x has {x.shape[2]}')
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f'x must be float32 on a HIP device (got {x.dtype} on {x.device}); this package has no CPU path')
+    return x.contiguous()
+
+
+def endpoint(x, output_len=None, rules=None, return_mask=False):
+    """Where do these utterances end?  ``x`` (B, T', C) float32 logits or log-probabilities on the device, ``output_len`` their valid
+    frames (tensor, sequence or None), ``rules`` an ``EndpointRules`` (None: the defaults, 49 classes).  Returns an ``EndpointResult``
+    -- with ``return_mask=True`` ``(result, mask)``, mask (B, T') uint8: 1 where the frame is speech, 0 beyond an utterance's length.
+    A fresh state and one step of the kernel the streams run (nbasr_ctc_endpoint_step): the same bits as any chunking of the frames."""
+    rules = EndpointRules() if rules is None else rules
+    x = _endpoint_chunk(x, rules)
+    b, n, _ = x.shape
+    lengths = _lengths(output_len, b, x.device)
+    state = torch.empty(b, hip.ENDPOINT_STATE_WORDS, dtype=torch.int32, device=x.device)
+    mask = torch.empty(b, n, dtype=torch.uint8, device=x.device) if return_mask else None
+    if b:
+        hip.ctc_endpoint_step(x, lengths, None, state, rules.table_on(x.device), rules.speech_lo, rules.speech_hi, rules.margin, mask)
+    result = EndpointResult(state)
+    return (result, mask) if return_mask else result
+
+
+class EndpointStream:
+    """``endpoint`` fed chunk by chunk (nbasr_ctc_endpoint_step with a carried state; DESIGN.md §9 "Endpoint").
+
+        ep = EndpointStream(batch, rules, device=dev)
+        r = ep.push(logits_chunk, lengths=None)  # EndpointResult of everything pushed: == endpoint(all frames), bit for bit
+        r = ep.peek(next_chunk)                  # what push(next_chunk) would return; the stream stays as it was
+        ep.result                                # the committed result; ep.reset() starts the next utterances
+
+    ``lengths`` (B) gives each utterance's frames in this chunk, as in ``BeamSearchStream.push``: fewer than the chunk has ends that
+    utterance, and it takes no frames after that (host values cost no synchronisation; a device tensor is read back).  A push of no
+    frames launches nothing.  ``peek`` writes to a second state record that the first peek allocates.  ``reset()`` launches nothing:
+    the next step is handed no input state (``state_in == NULL``) and starts from fresh rows, and until then ``result`` shows a
+    constant fresh record made with the stream."""
+
+    def __init__(self, batch, rules=None, device=None):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        rules = EndpointRules(device=device) if rules is None else rules
+        if not isinstance(rules, EndpointRules):
+            raise ValueError(f'rules must be an EndpointRules (got {type(rules).__name__})')
+        device = torch.device(rules.device if device is None and rules.device is not None else 'cuda' if device is None else device)
+        if device.type != 'cuda':
+            raise ValueError(f'the endpointer runs on a HIP device (got {device}); this package has no CPU path')
+        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        self.batch, self.rules, self._table = batch, rules, rules.table_on(self.device)
+        self.state = torch.empty(batch, hip.ENDPOINT_STATE_WORDS, dtype=torch.int32, device=self.device)
+        self._fresh_state = torch.tensor([[0, 0, -1, -1, -1, -1, 0, 0]] * batch, dtype=torch.int32).to(self.device)     # never written
+        self._peek_state = None
+        self.reset()
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the state: the committed record, the constant fresh one, and the peek record once it exists."""
+        return sum(t.numel() * t.element_size() for t in (self.state, self._fresh_state, self._peek_state) if t is not None)
+
+    def reset(self):
+        """Start a new batch of utterances.  No launch: the next step starts from fresh rows."""
+        self._fresh = True
+        self.ended = torch.zeros(self.batch, dtype=torch.bool)
+
+    @property
+    def result(self):
+        """The ``EndpointResult`` of the frames committed so far."""
+        return EndpointResult(self._fresh_state if self._fresh else self.state)
+
+    def _chunk(self, x, lengths):
+        x = _endpoint_chunk(x, self.rules, self.batch)
+        if x.device != self.device:
+            raise ValueError(f'x must be on {self.device} (got {x.device})')
+        n = x.shape[1]
+        if lengths is None:
+            return x, n, None, None
+        rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
+        if rows.numel() != self.batch:
+            raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
+        if bool(((rows < 0) | (rows > n)).any()):
+            raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
+        if bool((self.ended & (rows > 0)).any()):
+            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        return x, n, rows, rows.to(device=self.device, dtype=torch.int32)
+
+    def _step(self, x, chunk_lengths, state_out):
+        r = self.rules
+        hip.ctc_endpoint_step(x, chunk_lengths, None if self._fresh else self.state, state_out, self._table, r.speech_lo, r.speech_hi, r.margin)
+
+    def push(self, x, lengths=None):
+        """Take the next chunk (B, n, C) of logits or log-probabilities; returns the ``EndpointResult`` of everything pushed."""
+        x, n, rows, chunk_lengths = self._chunk(x, lengths)
+        if n:
+            self._step(x, chunk_lengths, self.state)
+            self._fresh = False
+            if rows is not None:
+                self.ended |= rows < n
+        return self.result
+
+    def peek(self, x=None, lengths=None):
+        """The result ``push(x, lengths)`` would return, with the stream left as it was (the committed record is only read).  ``x`` None
+        or of no frames: ``result``, no launch."""
+        if x is None:
+            return self.result
+        x, n, _, chunk_lengths = self._chunk(x, lengths)
+        if not n:
+            return self.result
+        if self._peek_state is None:
+            self._peek_state = torch.empty_like(self.state)
+        self._step(x, chunk_lengths, self._peek_state)
+        return EndpointResult(self._peek_state)
 
 
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):

@@ -124,6 +124,9 @@ SIGNATURES = {
     'nbasr_ctc_beam_search_lm': (_c_int, [_c_float_p] * 8 + [_c_int] * 7 + [_c_stream]),
     'nbasr_ctc_beam_stream_lm_step': (_c_int, [_c_float_p] * 12 + [_c_int] * 8 + [_c_stream]),
     'nbasr_ctc_beam_stream_lm_peek': (_c_int, [_c_float_p] * 3 + [ctypes.c_void_p] + [_c_float_p] * 5 + [_c_int] * 9 + [_c_stream]),
+    'nbasr_ctc_endpoint_state_bytes': (ctypes.c_size_t, [_c_int]),
+    'nbasr_ctc_endpoint_step': (_c_int, [_c_float_p] * 5 + [_c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
+                                + [_c_int] * 3 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -1294,6 +1297,46 @@ def ctc_forced_align(log_probs, lengths, targets, target_lengths, blank=0):
                                       scores.data_ptr(), path.data_ptr(), starts.data_ptr(), ends.data_ptr(), token_scores.data_ptr(),
                                       b, t, c, ld, blank, _stream(log_probs)), 'nbasr_ctc_forced_align')
     return scores, path, starts, ends, token_scores
+
+
+ENDPOINT_STATE_WORDS = 8         # int32 per utterance: frames, speech_frames, first_speech, last_speech, endpoint_frame, endpoint_rule, 0, 0
+
+
+def ctc_endpoint_state_bytes(batch):
+    """Bytes of the endpoint state of ``batch`` utterances (nbasr.h: nbasr_ctc_endpoint_state_bytes); 0 for a batch that is not positive."""
+    return int(load_library().nbasr_ctc_endpoint_state_bytes(int(batch)))
+
+
+def _signed64(word):
+    """An unsigned 64-bit pattern as the ``long long`` that carries it by value."""
+    word = int(word) & 0xFFFFFFFFFFFFFFFF
+    return word - (1 << 64) if word >> 63 else word
+
+
+def ctc_endpoint_step(x, lengths, state_in, state_out, rules, speech_lo, speech_hi, margin, mask_out=None):
+    """One step of the endpointer (nbasr.h: nbasr_ctc_endpoint_step) over ``x`` (B, n, C) float32 logits or log-probabilities.
+    ``lengths``: int32 device tensor (B) or None.  ``state_in`` / ``state_out``: (B, 8) int32 device tensors -- ``state_in`` None starts
+    fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.  ``rules``: (n_rules, 3) int32 device
+    table; ``speech_lo`` / ``speech_hi``: the class mask's two 64-bit words; ``mask_out``: (B, n) uint8 device tensor or None.
+    Returns ``state_out``."""
+    _dev(x, 'x')
+    if x.dim() != 3:
+        raise HipError(f'ctc_endpoint_step: x must be (batch, frames, classes), got {tuple(x.shape)}')
+    b, n, c = x.shape
+    _int_tensor(state_out, 'state_out', x.device, (b, ENDPOINT_STATE_WORDS))
+    if state_in is not None:
+        _int_tensor(state_in, 'state_in', x.device, (b, ENDPOINT_STATE_WORDS))
+    _int_tensor(rules, 'rules', x.device, (rules.shape[0], 3))
+    if lengths is not None:
+        _int_tensor(lengths, 'lengths', x.device, (b,))
+    if mask_out is not None and (mask_out.dtype != torch.uint8 or mask_out.device != x.device or tuple(mask_out.shape) != (b, n)
+                                 or not mask_out.is_contiguous()):
+        raise HipError(f'ctc_endpoint_step: mask_out must be a contiguous ({b}, {n}) uint8 tensor on {x.device}')
+    _check(load_library().nbasr_ctc_endpoint_step(
+        x.data_ptr() if x.numel() else None, None if lengths is None else lengths.data_ptr(), None if state_in is None else state_in.data_ptr(),
+        state_out.data_ptr(), rules.data_ptr(), rules.shape[0], _signed64(speech_lo), _signed64(speech_hi), float(margin),
+        mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None, b, n, c, _stream(x)), 'nbasr_ctc_endpoint_step')
+    return state_out
 
 
 # ---------------------------------------------------------------------------------------------

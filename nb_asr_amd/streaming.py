@@ -17,6 +17,9 @@
     sess = model.eval().stream(batch=B, frontend=fe)                   # fe: frontend.LogMelFrontend on the model's device
     logits = sess.push_audio(wave_chunk)         # (B, n) float32 samples: the front-end's stream (frontend.FrontendStream), then push
     sess = StreamingSession(model.eval(), B, frontend=fe, input_rate=48000)      # push_audio takes samples at 48 kHz (frontend.Resampler)
+    sess = StreamingSession(model.eval(), B, endpoint=ctc.EndpointRules())       # every push / flush also feeds an endpointer:
+    sess.endpoint.endpoint_frame                 # (B) int32 on the device, -1 until a rule held; latched until reset()
+    provisional, ahead = sess.peek_endpoint()    # peek(), and the endpointer's view with the provisional frames included
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -32,7 +35,7 @@ utterance's true start / end, where the full forward's padding is the same zeros
 import torch
 
 from . import hip
-from .ctc import BeamSearchStream, empty_beam_result, fusion_table
+from .ctc import BeamSearchStream, EndpointRules, EndpointStream, empty_beam_result, fusion_table
 from .frontend import LogMelFrontend, Resampler, end_frames_bound, frames_final
 
 FEATURES = 80
@@ -285,12 +288,17 @@ class StreamingSession:
     ``ASRModel.stream`` keeps its parameter list, so a session with an LM is made with this constructor, which takes ``stream``'s
     arguments after the model.  ``input_rate``: the sample rate of what ``push_audio`` is given, when it is not the front-end's
     (``frontend.Resampler``: a HIP resampler ahead of the front-end's stream; DESIGN.md 9 "Resampler").  ``None`` or the front-end's own
-    rate is the session without the argument, launch for launch.  ``lookahead_samples`` is then in samples at the input rate."""
+    rate is the session without the argument, launch for launch.  ``lookahead_samples`` is then in samples at the input rate.
+    ``endpoint``: a ``ctc.EndpointRules``; the session then keeps a ``ctc.EndpointStream`` and every push / push_audio / flush hands it
+    the logits it returns, after the decode launches -- one more launch when the step emitted a frame, none otherwise (``endpoint``,
+    ``peek_endpoint``; DESIGN.md 9 "Endpoint").  ``None`` is the session without the argument: nothing allocated, nothing launched."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, lm=None, alpha=1.0,
-                 beta=0.0):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, endpoint=None, lm=None,
+                 alpha=1.0, beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
+        if endpoint is not None and not isinstance(endpoint, EndpointRules):
+            raise ValueError(f'endpoint must be a ctc.EndpointRules or None (got {type(endpoint).__name__})')
         resampler = self.resampler_for(frontend, input_rate, getattr(frontend, 'device', None))
         self.end_frames = self.check_max_chunk(max_chunk, frontend, resampler)
         p0 = model.model[0].conv.weight
@@ -368,6 +376,12 @@ class StreamingSession:
                 self._resampler = resampler.stream(B)
                 self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
         self._pack()
+        self._endpoint = None
+        if endpoint is not None:
+            classes = model.model[self.specs[-1].layer].out_features
+            if endpoint.classes != classes:
+                raise ValueError(f'the endpoint rules are for {endpoint.classes} classes, the model has {classes}')
+            self._endpoint = EndpointStream(B, endpoint, dev)
         self.reset()
 
     @staticmethod
@@ -441,12 +455,19 @@ class StreamingSession:
     @property
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
-        front-end its sample tails and the staging buffer, and from the first ``peek`` on the peek's scratch window, state copies and
-        beam workspace)."""
+        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, and from the first ``peek`` on the
+        peek's scratch window, state copies and beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0)
-                + (self._resampler.state_bytes if self._resampler is not None else 0))
+                + (self._resampler.state_bytes if self._resampler is not None else 0)
+                + (self._endpoint.state_bytes if self._endpoint is not None else 0))
+
+    @property
+    def endpoint(self):
+        """The ``ctc.EndpointResult`` of the logit frames returned so far in this utterance (device tensors, no synchronisation); None for
+        a session made without ``endpoint=``.  Once ``endpoint_frame >= 0`` it stays until ``reset()``: committed frames never change."""
+        return None if self._endpoint is None else self._endpoint.result
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -461,6 +482,8 @@ class StreamingSession:
             self._frontend.reset()
         if self._resampler is not None:
             self._resampler.reset()
+        if self._endpoint is not None:
+            self._endpoint.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
@@ -568,6 +591,17 @@ class StreamingSession:
             return logits, dec.peek(self._log_probs(logits))
         return (logits, self._greedy(pk, logits)) if decode else logits
 
+    def peek_endpoint(self, decode=False):
+        """``(peek(decode), EndpointResult)``: one peek of the model, then the endpointer's peek over the provisional logits on top of its
+        committed state -- ``ctc.endpoint`` of the committed and the provisional frames together.  A peeked endpoint is PROVISIONAL:
+        the provisional frames are computed as if the audio stopped now and can change when more arrives, so an endpoint seen here
+        can disappear; a committed one (``endpoint``) cannot.  The session and its endpointer are left as they were."""
+        if self._endpoint is None:
+            raise ValueError('peek_endpoint needs endpoint rules: StreamingSession(..., endpoint=ctc.EndpointRules(...))')
+        peeked = self.peek(decode)
+        logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
+        return peeked, self._endpoint.peek(logits)
+
     def _peek_record(self):
         """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
         builds: the scratch window (sized for the largest stage window) and, for a session that pushes the front-end's two end frames
@@ -623,8 +657,12 @@ class StreamingSession:
             dec = self._decoder(decode)
             self._beam_frames += logits.shape[1]
             pushed = dec.push(self._log_probs(logits))
-            return (logits, dec.finish()) if final else (logits,) + pushed
-        return (logits, self._greedy(self._carried, logits)) if decode else logits
+            result = (logits, dec.finish()) if final else (logits,) + pushed
+        else:
+            result = (logits, self._greedy(self._carried, logits)) if decode else logits
+        if self._endpoint is not None:           # after the decode launches; a step that emitted no frame launches nothing
+            self._endpoint.push(logits)
+        return result
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
     # Where a step builds stage k's new window is all that tells a committed step from the steps of a peek: ``place(k, current)``,
