@@ -565,6 +565,51 @@ int nbasr_ctc_endpoint_step(const float* x, const int* lengths, const int* state
                             long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out, int batch, int frames, int classes,
                             nbasr_stream_t stream);
 
+/* ---- keywords: has this phrase just been said? (nb_asr_amd/ctc.py spot_keywords / KeywordStream; DESIGN.md 9 "Keywords") -------------
+ * No reference counterpart.  Per (utterance, keyword) and frame: the score of the best CTC path that spells the keyword, ends at this
+ * frame and starts anywhere, as a log-likelihood ratio against the unconstrained best path over the same frames.  Every step is a float32
+ * compare, one subtract or one add in a fixed order, so whole = chunked = peeked = a row alone = a keyword alone, bit for bit.
+ *   x(batch, frames, classes) float32, contiguous: logits or log-probabilities (the costs are the same for both, up to rounding);
+ *   lengths(batch) int32 or NULL: row b takes its first lengths[b] <= frames frames; nothing at or beyond them is read;
+ *   tokens(n_keywords, 32) int32 device memory: keyword k's token_counts[k] tokens, -1 past its end; 1 <= n_keywords <= 64; a keyword
+ *   has 1 to 32 tokens, each in [0, classes) and none of them `blank`; thresholds(n_keywords) float32 device memory, each finite and
+ *   <= 0 (the three tables are the caller's to keep: device memory is not inspected).
+ * States: a keyword of L tokens has S = 2 L - 1 states; state s = 2 i is token i, odd states are the blank between two tokens; there is
+ *   no leading or trailing blank state (the start is free, a match ends on its last token's frame).  z(s) is the class of state s.
+ * State: one row of 136 32-bit words per (utterance, keyword), utterance-major (nbasr_ctc_keyword_state_bytes = 544 batch n_keywords):
+ *   word 0 frames; 1-3 hit_frame, hit_start, hit_score (float bits); 4-6 best_frame, best_start, best_score (float bits); 7 zero;
+ *   8-71 V[0..63] (float bits); 72-135 start[0..63].  A fresh row is (0, -1, -1, -inf, -1, -1, -inf, 0), V = -inf, start = -1; states at
+ *   or above S always hold -inf and -1, so a state is comparable to the bit.
+ * Each frame of a row, with global index g = frames:
+ *   1. m = the maximum of x[c]: it starts at -inf and is taken with `if (x[c] > m) m = x[c]` in ascending c (a NaN is never taken);
+ *   2. for every state s, best starts at (-inf, start -1); the candidates are tried in this order and each replaces best only if its
+ *      value is > best's: stay V[s]; advance V[s-1] if s >= 1; skip the blank V[s-2] if s is even, s >= 2 and z(s) != z(s-2); for s = 0
+ *      only, a fresh start: value 0 with start g.  All reads are of the previous frame's V and start;
+ *   3. V'[s] = best + (x[z(s)] - m): one float32 subtract, then one float32 add (no multiply: nothing to contract); start'[s] is the
+ *      chosen candidate's start;
+ *   4. score = V'[S-1], from = start'[S-1]: the log-likelihood ratio between the best path that spells the keyword over frames
+ *      [from, g] and the unconstrained best path over the same frames.  It is always <= 0, and 0 exactly when the greedy path over that
+ *      span collapses to the keyword;
+ *   5. if score > best_score: (best_score, best_frame, best_start) = (score, g, from);
+ *   6. if hit_frame == -1 and score >= threshold: (hit_frame, hit_start, hit_score) = (g, from, score).  The hit is latched; the scores
+ *      and best_* go on updating after it;
+ *   7. frames += 1.
+ *   NaN: a frame in which x[z(s)] - m is NaN makes V'[s] NaN; that value is never taken again, because every compare is > or >=: paths
+ *   through it die, and later fresh starts are unaffected.
+ * nbasr_ctc_keyword_step: one launch over the frames of a chunk (or of whole utterances).
+ *   state_in == NULL: the rows start fresh.  state_out == state_in: the step is committed in place.  state_out != state_in: a peek --
+ *   state_in is only read and state_out receives what a commit would have left.  frames == 0 succeeds and still copies state_in (or
+ *   fresh rows) to a different state_out.
+ *   scores_out, starts_out (batch, n_keywords, frames) float32 / int32, both or neither: every frame's score and from; -inf and -1 at
+ *   and beyond a row's length.
+ *   Refused on the host before any device work: negative sizes, classes outside [2, 128], n_keywords outside [1, 64], blank outside
+ *   [0, classes), exactly one of the two trace pointers (NBASR_EINVAL); x (with frames > 0), tokens, token_counts, thresholds or
+ *   state_out NULL (NBASR_ENULL). */
+size_t nbasr_ctc_keyword_state_bytes(int batch, int n_keywords);
+int nbasr_ctc_keyword_step(const float* x, const int* lengths, const int* tokens, const int* token_counts, const float* thresholds,
+                           int n_keywords, int blank, const int* state_in, int* state_out, float* scores_out, int* starts_out, int batch,
+                           int frames, int classes, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

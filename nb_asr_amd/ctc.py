@@ -8,7 +8,8 @@ third-party C++, not in the reference's tree), ``PhonemeEncoder.fold_encoded(., 
 ``fold_table`` (the 48 -> 39 label table, with the reference's relabelling order), ``error_rates`` (label table + blank
 removal + Levenshtein distance) and ``decode_per`` = the whole of ``Trainer.decode``.  ``greedy_decode`` is the cheap
 width-1 relative (per-frame argmax, collapse, drop blank).  Beside the decoders, with no reference counterpart: ``forced_align``
-(which frames belong to which phoneme) and ``endpoint`` / ``EndpointStream`` (when has the utterance ended).
+(which frames belong to which phoneme), ``endpoint`` / ``EndpointStream`` (when has the utterance ended) and ``spot_keywords`` /
+``KeywordStream`` (has this phrase just been said).
 """
 import collections
 import inspect
@@ -587,6 +588,293 @@ class EndpointStream:
             self._peek_state = torch.empty_like(self.state)
         self._step(x, chunk_lengths, self._peek_state)
         return EndpointResult(self._peek_state)
+
+
+# ---- keywords: has this phrase just been said? (nbasr.h "keywords"; DESIGN.md §9 "Keywords") -------------------------------------------
+MAX_KEYWORDS = 64
+MAX_KEYWORD_TOKENS = hip.KEYWORD_MAX_TOKENS
+_NEG_INF_BITS = -8388608         # float32 -inf as an int32
+
+
+class KeywordSet:
+    """The phrases a spotter listens for: 1 to 64 keywords, each a sequence of 1 to 32 token ids in ``[0, classes)`` without the blank,
+    and one threshold per keyword.  A keyword's score at a frame is the log-likelihood ratio between the best CTC path that spells it
+    and ends at that frame (starting anywhere) and the unconstrained best path over the same frames: <= 0, and 0 exactly when the greedy
+    path over that span collapses to the keyword.  The first frame whose score is >= the threshold is the keyword's hit.
+
+    ``thresholds``: one finite float <= 0 per keyword, or one for all; None gives keyword k ``-per_token * len(keyword k)``.  That
+    default (one nat per token) is UNTUNED for this model: a starting point, not a recommendation.
+
+    Validates what the C side cannot see (``ValueError``): the counts above, a token outside ``[0, classes)`` or equal to the blank, a
+    threshold that is positive, NaN or infinite, a device that is not a HIP device.  Owns the device tables (tokens (K, 32) int32 with -1
+    past a keyword's end, token counts, thresholds), made once, by the first step that needs them (``device`` None: the current HIP
+    device)."""
+
+    def __init__(self, keywords, thresholds=None, per_token=1.0, classes=49, blank=0, device=None):
+        classes, blank = int(classes), int(blank)
+        if not 2 <= classes <= MAX_ENDPOINT_CLASSES:
+            raise ValueError(f'classes must lie in [2, {MAX_ENDPOINT_CLASSES}] (got {classes})')
+        if not 0 <= blank < classes:
+            raise ValueError(f'blank must lie in [0, {classes}) (got {blank})')
+        if isinstance(keywords, (str, bytes)) or not hasattr(keywords, '__iter__'):
+            raise ValueError('keywords must be a sequence of token-id sequences')
+        words = []
+        for word in keywords:
+            if isinstance(word, (str, bytes)) or not hasattr(word, '__iter__'):
+                raise ValueError(f'a keyword is a sequence of token ids (got {word!r}); names go through KeywordSet.from_phonemes')
+            word = list(word.tolist() if isinstance(word, torch.Tensor) else word)
+            if any(isinstance(t, (bool, str, bytes)) or int(t) != t for t in word):
+                raise ValueError(f'a keyword is a sequence of token ids (got {word})')
+            words.append(tuple(int(t) for t in word))
+        if not 1 <= len(words) <= MAX_KEYWORDS:
+            raise ValueError(f'there must be 1 to {MAX_KEYWORDS} keywords (got {len(words)})')
+        for word in words:
+            if not 1 <= len(word) <= MAX_KEYWORD_TOKENS:
+                raise ValueError(f'a keyword has 1 to {MAX_KEYWORD_TOKENS} tokens (got {len(word)})')
+            for t in word:
+                if not 0 <= t < classes:
+                    raise ValueError(f'a token must lie in [0, {classes}) (got {t})')
+                if t == blank:
+                    raise ValueError(f'a keyword cannot hold the blank ({blank})')
+        if thresholds is None:
+            per_token = float(per_token)
+            if not 0.0 <= per_token < float('inf'):
+                raise ValueError(f'per_token must be a finite number >= 0 (got {per_token})')
+            thresholds = [-per_token * len(word) for word in words]
+        elif not hasattr(thresholds, '__iter__'):
+            thresholds = [thresholds] * len(words)
+        thresholds = [float(t) for t in (thresholds.tolist() if isinstance(thresholds, torch.Tensor) else thresholds)]
+        if len(thresholds) != len(words):
+            raise ValueError(f'expected {len(words)} thresholds, got {len(thresholds)}')
+        thresholds = torch.tensor(thresholds, dtype=torch.float32)          # what the kernel compares with: float32
+        if not bool((torch.isfinite(thresholds) & (thresholds <= 0)).all()):
+            raise ValueError(f'a threshold must be a finite number <= 0 (got {thresholds.tolist()})')
+        self.keywords, self.thresholds, self.classes, self.blank = tuple(words), tuple(thresholds.tolist()), classes, blank
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise ValueError(f'the keyword spotter runs on a HIP device (got {self.device}); this package has no CPU path')
+        self._tables = None
+
+    @classmethod
+    def from_phonemes(cls, keywords, thresholds=None, per_token=1.0, device=None):
+        """Keywords given as phoneme names of the 48-set, ``[['sh', 'iy'], ...]``: each name's index in
+        ``phonemes.vocab(48, inc_blank=True)`` (49 classes, blank 0)."""
+        from .phonemes import vocab
+        index = {name: i for i, name in enumerate(vocab(48, inc_blank=True))}
+        words = []
+        for word in keywords:
+            if isinstance(word, (str, bytes)):
+                raise ValueError(f'a keyword is a sequence of phoneme names (got {word!r})')
+            for name in word:
+                if name not in index or index[name] == 0:
+                    raise ValueError(f'{name!r} is not a phoneme of the 48-set')
+            words.append([index[name] for name in word])
+        return cls(words, thresholds, per_token, classes=len(index), blank=0, device=device)
+
+    def __len__(self):
+        return len(self.keywords)
+
+    def host_tables(self):
+        """(tokens (K, 32) int32 with -1 past a keyword's end, token counts (K) int32, thresholds (K) float32) on the host."""
+        tokens = torch.full((len(self.keywords), MAX_KEYWORD_TOKENS), -1, dtype=torch.int32)
+        for k, word in enumerate(self.keywords):
+            tokens[k, :len(word)] = torch.tensor(word, dtype=torch.int32)
+        counts = torch.tensor([len(word) for word in self.keywords], dtype=torch.int32)
+        return tokens, counts, torch.tensor(self.thresholds, dtype=torch.float32)
+
+    def tables_on(self, device):
+        """The three tables on ``device``, made by the first call; a keyword set lives on one device."""
+        if self.device is not None and self.device.index is not None and self.device != device:
+            raise ValueError(f'the keywords live on {self.device}, not on {device}')
+        if self._tables is None:
+            self.device = device
+            self._tables = tuple(t.to(device).contiguous() for t in self.host_tables())
+        return self._tables
+
+    @property
+    def tables(self):
+        """The device tables (``device`` None or without an index: on the current HIP device)."""
+        if self.device is None or self.device.index is None:
+            return self.tables_on(torch.device('cuda', torch.cuda.current_device()))
+        return self.tables_on(self.device)
+
+    def __repr__(self):
+        return f'KeywordSet(keywords={self.keywords}, thresholds={self.thresholds}, classes={self.classes}, blank={self.blank})'
+
+
+class KeywordResult:
+    """The spotter's view of a batch: (B, K) device tensors, one entry per utterance and keyword.  int32 ``frames`` (frames seen),
+    ``hit_frame`` / ``hit_start`` (the first frame whose score reached the threshold and the frame the path that ends there started at;
+    -1: no hit yet), ``best_frame`` / ``best_start`` (the same for the highest score so far; the earliest frame on a tie), float32
+    ``hit_score`` / ``best_score`` (-inf: none), and ``detected`` (bool, ``hit_frame >= 0``, computed on the device when asked for).
+    Nothing here reads the device: ``bool(r.detected.any())`` is the caller's synchronisation.  The tensors are views of the state
+    record they were made from: a stream's ``result`` shows its committed record and moves with the next ``push`` or ``reset()``, a
+    peek's shows the peek record until the next ``peek``; ``clone()`` keeps one."""
+
+    INT_FIELDS = {'frames': 0, 'hit_frame': 1, 'hit_start': 2, 'best_frame': 4, 'best_start': 5}
+    FLOAT_FIELDS = {'hit_score': 3, 'best_score': 6}
+    FIELDS = ('frames', 'hit_frame', 'hit_start', 'hit_score', 'best_frame', 'best_start', 'best_score')
+
+    def __init__(self, state):
+        self.state = state                       # (B, K, 136) int32
+        as_float = state.view(torch.float32)
+        for name, word in self.INT_FIELDS.items():
+            setattr(self, name, state[:, :, word])
+        for name, word in self.FLOAT_FIELDS.items():
+            setattr(self, name, as_float[:, :, word])
+
+    @property
+    def detected(self):
+        return self.hit_frame >= 0
+
+    def clone(self):
+        """A copy that no later step changes (one device copy)."""
+        return KeywordResult(self.state.clone())
+
+    def seconds(self):
+        """(``hit_start``, ``hit_end``, ``best_start``, ``best_end``) as float32 device tensors of seconds from the utterance's start:
+        a span runs from the START of its first frame, ``start * FRAME_SECONDS``, to the END of its last, ``(frame + 1) *
+        FRAME_SECONDS``; where there is no hit (no frame yet) both are -1.0."""
+        def span(first, last):
+            return (torch.where(last >= 0, first.to(torch.float32) * FRAME_SECONDS, -1.0),
+                    torch.where(last >= 0, (last + 1).to(torch.float32) * FRAME_SECONDS, -1.0))
+        return span(self.hit_start, self.hit_frame) + span(self.best_start, self.best_frame)
+
+    def __repr__(self):
+        return 'KeywordResult(' + ', '.join(f'{name}={getattr(self, name).tolist()}' for name in self.FIELDS) + ')'
+
+
+def _keyword_chunk(x, keywords, batch=None):
+    if not isinstance(keywords, KeywordSet):
+        raise ValueError(f'keywords must be a KeywordSet (got {type(keywords).__name__})')
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or (batch is not None and x.shape[0] != batch):
+        raise ValueError(f'expected ({"batch" if batch is None else batch}, frames, classes) logits or log-probabilities, got '
+                         f'{tuple(getattr(x, "shape", ()))}')
+    if x.shape[2] != keywords.classes:
+        raise ValueError(f'the keywords are for {keywords.classes} classes, x has {x.shape[2]}')
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f'x must be float32 on a HIP device (got {x.dtype} on {x.device}); this package has no CPU path')
+    return x.contiguous()
+
+
+def _fresh_keyword_state(batch, n_keywords):
+    """(B, K, 136) int32 on the host: the fresh rows of nbasr.h."""
+    row = torch.full((hip.KEYWORD_STATE_WORDS,), -1, dtype=torch.int32)
+    row[0] = row[7] = 0
+    row[3] = row[6] = _NEG_INF_BITS
+    row[8:72] = _NEG_INF_BITS
+    return row.repeat(batch, n_keywords, 1)
+
+
+def spot_keywords(x, output_len=None, keywords=None, return_trace=False):
+    """Were these phrases said, and where?  ``x`` (B, T', C) float32 logits or log-probabilities on the device, ``output_len`` their
+    valid frames (tensor, sequence or None), ``keywords`` a ``KeywordSet``.  Returns a ``KeywordResult`` -- with ``return_trace=True``
+    ``(result, scores, starts)``, (B, K, T') float32 / int32: every frame's score and the frame its path started at, -inf and -1 beyond
+    an utterance's length (several occurrences of a keyword show as several peaks).  A fresh state and one step of the kernel the
+    streams run (nbasr_ctc_keyword_step): the same bits as any chunking of the frames."""
+    if keywords is None:
+        raise ValueError('keywords must be a KeywordSet: there is no default phrase')
+    x = _keyword_chunk(x, keywords)
+    b, n, _ = x.shape
+    k = len(keywords)
+    lengths = _lengths(output_len, b, x.device)
+    state = torch.empty(b, k, hip.KEYWORD_STATE_WORDS, dtype=torch.int32, device=x.device)
+    scores = torch.empty(b, k, n, dtype=torch.float32, device=x.device) if return_trace else None
+    starts = torch.empty(b, k, n, dtype=torch.int32, device=x.device) if return_trace else None
+    if b:
+        tokens, counts, thresholds = keywords.tables_on(x.device)
+        hip.ctc_keyword_step(x, lengths, tokens, counts, thresholds, keywords.blank, None, state, scores, starts)
+    result = KeywordResult(state)
+    return (result, scores, starts) if return_trace else result
+
+
+class KeywordStream:
+    """``spot_keywords`` fed chunk by chunk (nbasr_ctc_keyword_step with a carried state; DESIGN.md §9 "Keywords").
+
+        kw = KeywordStream(batch, keywords, device=dev)
+        r = kw.push(logits_chunk, lengths=None)  # KeywordResult of everything pushed: == spot_keywords(all frames), bit for bit
+        r = kw.peek(next_chunk)                  # what push(next_chunk) would return; the stream stays as it was
+        kw.result                                # the committed result; kw.reset() starts the next utterances
+
+    The contract is ``EndpointStream``'s.  ``lengths`` (B) gives each utterance's frames in this chunk: fewer than the chunk has ends
+    that utterance, and it takes no frames after that (host values cost no synchronisation; a device tensor is read back).  A push of
+    no frames launches nothing.  ``peek`` writes to a second state record that the first peek allocates.  ``reset()`` launches nothing:
+    the next step is handed no input state (``state_in == NULL``) and starts from fresh rows, and until then ``result`` shows a
+    constant fresh record made with the stream."""
+
+    def __init__(self, batch, keywords, device=None):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        if not isinstance(keywords, KeywordSet):
+            raise ValueError(f'keywords must be a KeywordSet (got {type(keywords).__name__})')
+        device = torch.device(keywords.device if device is None and keywords.device is not None else 'cuda' if device is None else device)
+        if device.type != 'cuda':
+            raise ValueError(f'the keyword spotter runs on a HIP device (got {device}); this package has no CPU path')
+        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        self.batch, self.keywords, self._tables = batch, keywords, keywords.tables_on(self.device)
+        self.state = torch.empty(batch, len(keywords), hip.KEYWORD_STATE_WORDS, dtype=torch.int32, device=self.device)
+        self._fresh_state = _fresh_keyword_state(batch, len(keywords)).to(self.device)      # never written
+        self._peek_state = None
+        self.reset()
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the state: the committed record, the constant fresh one, and the peek record once it exists."""
+        return sum(t.numel() * t.element_size() for t in (self.state, self._fresh_state, self._peek_state) if t is not None)
+
+    def reset(self):
+        """Start a new batch of utterances.  No launch: the next step starts from fresh rows."""
+        self._fresh = True
+        self.ended = torch.zeros(self.batch, dtype=torch.bool)
+
+    @property
+    def result(self):
+        """The ``KeywordResult`` of the frames committed so far."""
+        return KeywordResult(self._fresh_state if self._fresh else self.state)
+
+    def _chunk(self, x, lengths):
+        x = _keyword_chunk(x, self.keywords, self.batch)
+        if x.device != self.device:
+            raise ValueError(f'x must be on {self.device} (got {x.device})')
+        n = x.shape[1]
+        if lengths is None:
+            return x, n, None, None
+        rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
+        if rows.numel() != self.batch:
+            raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
+        if bool(((rows < 0) | (rows > n)).any()):
+            raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
+        if bool((self.ended & (rows > 0)).any()):
+            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+        return x, n, rows, rows.to(device=self.device, dtype=torch.int32)
+
+    def _step(self, x, chunk_lengths, state_out):
+        tokens, counts, thresholds = self._tables
+        hip.ctc_keyword_step(x, chunk_lengths, tokens, counts, thresholds, self.keywords.blank, None if self._fresh else self.state, state_out)
+
+    def push(self, x, lengths=None):
+        """Take the next chunk (B, n, C) of logits or log-probabilities; returns the ``KeywordResult`` of everything pushed."""
+        x, n, rows, chunk_lengths = self._chunk(x, lengths)
+        if n:
+            self._step(x, chunk_lengths, self.state)
+            self._fresh = False
+            if rows is not None:
+                self.ended |= rows < n
+        return self.result
+
+    def peek(self, x=None, lengths=None):
+        """The result ``push(x, lengths)`` would return, with the stream left as it was (the committed record is only read).  ``x`` None
+        or of no frames: ``result``, no launch."""
+        if x is None:
+            return self.result
+        x, n, _, chunk_lengths = self._chunk(x, lengths)
+        if not n:
+            return self.result
+        if self._peek_state is None:
+            self._peek_state = torch.empty_like(self.state)
+        self._step(x, chunk_lengths, self._peek_state)
+        return KeywordResult(self._peek_state)
 
 
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):

@@ -127,6 +127,8 @@ SIGNATURES = {
     'nbasr_ctc_endpoint_state_bytes': (ctypes.c_size_t, [_c_int]),
     'nbasr_ctc_endpoint_step': (_c_int, [_c_float_p] * 5 + [_c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
                                 + [_c_int] * 3 + [_c_stream]),
+    'nbasr_ctc_keyword_state_bytes': (ctypes.c_size_t, [_c_int, _c_int]),
+    'nbasr_ctc_keyword_step': (_c_int, [_c_float_p] * 5 + [_c_int] * 2 + [_c_float_p] * 4 + [_c_int] * 3 + [_c_stream]),
     # streaming windows
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
     # front-end
@@ -1336,6 +1338,52 @@ def ctc_endpoint_step(x, lengths, state_in, state_out, rules, speech_lo, speech_
         x.data_ptr() if x.numel() else None, None if lengths is None else lengths.data_ptr(), None if state_in is None else state_in.data_ptr(),
         state_out.data_ptr(), rules.data_ptr(), rules.shape[0], _signed64(speech_lo), _signed64(speech_hi), float(margin),
         mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None, b, n, c, _stream(x)), 'nbasr_ctc_endpoint_step')
+    return state_out
+
+
+KEYWORD_STATE_WORDS = 136        # 32-bit words per (utterance, keyword): frames, hit (frame, start, score), best (frame, start, score), 0, V[64], start[64]
+KEYWORD_MAX_TOKENS = 32          # the pitch of the token table
+
+
+def ctc_keyword_state_bytes(batch, n_keywords):
+    """Bytes of the keyword state of ``batch`` utterances and ``n_keywords`` keywords (nbasr.h: nbasr_ctc_keyword_state_bytes); 0 when
+    either is not positive."""
+    return int(load_library().nbasr_ctc_keyword_state_bytes(int(batch), int(n_keywords)))
+
+
+def ctc_keyword_step(x, lengths, tokens, token_counts, thresholds, blank, state_in, state_out, scores_out=None, starts_out=None):
+    """One step of the keyword spotter (nbasr.h: nbasr_ctc_keyword_step) over ``x`` (B, n, C) float32 logits or log-probabilities.
+    ``lengths``: int32 device tensor (B) or None.  ``tokens``: (K, 32) int32 device table, -1 past a keyword's end; ``token_counts``:
+    (K) int32; ``thresholds``: (K) float32.  ``state_in`` / ``state_out``: (B, K, 136) int32 device tensors -- ``state_in`` None starts
+    fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.  ``scores_out`` / ``starts_out``:
+    (B, K, n) float32 / int32 device tensors, both or neither.  Returns ``state_out``."""
+    _dev(x, 'x')
+    if x.dim() != 3:
+        raise HipError(f'ctc_keyword_step: x must be (batch, frames, classes), got {tuple(x.shape)}')
+    b, n, c = x.shape
+    _int_tensor(tokens, 'tokens', x.device, (tokens.shape[0], KEYWORD_MAX_TOKENS))
+    k = tokens.shape[0]
+    _int_tensor(token_counts, 'token_counts', x.device, (k,))
+    _dev(thresholds, 'thresholds')
+    if thresholds.device != x.device or tuple(thresholds.shape) != (k,):
+        raise HipError(f'ctc_keyword_step: thresholds must have shape ({k},) on {x.device}')
+    _int_tensor(state_out, 'state_out', x.device, (b, k, KEYWORD_STATE_WORDS))
+    if state_in is not None:
+        _int_tensor(state_in, 'state_in', x.device, (b, k, KEYWORD_STATE_WORDS))
+    if lengths is not None:
+        _int_tensor(lengths, 'lengths', x.device, (b,))
+    if (scores_out is None) != (starts_out is None):
+        raise HipError('ctc_keyword_step: the trace is scores_out and starts_out together: give both or neither')
+    if scores_out is not None:
+        _dev(scores_out, 'scores_out')
+        if scores_out.device != x.device or tuple(scores_out.shape) != (b, k, n):
+            raise HipError(f'ctc_keyword_step: scores_out must have shape ({b}, {k}, {n}) on {x.device}')
+        _int_tensor(starts_out, 'starts_out', x.device, (b, k, n))
+    trace = scores_out is not None and scores_out.numel() > 0
+    _check(load_library().nbasr_ctc_keyword_step(
+        x.data_ptr() if x.numel() else None, None if lengths is None else lengths.data_ptr(), tokens.data_ptr(), token_counts.data_ptr(),
+        thresholds.data_ptr(), k, int(blank), None if state_in is None else state_in.data_ptr(), state_out.data_ptr(),
+        scores_out.data_ptr() if trace else None, starts_out.data_ptr() if trace else None, b, n, c, _stream(x)), 'nbasr_ctc_keyword_step')
     return state_out
 
 

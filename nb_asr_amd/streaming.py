@@ -20,6 +20,9 @@
     sess = StreamingSession(model.eval(), B, endpoint=ctc.EndpointRules())       # every push / flush also feeds an endpointer:
     sess.endpoint.endpoint_frame                 # (B) int32 on the device, -1 until a rule held; latched until reset()
     provisional, ahead = sess.peek_endpoint()    # peek(), and the endpointer's view with the provisional frames included
+    sess = StreamingSession(model.eval(), B, keywords=ctc.KeywordSet.from_phonemes([['sh', 'iy']]))      # ... and a keyword spotter:
+    sess.keywords.hit_frame                      # (B, K) int32 on the device, -1 until keyword k's score reached its threshold; latched
+    provisional, ahead = sess.peek_keywords()    # peek(), and the spotter's view with the provisional frames included
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -35,7 +38,7 @@ utterance's true start / end, where the full forward's padding is the same zeros
 import torch
 
 from . import hip
-from .ctc import BeamSearchStream, EndpointRules, EndpointStream, empty_beam_result, fusion_table
+from .ctc import BeamSearchStream, EndpointRules, EndpointStream, KeywordSet, KeywordStream, empty_beam_result, fusion_table
 from .frontend import LogMelFrontend, Resampler, end_frames_bound, frames_final
 
 FEATURES = 80
@@ -291,14 +294,19 @@ class StreamingSession:
     rate is the session without the argument, launch for launch.  ``lookahead_samples`` is then in samples at the input rate.
     ``endpoint``: a ``ctc.EndpointRules``; the session then keeps a ``ctc.EndpointStream`` and every push / push_audio / flush hands it
     the logits it returns, after the decode launches -- one more launch when the step emitted a frame, none otherwise (``endpoint``,
-    ``peek_endpoint``; DESIGN.md 9 "Endpoint").  ``None`` is the session without the argument: nothing allocated, nothing launched."""
+    ``peek_endpoint``; DESIGN.md 9 "Endpoint").  ``None`` is the session without the argument: nothing allocated, nothing launched.
+    ``keywords``: a ``ctc.KeywordSet``; the session then keeps a ``ctc.KeywordStream`` and hands it the same logits after the decode
+    and endpoint launches, again one more launch when the step emitted a frame (``keywords``, ``peek_keywords``; DESIGN.md 9
+    "Keywords").  ``None``: nothing allocated, nothing launched."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, endpoint=None, lm=None,
-                 alpha=1.0, beta=0.0):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, endpoint=None,
+                 keywords=None, lm=None, alpha=1.0, beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
         if endpoint is not None and not isinstance(endpoint, EndpointRules):
             raise ValueError(f'endpoint must be a ctc.EndpointRules or None (got {type(endpoint).__name__})')
+        if keywords is not None and not isinstance(keywords, KeywordSet):
+            raise ValueError(f'keywords must be a ctc.KeywordSet or None (got {type(keywords).__name__})')
         resampler = self.resampler_for(frontend, input_rate, getattr(frontend, 'device', None))
         self.end_frames = self.check_max_chunk(max_chunk, frontend, resampler)
         p0 = model.model[0].conv.weight
@@ -382,6 +390,12 @@ class StreamingSession:
             if endpoint.classes != classes:
                 raise ValueError(f'the endpoint rules are for {endpoint.classes} classes, the model has {classes}')
             self._endpoint = EndpointStream(B, endpoint, dev)
+        self._keywords = None
+        if keywords is not None:
+            classes = model.model[self.specs[-1].layer].out_features
+            if keywords.classes != classes:
+                raise ValueError(f'the keywords are for {keywords.classes} classes, the model has {classes}')
+            self._keywords = KeywordStream(B, keywords, dev)
         self.reset()
 
     @staticmethod
@@ -455,19 +469,26 @@ class StreamingSession:
     @property
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
-        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, and from the first ``peek`` on the
-        peek's scratch window, state copies and beam workspace)."""
+        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's, and from
+        the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0)
                 + (self._resampler.state_bytes if self._resampler is not None else 0)
-                + (self._endpoint.state_bytes if self._endpoint is not None else 0))
+                + (self._endpoint.state_bytes if self._endpoint is not None else 0)
+                + (self._keywords.state_bytes if self._keywords is not None else 0))
 
     @property
     def endpoint(self):
         """The ``ctc.EndpointResult`` of the logit frames returned so far in this utterance (device tensors, no synchronisation); None for
         a session made without ``endpoint=``.  Once ``endpoint_frame >= 0`` it stays until ``reset()``: committed frames never change."""
         return None if self._endpoint is None else self._endpoint.result
+
+    @property
+    def keywords(self):
+        """The ``ctc.KeywordResult`` of the logit frames returned so far in this utterance ((B, K) device tensors, no synchronisation);
+        None for a session made without ``keywords=``.  Once ``hit_frame >= 0`` the hit stays until ``reset()``; ``best_*`` go on improving."""
+        return None if self._keywords is None else self._keywords.result
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -484,6 +505,8 @@ class StreamingSession:
             self._resampler.reset()
         if self._endpoint is not None:
             self._endpoint.reset()
+        if self._keywords is not None:
+            self._keywords.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
@@ -602,6 +625,17 @@ class StreamingSession:
         logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
         return peeked, self._endpoint.peek(logits)
 
+    def peek_keywords(self, decode=False):
+        """``(peek(decode), KeywordResult)``: one peek of the model, then the spotter's peek over the provisional logits on top of its
+        committed state -- ``ctc.spot_keywords`` of the committed and the provisional frames together.  A peeked hit is PROVISIONAL:
+        the provisional frames are computed as if the audio stopped now and can change when more arrives, so a hit seen here can
+        disappear; a committed one (``keywords``) cannot.  The session and its spotter are left as they were."""
+        if self._keywords is None:
+            raise ValueError('peek_keywords needs a keyword set: StreamingSession(..., keywords=ctc.KeywordSet(...))')
+        peeked = self.peek(decode)
+        logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
+        return peeked, self._keywords.peek(logits)
+
     def _peek_record(self):
         """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
         builds: the scratch window (sized for the largest stage window) and, for a session that pushes the front-end's two end frames
@@ -662,6 +696,8 @@ class StreamingSession:
             result = (logits, self._greedy(self._carried, logits)) if decode else logits
         if self._endpoint is not None:           # after the decode launches; a step that emitted no frame launches nothing
             self._endpoint.push(logits)
+        if self._keywords is not None:           # after the decode and endpoint launches, on the same terms
+            self._keywords.push(logits)
         return result
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
