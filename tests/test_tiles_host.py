@@ -74,6 +74,39 @@ def test_variant_choices_are_the_recorded_ones(recorded, monkeypatch):
     assert len(set(want.values())) > 3                    # (the table's choices, the default kernel and the forced variant all occur)
 
 
+def test_every_tiling_the_planner_can_pick_is_exercised_on_the_gpu(monkeypatch):
+    """Closure: whatever ``dense_tile`` and ``bf16_tile`` (plain and pipelined) return for 1 ... 128 utterances of 40 ... 3000 frames through
+    the model's four convolutions is an instantiation that tests/test_dense_tilings_gpu.py runs element by element (dense_tilings.EXERCISED)
+    -- the fp16 image path, which always emits the statistics by-product, with it.  A tiling added to tiles.py fails here, without a
+    GPU, until a GPU test names it."""
+    import dense_tilings as dt
+    monkeypatch.delenv('NBASR_BF16_FTILE', raising=False)
+    picked = set()
+    for batch, frames in itertools.product(range(1, 129), range(40, 3001, 20)):
+        t = frames
+        for c_in, c_out, stride in CONVS:
+            t = (t + stride - 1) // stride                          # frames out of this convolution, into the next
+            picked.add((dt.F16_IMAGE, stride, *tiles.dense_tile(batch, c_in, c_out, stride, t)))
+            picked.add((dt.BF16, stride, *tiles.bf16_tile(batch, c_out, t)))
+            picked.add((dt.BF16, stride, *tiles.bf16_tile(batch, c_out, t, pipe=True)))
+    for scheme, stride, rows, frame_tile in sorted(picked):
+        assert (scheme, stride, rows, frame_tile, False) in dt.EXERCISED, (scheme, stride, rows, frame_tile)
+        if scheme == dt.F16_IMAGE:
+            assert (scheme, stride, rows, frame_tile, True) in dt.EXERCISED, (scheme, stride, rows, frame_tile, 'statistics')
+    # the enumeration is not vacuous: it reaches the 512-frame bf16 tiles at both strides and row tiles, and 128-frame fp16 tiles
+    bf16 = {p[1:] for p in picked if p[0] == dt.BF16}
+    f16 = {p[1:] for p in picked if p[0] == dt.F16_IMAGE}
+    assert {(s, rows, 512) for s in (1, 2) for rows in (128, 160)} <= bf16
+    assert any(ft == 128 for _, _, ft in f16) and {rows for _, rows, _ in f16} == set(dt.F16_IMAGE_ROWS)
+    # every GPU case is drawn from EXERCISED, and every EXERCISED entry has a case at its stride
+    assert {(dt.BF16, shape[3], rows, ft, False) for shape, rows in dt.bf16_cases() for r, ft in dt.tilings(dt.BF16, shape[3], False) if r == rows} \
+        == {e for e in dt.EXERCISED if e[0] == dt.BF16}
+    assert {(dt.F16_IMAGE, shape[3], rows, ft, True) for shape, rows, ft in dt.stats_cases()} == {e for e in dt.EXERCISED if e[0] == dt.F16_IMAGE and e[4]}
+    ran = {(scheme, shape[3], *tile, True) for shape, route in dt.route_cases() for scheme, tile in dt.ROUTES[route]}
+    assert {e for e in dt.EXERCISED if e[0] in (dt.F16_SPLIT, dt.BF16X3) and e[4]} <= ran <= dt.EXERCISED
+    assert len(dt.route_cases()) == len(dt.ROUTE_SHAPES) * len(dt.ROUTES)
+
+
 def test_dense_tile_rule_and_measured_table():
     """The whole-rounds model at 2, 8 and 64 utterances, and the measured table (dense_tile_table.json) that overrules it where it knows the
     shape (round 5): 128-frame tiles for the stride-2 convs of a small batch, 64-row tiles (two workgroups per CU) for conv 0; shapes it does
