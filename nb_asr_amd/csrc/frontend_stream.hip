@@ -18,7 +18,7 @@
 // The matrices arrive as operand images in the order the lanes read them (16 bytes per lane, 1 KB per wave and k block):
 //   dft image   [13 bin tiles][cos | sin][25 k blocks][64 lanes][4]: lane l, element s = row 16 tile + (l & 15), k = 16 kb + 4 s + (l >> 4)
 //   fbank image [5 mel tiles][13 k blocks][64 lanes][4]            : the same map over the (80, 208) filterbank
-#include "common.h"
+#include "sample_tail.h"
 
 namespace nbasr {
 namespace {
@@ -31,16 +31,6 @@ constexpr int kFrameLd = 17;                     // LDS pitch of frames[k][.]: t
 constexpr int kTailLd = (kWin + 1 + 3) / 4 * 4;  // 404 floats per utterance and tail
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct Samples {                                 // the stream's samples [tail_first, tail_first + tail_len + n_new) of one utterance
-    const float* tail; const float* wave; long long tail_first; int tail_len; int n_new;
-    __device__ __forceinline__ float at(long long i) const {
-        const long long r = i - tail_first;
-        if (r < 0) return 0.f;                   // (the host refuses a step that would need such a sample)
-        if (r < tail_len) return tail[r];
-        return r - tail_len < n_new ? wave[r - tail_len] : 0.f;
-    }
-};
 
 __global__ __launch_bounds__(kThreads) void frontend_stream_kernel(
     const float* __restrict__ tail_in, int tail_len, long long tail_first, const float* __restrict__ wave, int n_new, int ld_wave,
@@ -139,19 +129,17 @@ extern "C" int nbasr_frontend_stream_step(const float* tail_in, int tail_len, lo
                                           long long total_len, int final, int batch, int win, int hop, int bins, int n_mels,
                                           nbasr_stream_t stream)
 {
+    static const char* who = "nbasr_frontend_stream_step";
     clear_error();
     NBASR_REQUIRE(win == kWin && hop == kHop && bins == kBins && n_mels == kMels, NBASR_EINVAL,
                   "nbasr_frontend_stream_step: unsupported geometry win=%d hop=%d bins=%d n_mels=%d (built for %d / %d / %d / %d)", win, hop, bins,
                   n_mels, kWin, kHop, kBins, kMels);
-    NBASR_REQUIRE(batch >= 0 && tail_len >= 0 && tail_len <= kTailLd && tail_first >= 0 && n_new >= 0 && ld_wave >= n_new && first_frame >= 0 &&
-                  n_frames >= 0 && col0 >= 0, NBASR_EINVAL, "nbasr_frontend_stream_step: bad sizes");
-    NBASR_REQUIRE(total_len == tail_first + tail_len + n_new, NBASR_EINVAL,
-                  "nbasr_frontend_stream_step: total_len=%lld is not tail_first + tail_len + n_new = %lld", total_len, tail_first + tail_len + n_new);
+    if (const int rc = tail_step_sizes(who, kTailLd, batch, tail_len, tail_first, n_new, ld_wave, first_frame >= 0 && n_frames >= 0 && col0 >= 0,
+                                       total_len)) return rc;
     NBASR_REQUIRE(!final || total_len > win / 2, NBASR_EINVAL, "nbasr_frontend_stream_step: reflect padding needs more than %d samples", win / 2);
     const bool retain = !final && tail_out != nullptr;      // (tail_out == NULL: a step that emits some frames of a push and leaves the tail alone)
     if (batch == 0 || (n_frames == 0 && (n_new == 0 || !retain))) return NBASR_OK;
-    NBASR_REQUIRE(batch <= 65535, NBASR_EINVAL, "nbasr_frontend_stream_step: batch %d > 65535", batch);
-    NBASR_REQUIRE((tail_in || tail_len == 0) && (wave || n_new == 0), NBASR_ENULL, "nbasr_frontend_stream_step: NULL sample pointer");
+    if (const int rc = tail_step_pointers(who, batch, tail_in, tail_len, wave, n_new)) return rc;
     if (n_frames > 0) {
         NBASR_REQUIRE(dft && fbank && mean && inv_scale && feats, NBASR_ENULL, "nbasr_frontend_stream_step: NULL pointer");
         NBASR_REQUIRE(ld_feats % 4 == 0 && aligned16(dft) && aligned16(fbank), NBASR_EALIGN,
@@ -172,16 +160,12 @@ extern "C" int nbasr_frontend_stream_step(const float* tail_in, int tail_len, lo
                       "nbasr_frontend_stream_step: frames %d..%lld need samples %lld..%lld, the stream holds %lld..%lld", first_frame,
                       static_cast<long long>(first_frame) + n_frames - 1, lo, top, tail_first, total_len - 1);
     }
-    if (retain) {
-        NBASR_REQUIRE(aligned16(tail_out), NBASR_EALIGN, "nbasr_frontend_stream_step: tail_out must be 16-byte aligned");
-        NBASR_REQUIRE(tail_out != tail_in, NBASR_EINVAL, "nbasr_frontend_stream_step: tail_out must not be tail_in (two tails, used in turn)");
-        NBASR_REQUIRE(tail_out_first_rel >= 0 && tail_out_first_rel <= tail_len + n_new && tail_len + n_new - tail_out_first_rel <= kTailLd,
-                      NBASR_EINVAL, "nbasr_frontend_stream_step: retaining %d samples, a tail holds %d", tail_len + n_new - tail_out_first_rel, kTailLd);
-    }
+    if (retain)
+        if (const int rc = tail_step_retain(who, kTailLd, tail_in, tail_len, n_new, tail_out, tail_out_first_rel)) return rc;
     const int n_tiles = (n_frames + kTile - 1) / kTile;
     hipLaunchKernelGGL(frontend_stream_kernel, dim3(n_tiles + (retain ? 1 : 0), batch), dim3(kThreads), 0, as_stream(stream), tail_in, tail_len,
                        tail_first, wave, n_new, ld_wave, tail_out, tail_out_first_rel, reinterpret_cast<const float4*>(dft),
                        reinterpret_cast<const float4*>(fbank), mean, inv_scale, feats, ld_feats, col0, first_frame, n_frames, total_len, final,
                        n_tiles);
-    return launch_status("nbasr_frontend_stream_step");
+    return launch_status(who);
 }

@@ -9,14 +9,14 @@
 //
 // One thread computes one output sample: a single accumulator, its taps in ascending m, fmaf -- so an output's bits are a function of
 // the utterance's samples alone, whatever the push sizes, the sample's place in the launch or the batch.  A stream's samples are read
-// by absolute index from the retained tail or this push's samples (the Samples::at of frontend_stream.hip); the host decides which
+// by absolute index from the retained tail or this push's samples (the Samples::at of sample_tail.h); the host decides which
 // outputs a step computes (frontend.py: resample_final / resample_total / resample_retain_from) and the step refuses outputs whose
 // samples the stream does not hold.  One more workgroup per utterance copies what the next push needs into the OTHER tail.
 //
 // The phase table lives in LDS when n <= 256 phases (a workgroup of 256 consecutive outputs then reads every row 256 / n times;
 // the odd pitch spreads consecutive phases over the banks) and fits 32 KB; with more phases than threads no row is read twice by a
 // workgroup, and the rows are read from global memory (the whole table is at most 200 KB and stays in the caches).
-#include "common.h"
+#include "sample_tail.h"
 
 namespace nbasr {
 namespace {
@@ -58,16 +58,6 @@ int geometry(const char* who, int orig_freq, int new_freq, Geometry* g)
     g->pitch = g->taps | 1;
     return NBASR_OK;
 }
-
-struct Samples {                                 // the stream's samples [tail_first, tail_first + tail_len + n_new) of one utterance
-    const float* tail; const float* wave; long long tail_first; int tail_len; int n_new;
-    __device__ __forceinline__ float at(long long i) const {
-        const long long r = i - tail_first;
-        if (r < 0) return 0.f;                   // (the host refuses a step that would need such a sample)
-        if (r < tail_len) return tail[r];
-        return r - tail_len < n_new ? wave[r - tail_len] : 0.f;
-    }
-};
 
 // outputs first_out .. first_out + n_out - 1 of every utterance, first_out = k0 n + p0 (0 <= p0 < n); lengths (or NULL): utterance b
 // has lengths[b] samples -- it reads nothing at or beyond them, and outputs at or beyond ceil(n lengths[b] / o) are written as zero
@@ -158,14 +148,11 @@ extern "C" int nbasr_resample_stream_step(const float* tail_in, int tail_len, lo
     if (const int rc = geometry(who, orig_freq, new_freq, &g)) return rc;
     NBASR_REQUIRE(tail_capacity > 0, NBASR_EINVAL, "%s: tail_capacity=%d must be positive", who, tail_capacity);
     const int tail_ld = (tail_capacity + 3) / 4 * 4;
-    NBASR_REQUIRE(batch >= 0 && tail_len >= 0 && tail_len <= tail_ld && tail_first >= 0 && n_new >= 0 && ld_wave >= n_new && first_out >= 0 &&
-                  n_out >= 0 && col0 >= 0, NBASR_EINVAL, "%s: bad sizes", who);
-    NBASR_REQUIRE(total_len == tail_first + tail_len + n_new, NBASR_EINVAL, "%s: total_len=%lld is not tail_first + tail_len + n_new = %lld", who,
-                  total_len, tail_first + tail_len + n_new);
+    if (const int rc = tail_step_sizes(who, tail_ld, batch, tail_len, tail_first, n_new, ld_wave, first_out >= 0 && n_out >= 0 && col0 >= 0,
+                                       total_len)) return rc;
     const bool retain = !final && tail_out != nullptr;
     if (batch == 0 || (n_out == 0 && (n_new == 0 || !retain))) return NBASR_OK;
-    NBASR_REQUIRE(batch <= 65535, NBASR_EINVAL, "%s: batch %d > 65535", who, batch);
-    NBASR_REQUIRE((tail_in || tail_len == 0) && (wave || n_new == 0), NBASR_ENULL, "%s: NULL sample pointer", who);
+    if (const int rc = tail_step_pointers(who, batch, tail_in, tail_len, wave, n_new)) return rc;
     if (n_out > 0) {
         NBASR_REQUIRE(table && out, NBASR_ENULL, "%s: NULL pointer", who);
         NBASR_REQUIRE(col0 + static_cast<long long>(n_out) <= ld_out, NBASR_EINVAL, "%s: columns %d..%lld do not fit ld_out=%d", who, col0,
@@ -182,12 +169,8 @@ extern "C" int nbasr_resample_stream_step(const float* tail_in, int tail_len, lo
         NBASR_REQUIRE(lo >= tail_first && top < total_len, NBASR_EINVAL, "%s: outputs %lld..%lld need samples %lld..%lld, the stream holds %lld..%lld",
                       who, first_out, last_out, lo, top, tail_first, total_len - 1);
     }
-    if (retain) {
-        NBASR_REQUIRE(aligned16(tail_out), NBASR_EALIGN, "%s: tail_out must be 16-byte aligned", who);
-        NBASR_REQUIRE(tail_out != tail_in, NBASR_EINVAL, "%s: tail_out must not be tail_in (two tails, used in turn)", who);
-        NBASR_REQUIRE(tail_out_first_rel >= 0 && tail_out_first_rel <= tail_len + n_new && tail_len + n_new - tail_out_first_rel <= tail_ld,
-                      NBASR_EINVAL, "%s: retaining %d samples, a tail holds %d", who, tail_len + n_new - tail_out_first_rel, tail_ld);
-    }
+    if (retain)
+        if (const int rc = tail_step_retain(who, tail_ld, tail_in, tail_len, n_new, tail_out, tail_out_first_rel)) return rc;
     return launch(who, g, tail_in, tail_len, tail_first, tail_ld, wave, n_new, ld_wave, tail_out, tail_out_first_rel, table, out, ld_out, col0,
                   first_out, n_out, total_len, nullptr, batch, retain, stream);
 }

@@ -141,6 +141,29 @@ def _cut_rows(host, at, n_c, counts):
             [host[i, at + n_c: at + n_c + int(counts[1, i])].clone() for i in batch])
 
 
+def _positive(batch):
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f'batch must be positive (got {batch})')
+    return batch
+
+
+def _chunk_rows(lengths, n, batch, ended):
+    """Each utterance's frames in a chunk of ``n`` frames, as every stream over the logits admits them: int64 (B) on the host from
+    ``lengths`` (None: all ``n``; a device tensor is read back).  ``ended``: bool (B), the utterances an earlier chunk gave fewer frames."""
+    if lengths is None:
+        rows = torch.full((batch,), n, dtype=torch.int64)
+    else:
+        rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
+        if rows.numel() != batch:
+            raise ValueError(f'expected {batch} lengths, got {rows.numel()}')
+        if bool(((rows < 0) | (rows > n)).any()):
+            raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
+    if bool((ended & (rows > 0)).any()):
+        raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
+    return rows
+
+
 class BeamSearchStream:
     """``beam_decode`` fed chunk by chunk, with committed partial results (nbasr_ctc_beam_stream_*; DESIGN.md §9 "Beam decode").
 
@@ -166,9 +189,7 @@ class BeamSearchStream:
 
     def __init__(self, batch, beam_width=12, blank=0, cutoff_top_n=40, device=None, pool_nodes=None, timesteps=False, *, lm=None, alpha=1.0,
                  beta=0.0):
-        batch, beam_width = int(batch), int(beam_width)
-        if batch < 1:
-            raise ValueError(f'batch must be positive (got {batch})')
+        batch, beam_width = _positive(batch), int(beam_width)
         if not 1 <= beam_width <= 32:
             raise ValueError(f'beam_width must be in [1, 32] (got {beam_width})')
         self.batch, self.beam_width, self.blank, self.cutoff_top_n = batch, beam_width, int(blank), int(cutoff_top_n)
@@ -229,17 +250,7 @@ class BeamSearchStream:
         n, c = log_probs.shape[1], log_probs.shape[2]
         if self.classes is not None and c != self.classes and (n or empty_has_classes):
             raise ValueError(f'every chunk must have {self.classes} classes (got {c})')
-        if lengths is None:
-            rows = torch.full((self.batch,), n, dtype=torch.int64)
-        else:
-            rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
-            if rows.numel() != self.batch:
-                raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
-            if bool(((rows < 0) | (rows > n)).any()):
-                raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
-        if bool((self.ended & (rows > 0)).any()):
-            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
-        return n, c, rows
+        return n, c, _chunk_rows(lengths, n, self.batch, self.ended)
 
     def push(self, log_probs, lengths=None):
         """Decode the next chunk of log-probabilities (B, n, C) float32 on the device.  Returns ``(committed, partial)``, with
@@ -346,6 +357,112 @@ def empty_beam_result(batch, beam_width, device, timesteps=False):
     return hip.beam_result(none, scores.to(device), none.clone() if timesteps else None, lens)
 
 
+# ---- detectors over the logits: what the endpointer and the keyword spotter share (DESIGN.md §9 "Endpoint", "Keywords") ----------------
+class _DeviceTables:
+    """What a detector decides with (``EndpointRules``, ``KeywordSet``) owns its device tables, ``_build(device)``'s, made once.
+    ``OWNER`` / ``THINGS``: the nouns of the refusals ('the endpointer' / 'the rules')."""
+
+    def _set_device(self, device):
+        self.device = None if device is None else torch.device(device)
+        if self.device is not None and self.device.type != 'cuda':
+            raise ValueError(f'{self.OWNER} runs on a HIP device (got {self.device}); this package has no CPU path')
+        self._built = None
+
+    def _on(self, device):
+        if self.device is not None and self.device.index is not None and self.device != device:
+            raise ValueError(f'{self.THINGS} live on {self.device}, not on {device}')
+        if self._built is None:
+            self.device, self._built = device, self._build(device)
+        return self._built
+
+    def _here(self):
+        own = self.device is not None and self.device.index is not None
+        return self._on(self.device if own else torch.device('cuda', torch.cuda.current_device()))
+
+
+def _logit_chunk(x, classes, owner, batch=None):
+    """Is ``x`` a chunk a detector can step over -- (``batch`` or any B, frames, ``classes``) float32 on a HIP device?  -> ``x``, contiguous.
+    ``owner``: who wants ``classes`` classes ('the rules' / 'the keywords')."""
+    shape = x.shape if isinstance(x, torch.Tensor) else ()
+    if len(shape) != 3 or (batch is not None and shape[0] != batch):
+        raise ValueError(f'expected ({"batch" if batch is None else batch}, frames, classes) logits or log-probabilities, got '
+                         f'{tuple(getattr(x, "shape", ()))}')
+    if shape[2] != classes:
+        raise ValueError(f'{owner} are for {classes} classes, x has {shape[2]}')
+    if x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f'x must be float32 on a HIP device (got {x.dtype} on {x.device}); this package has no CPU path')
+    return x.contiguous()
+
+
+class _LogitDetectorStream:
+    """A detector fed the logits chunk by chunk: the push / peek / reset contract of ``EndpointStream`` and ``KeywordStream``.
+
+    The state is one int32 record per batch, three times: ``state``, the committed one; ``_fresh_state``, constant, what ``result``
+    shows until the first frame; ``_peek_state``, which the first peek allocates and every peek overwrites.  ``reset()`` launches
+    nothing: the next step is handed no input state (``state_in == NULL``) and starts from fresh rows.  A subclass gives ``RESULT``
+    (the class that reads a record), ``_fresh_rows()`` (the fresh record on the host; its shape is the record's) and ``_step(x,
+    chunk_lengths, state_out)``, one launch from ``None if self._fresh else self.state``; it has checked ``spec``, its rules or keywords."""
+
+    def __init__(self, batch, spec, device):
+        device = torch.device(spec.device if device is None and spec.device is not None else 'cuda' if device is None else device)
+        if device.type != 'cuda':
+            raise ValueError(f'{spec.OWNER} runs on a HIP device (got {device}); this package has no CPU path')
+        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+        self.batch, self._tables, self._classes, self._things = batch, spec._on(self.device), spec.classes, spec.THINGS
+        self._fresh_state = self._fresh_rows().to(self.device)        # never written
+        self.state = torch.empty_like(self._fresh_state)
+        self._peek_state = None
+        self.reset()
+
+    @property
+    def state_bytes(self):
+        """Device bytes of the state: the committed record, the constant fresh one, and the peek record once it exists."""
+        return sum(t.numel() * t.element_size() for t in (self.state, self._fresh_state, self._peek_state) if t is not None)
+
+    def reset(self):
+        """Start a new batch of utterances.  No launch: the next step starts from fresh rows."""
+        self._fresh = True
+        self.ended = torch.zeros(self.batch, dtype=torch.bool)
+
+    @property
+    def result(self):
+        """The result (``RESULT``) of the frames committed so far."""
+        return self.RESULT(self._fresh_state if self._fresh else self.state)
+
+    def _chunk(self, x, lengths):
+        x = _logit_chunk(x, self._classes, self._things, self.batch)
+        if x.device != self.device:
+            raise ValueError(f'x must be on {self.device} (got {x.device})')
+        n = x.shape[1]
+        if lengths is None:
+            return x, n, None, None
+        rows = _chunk_rows(lengths, n, self.batch, self.ended)
+        return x, n, rows, rows.to(device=self.device, dtype=torch.int32)
+
+    def push(self, x, lengths=None):
+        """Take the next chunk (B, n, C) of logits or log-probabilities; returns the result of everything pushed."""
+        x, n, rows, chunk_lengths = self._chunk(x, lengths)
+        if n:
+            self._step(x, chunk_lengths, self.state)
+            self._fresh = False
+            if rows is not None:
+                self.ended |= rows < n
+        return self.result
+
+    def peek(self, x=None, lengths=None):
+        """The result ``push(x, lengths)`` would return, with the stream left as it was (the committed record is only read).  ``x`` None
+        or of no frames: ``result``, no launch."""
+        if x is None:
+            return self.result
+        x, n, _, chunk_lengths = self._chunk(x, lengths)
+        if not n:
+            return self.result
+        if self._peek_state is None:
+            self._peek_state = torch.empty_like(self.state)
+        self._step(x, chunk_lengths, self._peek_state)
+        return self.RESULT(self._peek_state)
+
+
 # ---- endpointing: when has an utterance ended? (nbasr.h "endpointing"; DESIGN.md §9 "Endpoint") ---------------------------------------
 NON_SPEECH_PHONEMES = ('sil', 'cl', 'vcl', 'epi')        # of the 48-set: silence, the two closures, the epenthetic silence
 MAX_ENDPOINT_RULES = 8
@@ -359,7 +476,7 @@ def default_speech_classes():
     return tuple(i for i, name in enumerate(vocab(48, inc_blank=True)) if i != 0 and name not in NON_SPEECH_PHONEMES)
 
 
-class EndpointRules:
+class EndpointRules(_DeviceTables):
     """What the endpointer decides with: the speech classes, the margin, and up to 8 rules ``(min_speech, min_trailing, min_frames)`` in
     output frames (40 ms each, ``FRAME_SECONDS``).  A frame is speech iff its largest value over ``speech_classes`` exceeds its largest
     value over the other classes by more than ``margin`` (logits and log-probabilities give the same answer); a rule holds at a frame
@@ -372,6 +489,8 @@ class EndpointRules:
     Validates as the C side does (``ValueError``): 2..128 classes, a speech set that is neither empty nor every class and names no
     class outside them, 1..8 rules of three non-negative int32 values, a margin that is a number >= 0.  Owns the device table of the
     rules, made once, by the first step that needs it (``device`` None: the current HIP device)."""
+
+    OWNER, THINGS = 'the endpointer', 'the rules'
 
     def __init__(self, rules=((0, 125, 0), (1, 25, 0), (0, 0, 500)), speech_classes=None, margin=0.0, classes=49, device=None):
         classes = int(classes)
@@ -404,10 +523,7 @@ class EndpointRules:
         self.speech_classes, self.margin, self.classes = tuple(speech), margin, classes
         word = sum(1 << c for c in speech)
         self.speech_lo, self.speech_hi = word & (2 ** 64 - 1), word >> 64
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != 'cuda':
-            raise ValueError(f'the endpointer runs on a HIP device (got {self.device}); this package has no CPU path')
-        self._table = None
+        self._set_device(device)
 
     @staticmethod
     def frames_for(seconds):
@@ -423,21 +539,17 @@ class EndpointRules:
         are the constructor's.  The defaults are the constructor's."""
         return cls(tuple(tuple(cls.frames_for(v) for v in rule) for rule in rules), **kwargs)
 
+    def _build(self, device):
+        return torch.tensor(self.rules, dtype=torch.int32).to(device).contiguous()
+
     def table_on(self, device):
         """The rules as an (n_rules, 3) int32 tensor on ``device``, made by the first call; a rule set lives on one device."""
-        if self.device is not None and self.device.index is not None and self.device != device:
-            raise ValueError(f'the rules live on {self.device}, not on {device}')
-        if self._table is None:
-            self.device = device
-            self._table = torch.tensor(self.rules, dtype=torch.int32).to(device).contiguous()
-        return self._table
+        return self._on(device)
 
     @property
     def table(self):
         """The device table (``device`` None or without an index: on the current HIP device)."""
-        if self.device is None or self.device.index is None:
-            return self.table_on(torch.device('cuda', torch.cuda.current_device()))
-        return self.table_on(self.device)
+        return self._here()
 
     def __repr__(self):
         return f'EndpointRules(rules={self.rules}, speech_classes={self.speech_classes}, margin={self.margin}, classes={self.classes})'
@@ -470,26 +582,15 @@ class EndpointResult:
         return 'EndpointResult(' + ', '.join(f'{name}={getattr(self, name).tolist()}' for name in self.FIELDS) + ')'
 
 
-def _endpoint_chunk(x, rules, batch=None):
-    if not isinstance(rules, EndpointRules):
-        raise ValueError(f'rules must be an EndpointRules (got {type(rules).__name__})')
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or (batch is not None and x.shape[0] != batch):
-        raise ValueError(f'expected ({"batch" if batch is None else batch}, frames, classes) logits or log-probabilities, got '
-                         f'{tuple(getattr(x, "shape", ()))}')
-    if x.shape[2] != rules.classes:
-        raise ValueError(f'the rules are for {rules.classes} classes, x has {x.shape[2]}')
-    if x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError(f'x must be float32 on a HIP device (got {x.dtype} on {x.device}); this package has no CPU path')
-    return x.contiguous()
-
-
 def endpoint(x, output_len=None, rules=None, return_mask=False):
     """Where do these utterances end?  ``x`` (B, T', C) float32 logits or log-probabilities on the device, ``output_len`` their valid
     frames (tensor, sequence or None), ``rules`` an ``EndpointRules`` (None: the defaults, 49 classes).  Returns an ``EndpointResult``
     -- with ``return_mask=True`` ``(result, mask)``, mask (B, T') uint8: 1 where the frame is speech, 0 beyond an utterance's length.
     A fresh state and one step of the kernel the streams run (nbasr_ctc_endpoint_step): the same bits as any chunking of the frames."""
     rules = EndpointRules() if rules is None else rules
-    x = _endpoint_chunk(x, rules)
+    if not isinstance(rules, EndpointRules):
+        raise ValueError(f'rules must be an EndpointRules (got {type(rules).__name__})')
+    x = _logit_chunk(x, rules.classes, rules.THINGS)
     b, n, _ = x.shape
     lengths = _lengths(output_len, b, x.device)
     state = torch.empty(b, hip.ENDPOINT_STATE_WORDS, dtype=torch.int32, device=x.device)
@@ -500,7 +601,7 @@ def endpoint(x, output_len=None, rules=None, return_mask=False):
     return (result, mask) if return_mask else result
 
 
-class EndpointStream:
+class EndpointStream(_LogitDetectorStream):
     """``endpoint`` fed chunk by chunk (nbasr_ctc_endpoint_step with a carried state; DESIGN.md §9 "Endpoint").
 
         ep = EndpointStream(batch, rules, device=dev)
@@ -508,86 +609,26 @@ class EndpointStream:
         r = ep.peek(next_chunk)                  # what push(next_chunk) would return; the stream stays as it was
         ep.result                                # the committed result; ep.reset() starts the next utterances
 
-    ``lengths`` (B) gives each utterance's frames in this chunk, as in ``BeamSearchStream.push``: fewer than the chunk has ends that
-    utterance, and it takes no frames after that (host values cost no synchronisation; a device tensor is read back).  A push of no
-    frames launches nothing.  ``peek`` writes to a second state record that the first peek allocates.  ``reset()`` launches nothing:
-    the next step is handed no input state (``state_in == NULL``) and starts from fresh rows, and until then ``result`` shows a
-    constant fresh record made with the stream."""
+    The push / peek / reset contract is ``_LogitDetectorStream``'s.  ``lengths`` (B) gives each utterance's frames in this chunk, as in
+    ``BeamSearchStream.push``: fewer than the chunk has ends that utterance, and it takes no frames after that (host values cost no
+    synchronisation; a device tensor is read back).  A push of no frames launches nothing, and neither does ``reset()``."""
+
+    RESULT = EndpointResult
 
     def __init__(self, batch, rules=None, device=None):
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError(f'batch must be positive (got {batch})')
+        batch = _positive(batch)
         rules = EndpointRules(device=device) if rules is None else rules
         if not isinstance(rules, EndpointRules):
             raise ValueError(f'rules must be an EndpointRules (got {type(rules).__name__})')
-        device = torch.device(rules.device if device is None and rules.device is not None else 'cuda' if device is None else device)
-        if device.type != 'cuda':
-            raise ValueError(f'the endpointer runs on a HIP device (got {device}); this package has no CPU path')
-        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
-        self.batch, self.rules, self._table = batch, rules, rules.table_on(self.device)
-        self.state = torch.empty(batch, hip.ENDPOINT_STATE_WORDS, dtype=torch.int32, device=self.device)
-        self._fresh_state = torch.tensor([[0, 0, -1, -1, -1, -1, 0, 0]] * batch, dtype=torch.int32).to(self.device)     # never written
-        self._peek_state = None
-        self.reset()
+        self.rules = rules
+        super().__init__(batch, rules, device)
 
-    @property
-    def state_bytes(self):
-        """Device bytes of the state: the committed record, the constant fresh one, and the peek record once it exists."""
-        return sum(t.numel() * t.element_size() for t in (self.state, self._fresh_state, self._peek_state) if t is not None)
-
-    def reset(self):
-        """Start a new batch of utterances.  No launch: the next step starts from fresh rows."""
-        self._fresh = True
-        self.ended = torch.zeros(self.batch, dtype=torch.bool)
-
-    @property
-    def result(self):
-        """The ``EndpointResult`` of the frames committed so far."""
-        return EndpointResult(self._fresh_state if self._fresh else self.state)
-
-    def _chunk(self, x, lengths):
-        x = _endpoint_chunk(x, self.rules, self.batch)
-        if x.device != self.device:
-            raise ValueError(f'x must be on {self.device} (got {x.device})')
-        n = x.shape[1]
-        if lengths is None:
-            return x, n, None, None
-        rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
-        if rows.numel() != self.batch:
-            raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
-        if bool(((rows < 0) | (rows > n)).any()):
-            raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
-        if bool((self.ended & (rows > 0)).any()):
-            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
-        return x, n, rows, rows.to(device=self.device, dtype=torch.int32)
+    def _fresh_rows(self):
+        return torch.tensor([[0, 0, -1, -1, -1, -1, 0, 0]] * self.batch, dtype=torch.int32)
 
     def _step(self, x, chunk_lengths, state_out):
         r = self.rules
-        hip.ctc_endpoint_step(x, chunk_lengths, None if self._fresh else self.state, state_out, self._table, r.speech_lo, r.speech_hi, r.margin)
-
-    def push(self, x, lengths=None):
-        """Take the next chunk (B, n, C) of logits or log-probabilities; returns the ``EndpointResult`` of everything pushed."""
-        x, n, rows, chunk_lengths = self._chunk(x, lengths)
-        if n:
-            self._step(x, chunk_lengths, self.state)
-            self._fresh = False
-            if rows is not None:
-                self.ended |= rows < n
-        return self.result
-
-    def peek(self, x=None, lengths=None):
-        """The result ``push(x, lengths)`` would return, with the stream left as it was (the committed record is only read).  ``x`` None
-        or of no frames: ``result``, no launch."""
-        if x is None:
-            return self.result
-        x, n, _, chunk_lengths = self._chunk(x, lengths)
-        if not n:
-            return self.result
-        if self._peek_state is None:
-            self._peek_state = torch.empty_like(self.state)
-        self._step(x, chunk_lengths, self._peek_state)
-        return EndpointResult(self._peek_state)
+        hip.ctc_endpoint_step(x, chunk_lengths, None if self._fresh else self.state, state_out, self._tables, r.speech_lo, r.speech_hi, r.margin)
 
 
 # ---- keywords: has this phrase just been said? (nbasr.h "keywords"; DESIGN.md §9 "Keywords") -------------------------------------------
@@ -596,7 +637,7 @@ MAX_KEYWORD_TOKENS = hip.KEYWORD_MAX_TOKENS
 _NEG_INF_BITS = -8388608         # float32 -inf as an int32
 
 
-class KeywordSet:
+class KeywordSet(_DeviceTables):
     """The phrases a spotter listens for: 1 to 64 keywords, each a sequence of 1 to 32 token ids in ``[0, classes)`` without the blank,
     and one threshold per keyword.  A keyword's score at a frame is the log-likelihood ratio between the best CTC path that spells it
     and ends at that frame (starting anywhere) and the unconstrained best path over the same frames: <= 0, and 0 exactly when the greedy
@@ -609,6 +650,8 @@ class KeywordSet:
     threshold that is positive, NaN or infinite, a device that is not a HIP device.  Owns the device tables (tokens (K, 32) int32 with -1
     past a keyword's end, token counts, thresholds), made once, by the first step that needs them (``device`` None: the current HIP
     device)."""
+
+    OWNER, THINGS = 'the keyword spotter', 'the keywords'
 
     def __init__(self, keywords, thresholds=None, per_token=1.0, classes=49, blank=0, device=None):
         classes, blank = int(classes), int(blank)
@@ -650,10 +693,7 @@ class KeywordSet:
         if not bool((torch.isfinite(thresholds) & (thresholds <= 0)).all()):
             raise ValueError(f'a threshold must be a finite number <= 0 (got {thresholds.tolist()})')
         self.keywords, self.thresholds, self.classes, self.blank = tuple(words), tuple(thresholds.tolist()), classes, blank
-        self.device = None if device is None else torch.device(device)
-        if self.device is not None and self.device.type != 'cuda':
-            raise ValueError(f'the keyword spotter runs on a HIP device (got {self.device}); this package has no CPU path')
-        self._tables = None
+        self._set_device(device)
 
     @classmethod
     def from_phonemes(cls, keywords, thresholds=None, per_token=1.0, device=None):
@@ -682,21 +722,17 @@ class KeywordSet:
         counts = torch.tensor([len(word) for word in self.keywords], dtype=torch.int32)
         return tokens, counts, torch.tensor(self.thresholds, dtype=torch.float32)
 
+    def _build(self, device):
+        return tuple(t.to(device).contiguous() for t in self.host_tables())
+
     def tables_on(self, device):
         """The three tables on ``device``, made by the first call; a keyword set lives on one device."""
-        if self.device is not None and self.device.index is not None and self.device != device:
-            raise ValueError(f'the keywords live on {self.device}, not on {device}')
-        if self._tables is None:
-            self.device = device
-            self._tables = tuple(t.to(device).contiguous() for t in self.host_tables())
-        return self._tables
+        return self._on(device)
 
     @property
     def tables(self):
         """The device tables (``device`` None or without an index: on the current HIP device)."""
-        if self.device is None or self.device.index is None:
-            return self.tables_on(torch.device('cuda', torch.cuda.current_device()))
-        return self.tables_on(self.device)
+        return self._here()
 
     def __repr__(self):
         return f'KeywordSet(keywords={self.keywords}, thresholds={self.thresholds}, classes={self.classes}, blank={self.blank})'
@@ -744,19 +780,6 @@ class KeywordResult:
         return 'KeywordResult(' + ', '.join(f'{name}={getattr(self, name).tolist()}' for name in self.FIELDS) + ')'
 
 
-def _keyword_chunk(x, keywords, batch=None):
-    if not isinstance(keywords, KeywordSet):
-        raise ValueError(f'keywords must be a KeywordSet (got {type(keywords).__name__})')
-    if not isinstance(x, torch.Tensor) or x.dim() != 3 or (batch is not None and x.shape[0] != batch):
-        raise ValueError(f'expected ({"batch" if batch is None else batch}, frames, classes) logits or log-probabilities, got '
-                         f'{tuple(getattr(x, "shape", ()))}')
-    if x.shape[2] != keywords.classes:
-        raise ValueError(f'the keywords are for {keywords.classes} classes, x has {x.shape[2]}')
-    if x.dtype != torch.float32 or not x.is_cuda:
-        raise ValueError(f'x must be float32 on a HIP device (got {x.dtype} on {x.device}); this package has no CPU path')
-    return x.contiguous()
-
-
 def _fresh_keyword_state(batch, n_keywords):
     """(B, K, 136) int32 on the host: the fresh rows of nbasr.h."""
     row = torch.full((hip.KEYWORD_STATE_WORDS,), -1, dtype=torch.int32)
@@ -774,7 +797,9 @@ def spot_keywords(x, output_len=None, keywords=None, return_trace=False):
     streams run (nbasr_ctc_keyword_step): the same bits as any chunking of the frames."""
     if keywords is None:
         raise ValueError('keywords must be a KeywordSet: there is no default phrase')
-    x = _keyword_chunk(x, keywords)
+    if not isinstance(keywords, KeywordSet):
+        raise ValueError(f'keywords must be a KeywordSet (got {type(keywords).__name__})')
+    x = _logit_chunk(x, keywords.classes, keywords.THINGS)
     b, n, _ = x.shape
     k = len(keywords)
     lengths = _lengths(output_len, b, x.device)
@@ -788,7 +813,7 @@ def spot_keywords(x, output_len=None, keywords=None, return_trace=False):
     return (result, scores, starts) if return_trace else result
 
 
-class KeywordStream:
+class KeywordStream(_LogitDetectorStream):
     """``spot_keywords`` fed chunk by chunk (nbasr_ctc_keyword_step with a carried state; DESIGN.md §9 "Keywords").
 
         kw = KeywordStream(batch, keywords, device=dev)
@@ -796,85 +821,23 @@ class KeywordStream:
         r = kw.peek(next_chunk)                  # what push(next_chunk) would return; the stream stays as it was
         kw.result                                # the committed result; kw.reset() starts the next utterances
 
-    The contract is ``EndpointStream``'s.  ``lengths`` (B) gives each utterance's frames in this chunk: fewer than the chunk has ends
-    that utterance, and it takes no frames after that (host values cost no synchronisation; a device tensor is read back).  A push of
-    no frames launches nothing.  ``peek`` writes to a second state record that the first peek allocates.  ``reset()`` launches nothing:
-    the next step is handed no input state (``state_in == NULL``) and starts from fresh rows, and until then ``result`` shows a
-    constant fresh record made with the stream."""
+    The contract is ``EndpointStream``'s: both are ``_LogitDetectorStream``s, and this class adds only its record and its launch."""
+
+    RESULT = KeywordResult
 
     def __init__(self, batch, keywords, device=None):
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError(f'batch must be positive (got {batch})')
+        batch = _positive(batch)
         if not isinstance(keywords, KeywordSet):
             raise ValueError(f'keywords must be a KeywordSet (got {type(keywords).__name__})')
-        device = torch.device(keywords.device if device is None and keywords.device is not None else 'cuda' if device is None else device)
-        if device.type != 'cuda':
-            raise ValueError(f'the keyword spotter runs on a HIP device (got {device}); this package has no CPU path')
-        self.device = device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
-        self.batch, self.keywords, self._tables = batch, keywords, keywords.tables_on(self.device)
-        self.state = torch.empty(batch, len(keywords), hip.KEYWORD_STATE_WORDS, dtype=torch.int32, device=self.device)
-        self._fresh_state = _fresh_keyword_state(batch, len(keywords)).to(self.device)      # never written
-        self._peek_state = None
-        self.reset()
+        self.keywords = keywords
+        super().__init__(batch, keywords, device)
 
-    @property
-    def state_bytes(self):
-        """Device bytes of the state: the committed record, the constant fresh one, and the peek record once it exists."""
-        return sum(t.numel() * t.element_size() for t in (self.state, self._fresh_state, self._peek_state) if t is not None)
-
-    def reset(self):
-        """Start a new batch of utterances.  No launch: the next step starts from fresh rows."""
-        self._fresh = True
-        self.ended = torch.zeros(self.batch, dtype=torch.bool)
-
-    @property
-    def result(self):
-        """The ``KeywordResult`` of the frames committed so far."""
-        return KeywordResult(self._fresh_state if self._fresh else self.state)
-
-    def _chunk(self, x, lengths):
-        x = _keyword_chunk(x, self.keywords, self.batch)
-        if x.device != self.device:
-            raise ValueError(f'x must be on {self.device} (got {x.device})')
-        n = x.shape[1]
-        if lengths is None:
-            return x, n, None, None
-        rows = torch.as_tensor(lengths).reshape(-1).to(torch.int64).cpu()
-        if rows.numel() != self.batch:
-            raise ValueError(f'expected {self.batch} lengths, got {rows.numel()}')
-        if bool(((rows < 0) | (rows > n)).any()):
-            raise ValueError(f'lengths must lie in [0, {n}] for a chunk of {n} frames (got {rows.tolist()})')
-        if bool((self.ended & (rows > 0)).any()):
-            raise ValueError('an utterance that has ended (a chunk with fewer frames than the others) cannot take more frames')
-        return x, n, rows, rows.to(device=self.device, dtype=torch.int32)
+    def _fresh_rows(self):
+        return _fresh_keyword_state(self.batch, len(self.keywords))
 
     def _step(self, x, chunk_lengths, state_out):
         tokens, counts, thresholds = self._tables
         hip.ctc_keyword_step(x, chunk_lengths, tokens, counts, thresholds, self.keywords.blank, None if self._fresh else self.state, state_out)
-
-    def push(self, x, lengths=None):
-        """Take the next chunk (B, n, C) of logits or log-probabilities; returns the ``KeywordResult`` of everything pushed."""
-        x, n, rows, chunk_lengths = self._chunk(x, lengths)
-        if n:
-            self._step(x, chunk_lengths, self.state)
-            self._fresh = False
-            if rows is not None:
-                self.ended |= rows < n
-        return self.result
-
-    def peek(self, x=None, lengths=None):
-        """The result ``push(x, lengths)`` would return, with the stream left as it was (the committed record is only read).  ``x`` None
-        or of no frames: ``result``, no launch."""
-        if x is None:
-            return self.result
-        x, n, _, chunk_lengths = self._chunk(x, lengths)
-        if not n:
-            return self.result
-        if self._peek_state is None:
-            self._peek_state = torch.empty_like(self.state)
-        self._step(x, chunk_lengths, self._peek_state)
-        return KeywordResult(self._peek_state)
 
 
 def error_rates(hyp, hyp_len, ref, ref_len, blank=0, table=None):

@@ -252,7 +252,58 @@ class LogMelFrontend:
         return mel[:, :, :t] if ld != t else mel
 
 
-class FrontendStream:
+class _SampleTailStream:
+    """A lockstep batch of waveform streams whose state is two sample tails, used in turn: what ``FrontendStream`` and
+    ``ResamplerStream`` share (csrc/sample_tail.h is the C side's half).  ``_tails[_turn]`` (batch, ``pitch`` rounded up to 4) holds
+    samples ``_tail_first`` .. ``_tail_first + _tail_len - 1`` of every utterance; ``samples_in`` counts what was pushed.  A step reads
+    that tail and the new samples; the step that ends a push copies what the next one needs into the OTHER tail, which becomes the
+    current one; the step that ends the utterance, a peek's included, retains nothing.  A subclass adds its output counter, the
+    launch, and which sample is the first that the next step still needs."""
+
+    def __init__(self, batch, device, pitch):
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError(f'batch must be positive (got {batch})')
+        self.batch, self.device = batch, device
+        self._tails = torch.zeros(2, batch, hip.round_up4(pitch), device=device)
+        self._tail = tuple(self._tails)           # the two tails as views made once: a step indexes a tuple, not a tensor
+        self.state_bytes = self._tails.numel() * self._tails.element_size()
+
+    def reset(self):
+        """Start the next batch of utterances; the tails are re-used."""
+        self.samples_in = self._tail_first = self._tail_len = self._turn = 0
+        self._flushed = False
+
+    def _admit(self, wave):
+        if self._flushed:
+            raise ValueError('push after flush: call reset() to start the next utterance')
+        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.batch:
+            raise ValueError(f'expected a ({self.batch}, samples) chunk, got {tuple(getattr(wave, "shape", ()))}')
+        if wave.dtype != torch.float32 or wave.device != self.device:
+            raise ValueError(f'the chunk must be float32 on {self.device} (got {wave.dtype} on {wave.device})')
+        wave, n = wave.detach(), wave.shape[1]
+        if n and (wave.stride(1) != 1 or (self.batch > 1 and wave.stride(0) < n)):
+            wave = wave.contiguous()
+        return wave
+
+    def _turns(self, n, commit, final):
+        """Where does a step of ``n`` new samples read, and where, if anywhere, does it retain?  -> (tail_in, tail_out or None).  An empty
+        push leaves the tail where it is: nothing to copy.  The subclass works out the first retained sample only for a step that
+        retains (``ResamplerStream``'s form of the rule; ``FrontendStream`` did so for an empty committed push as well, and never read
+        it: such a push completes no frame -- the push before it emitted every final one -- and launches nothing)."""
+        turn = self._turn
+        return self._tail[turn], (self._tail[turn ^ 1] if commit and not final and n else None)
+
+    def _retained(self, n, tail_out, new_first):
+        """Commit a step: its ``n`` samples are in, and the tail it wrote, if any, is the current one."""
+        self.samples_in += n
+        if tail_out is not None:
+            self._turn ^= 1
+            self._tail_first = new_first
+            self._tail_len = self.samples_in - new_first
+
+
+class FrontendStream(_SampleTailStream):
     """``LogMelFrontend`` push by push (``LogMelFrontend.stream``): one fused HIP launch per push, state carried in two sample tails.
 
         fs = frontend.stream(batch=B)
@@ -264,29 +315,22 @@ class FrontendStream:
 
     ``out=(tensor, col0)``: write the frames into columns ``col0`` .. of a caller's contiguous (B, 80, ld) float32 tensor (ld % 4 == 0)
     and return that view.  The batch is lockstep: every lane receives the same number of samples.  Apart from returned features all
-    memory is allocated here (``state_bytes``: the two tails of 404 samples per lane; the matrices belong to the front-end)."""
+    memory is allocated here (``state_bytes``: the two tails of 404 samples per lane; the matrices belong to the front-end).  The
+    tails and their turn-taking are ``_SampleTailStream``'s."""
 
     def __init__(self, frontend, batch):
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError(f'batch must be positive (got {batch})')
-        self.frontend, self.batch, self.device = frontend, batch, frontend.device
+        self.frontend = frontend
         self.hop, self.win = frontend.hop_length, frontend.n_fft
+        super().__init__(batch, frontend.device, self.win + 1)
         self.lookahead_samples = self.win // 2
         self._dft_image, self._fbank_image = frontend.stream_images()
-        self._tails = torch.zeros(2, batch, hip.round_up4(self.win + 1), device=self.device)
-        self.state_bytes = self._tails.numel() * self._tails.element_size()
-        assert self.state_bytes == hip.frontend_stream_state_bytes(batch, self.win)
+        assert self.state_bytes == hip.frontend_stream_state_bytes(self.batch, self.win)
         self.reset()
 
     def reset(self):
         """Start the next batch of utterances; the tails are re-used."""
-        self.samples_in = 0
+        super().reset()
         self.frames_out = 0
-        self._tail_first = 0
-        self._tail_len = 0
-        self._turn = 0
-        self._flushed = False
 
     # ---- public ----------------------------------------------------------------------------------------------------------------
     def push(self, wave_chunk, out=None):
@@ -339,18 +383,6 @@ class FrontendStream:
         return view
 
     # ---- one launch ------------------------------------------------------------------------------------------------------------
-    def _admit(self, wave):
-        if self._flushed:
-            raise ValueError('push after flush: call reset() to start the next utterance')
-        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.batch:
-            raise ValueError(f'expected a ({self.batch}, samples) chunk, got {tuple(getattr(wave, "shape", ()))}')
-        if wave.dtype != torch.float32 or wave.device != self.device:
-            raise ValueError(f'the chunk must be float32 on {self.device} (got {wave.dtype} on {wave.device})')
-        wave = wave.detach()
-        if wave.shape[1] and (wave.stride(1) != 1 or (self.batch > 1 and wave.stride(0) < wave.shape[1])):
-            wave = wave.contiguous()
-        return wave
-
     def _destination(self, out, m):
         """(tensor the launch writes, first column, the view of the m frames)."""
         fe = self.frontend
@@ -370,23 +402,15 @@ class FrontendStream:
         """Frames first .. first + m - 1 from the tail and ``wave``; ``commit``: the push / flush ends with this launch (retain, advance)."""
         fe = self.frontend
         n = 0 if wave is None else wave.shape[1]
-        tail_in, tail_out, rel = self._tails[self._turn], None, 0
-        new_first = self._tail_first
-        if commit and not final:
-            new_first = retain_from(first + m, self.hop, self.win)
-            rel = new_first - self._tail_first
-            if n:                                            # (an empty push leaves the tail where it is: nothing to copy)
-                tail_out = self._tails[self._turn ^ 1]
+        tail_in, tail_out = self._turns(n, commit, final)
+        new_first = self._tail_first if tail_out is None else retain_from(first + m, self.hop, self.win)
+        rel = new_first - self._tail_first
         if m or tail_out is not None:
             hip.frontend_stream_step(tail_in, self._tail_len, self._tail_first, wave if n else None, tail_out, rel, self._dft_image,
                                      self._fbank_image, fe.mean, fe.inv_scale, feats, col0, first, m, final, self.win, self.hop, fe.bins)
         if commit:
-            self.samples_in += n
             self.frames_out = first + m
-            if tail_out is not None:
-                self._turn ^= 1
-                self._tail_first = new_first
-                self._tail_len = self.samples_in - new_first
+            self._retained(n, tail_out, new_first)
 
 
 class Resampler:
@@ -443,7 +467,7 @@ class Resampler:
         return out, out_lengths
 
 
-class ResamplerStream:
+class ResamplerStream(_SampleTailStream):
     """``Resampler`` push by push (``Resampler.stream``): one HIP launch per push, state carried in two sample tails.
 
         rs = resampler.stream(batch=B)
@@ -453,30 +477,22 @@ class ResamplerStream:
         # rs.peek() at any point before: the outputs flush() would return then, the stream left as it was
         # torch.cat([*pushes, last], 1) is resampler(whole waveform)[0]; the bits do not depend on the chunking
 
-    ``FrontendStream``'s contract: the batch is lockstep, ``flush`` twice or ``push`` after ``flush`` raises.  ``state_bytes``: the two
-    tails of ``resampler.tail_capacity`` samples per lane (the table belongs to the resampler)."""
+    ``FrontendStream``'s contract (both are ``_SampleTailStream``s): the batch is lockstep, ``flush`` twice or ``push`` after ``flush``
+    raises.  ``state_bytes``: the two tails of ``resampler.tail_capacity`` samples per lane (the table belongs to the resampler)."""
 
     def __init__(self, resampler, batch):
-        batch = int(batch)
-        if batch < 1:
-            raise ValueError(f'batch must be positive (got {batch})')
-        self.resampler, self.batch, self.device = resampler, batch, resampler.device
+        super().__init__(batch, resampler.device, resampler.tail_capacity)
+        self.resampler = resampler
         self.o, self.n = resampler.o, resampler.n
         self.lookahead_samples = resampler.lookahead_samples
         self._table = resampler.table()
-        self._tails = torch.zeros(2, batch, hip.round_up4(resampler.tail_capacity), device=self.device)
-        self.state_bytes = self._tails.numel() * self._tails.element_size()
-        assert self.state_bytes == hip.resample_state_bytes(batch, resampler.tail_capacity)
+        assert self.state_bytes == hip.resample_state_bytes(self.batch, resampler.tail_capacity)
         self.reset()
 
     def reset(self):
         """Start the next batch of utterances; the tails are re-used."""
-        self.samples_in = 0
+        super().reset()
         self.samples_out = 0
-        self._tail_first = 0
-        self._tail_len = 0
-        self._turn = 0
-        self._flushed = False
 
     @property
     def pending(self):
@@ -503,37 +519,18 @@ class ResamplerStream:
             raise ValueError('peek after flush: call reset() to start the next utterance')
         return self._step(None, resample_total(self.samples_in, self.o, self.n) - self.samples_out, False, True)
 
-    def _admit(self, wave):
-        if self._flushed:
-            raise ValueError('push after flush: call reset() to start the next utterance')
-        if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != self.batch:
-            raise ValueError(f'expected a ({self.batch}, samples) chunk, got {tuple(getattr(wave, "shape", ()))}')
-        if wave.dtype != torch.float32 or wave.device != self.device:
-            raise ValueError(f'the chunk must be float32 on {self.device} (got {wave.dtype} on {wave.device})')
-        wave = wave.detach()
-        if wave.shape[1] and (wave.stride(1) != 1 or (self.batch > 1 and wave.stride(0) < wave.shape[1])):
-            wave = wave.contiguous()
-        return wave
-
     def _step(self, wave, m, commit, final):
         """Outputs samples_out .. samples_out + m - 1 from the tail and ``wave``; ``commit``: retain and advance."""
         r = self.resampler
         n = 0 if wave is None else wave.shape[1]
         out = torch.empty(self.batch, m, device=self.device)
-        tail_in, tail_out, rel = self._tails[self._turn], None, 0
-        new_first = self._tail_first
-        if commit and not final and n:                       # (an empty push leaves the tail where it is: nothing to copy)
-            new_first = resample_retain_from(self.samples_out + m, self.o, self.n)
-            rel = new_first - self._tail_first
-            tail_out = self._tails[self._turn ^ 1]
+        tail_in, tail_out = self._turns(n, commit, final)
+        new_first = self._tail_first if tail_out is None else resample_retain_from(self.samples_out + m, self.o, self.n)
+        rel = new_first - self._tail_first
         if m or tail_out is not None:
             hip.resample_stream_step(tail_in, self._tail_len, self._tail_first, wave if n else None, tail_out, rel, r.tail_capacity,
                                      self._table, r.orig_freq, r.new_freq, out, 0, self.samples_out, m, final)
         if commit:
-            self.samples_in += n
             self.samples_out += m
-            if tail_out is not None:
-                self._turn ^= 1
-                self._tail_first = new_first
-                self._tail_len = self.samples_in - new_first
+            self._retained(n, tail_out, new_first)
         return out

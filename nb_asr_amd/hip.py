@@ -888,22 +888,38 @@ def frontend_stream_state_bytes(batch, win):
     return int(load_library().nbasr_frontend_stream_state_bytes(batch, win))
 
 
+def _wave_rows(wave, b, device, who, check_dtype=True):
+    """(samples, row pitch) of a (b, samples) float32 chunk whose rows are contiguous and do not overlap.  ``check_dtype`` False: the
+    caller refuses another dtype itself, after this (``frontend_stream_step``, in its own order and words)."""
+    shape = wave.shape if isinstance(wave, torch.Tensor) else ()
+    if len(shape) != 2 or shape[0] != b or wave.device != device:
+        raise HipError(f'{who}: wave must be a ({b}, samples) tensor on {device}')
+    n = shape[1]
+    if not n:
+        return 0, 0
+    if check_dtype and wave.dtype != torch.float32:
+        raise HipError(f'{who}: wave must be float32 (got {wave.dtype})')
+    pitch = wave.stride(0)
+    if wave.stride(1) != 1 or (b > 1 and pitch < n):
+        raise HipError(f'{who}: the samples of an utterance must be contiguous, the utterances must not overlap')
+    return n, max(pitch, n)
+
+
+def _tail_pair(tail_in, tail_out, samples, who):
+    """The batch of a stream step's two tails: (B, round_up4(samples)) tensors, ``tail_out`` possibly None."""
+    b, tail_ld = tail_in.shape
+    if tail_ld != round_up4(samples) or (tail_out is not None and tuple(tail_out.shape) != (b, tail_ld)):
+        raise HipError(f'{who}: the tails must be ({b}, {round_up4(samples)}) tensors')
+    return b
+
+
 def frontend_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out_first_rel, dft_image, fbank_image, mean, inv_scale, feats,
                          col0, first_frame, n_frames, final, win, hop, bins):
     """One step of a front-end stream (nbasr.h: nbasr_frontend_stream_step).  ``tail_in`` / ``tail_out``: (B, round_up4(win + 1)) float32
     tails (``tail_out`` None: retain nothing); ``wave`` (B, n) float32 or None; ``feats`` (B, n_mels, ld) receives frames ``first_frame`` ..
     at columns ``col0`` .. (None when ``n_frames`` is 0).  Returns ``feats``."""
-    b, tail_ld = tail_in.shape
-    if tail_ld != round_up4(win + 1) or (tail_out is not None and tuple(tail_out.shape) != (b, tail_ld)):
-        raise HipError(f'frontend_stream_step: the tails must be ({b}, {round_up4(win + 1)}) tensors')
-    n_new = 0
-    if wave is not None:
-        if wave.dim() != 2 or wave.shape[0] != b or wave.device != tail_in.device:
-            raise HipError(f'frontend_stream_step: wave must be a ({b}, samples) tensor on {tail_in.device}')
-        n_new = wave.shape[1]
-        if n_new and (wave.stride(1) != 1 or (b > 1 and wave.stride(0) < n_new)):
-            raise HipError('frontend_stream_step: the samples of an utterance must be contiguous, the utterances must not overlap')
-    ld_wave = wave.stride(0) if n_new else 0
+    b = _tail_pair(tail_in, tail_out, win + 1, 'frontend_stream_step')
+    n_new, ld_wave = (0, 0) if wave is None else _wave_rows(wave, b, tail_in.device, 'frontend_stream_step', check_dtype=False)
     if n_new and wave.dtype != torch.float32:
         raise HipError(f'wave must be float32 (got {wave.dtype})')
     n_mels = mean.numel()
@@ -913,7 +929,7 @@ def frontend_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out
             raise HipError(f'frontend_stream_step: feats must be a ({b}, {n_mels}, ld) tensor on {tail_in.device}')
         ld_feats = feats.shape[2]
     _check(load_library().nbasr_frontend_stream_step(
-        _dev(tail_in, 'tail_in'), int(tail_len), int(tail_first), wave.data_ptr() if n_new else None, n_new, max(ld_wave, n_new),
+        _dev(tail_in, 'tail_in'), int(tail_len), int(tail_first), wave.data_ptr() if n_new else None, n_new, ld_wave,
         _opt(tail_out, 'tail_out'), int(tail_out_first_rel), _dev(dft_image, 'dft_image'), _dev(fbank_image, 'fbank_image'), _dev(mean, 'mean'),
         _dev(inv_scale, 'inv_scale'), _dev(feats, 'feats') if n_frames else None, ld_feats, int(col0), int(first_frame), int(n_frames),
         int(tail_first) + int(tail_len) + n_new, int(bool(final)), b, win, hop, bins, n_mels, _stream(tail_in)), 'nbasr_frontend_stream_step')
@@ -925,26 +941,12 @@ def resample_state_bytes(batch, tail_capacity):
     return int(load_library().nbasr_resample_state_bytes(batch, tail_capacity))
 
 
-def _wave_rows(wave, b, device, who):
-    """(samples, row pitch) of a (b, samples) float32 chunk whose rows are contiguous and do not overlap."""
-    if not isinstance(wave, torch.Tensor) or wave.dim() != 2 or wave.shape[0] != b or wave.device != device:
-        raise HipError(f'{who}: wave must be a ({b}, samples) tensor on {device}')
-    n = wave.shape[1]
-    if n and wave.dtype != torch.float32:
-        raise HipError(f'{who}: wave must be float32 (got {wave.dtype})')
-    if n and (wave.stride(1) != 1 or (b > 1 and wave.stride(0) < n)):
-        raise HipError(f'{who}: the samples of an utterance must be contiguous, the utterances must not overlap')
-    return n, (max(wave.stride(0), n) if n else 0)
-
-
 def resample_stream_step(tail_in, tail_len, tail_first, wave, tail_out, tail_out_first_rel, tail_capacity, table, orig_freq, new_freq, out,
                          col0, first_out, n_out, final):
     """One step of a resampler stream (nbasr.h: nbasr_resample_stream_step).  ``tail_in`` / ``tail_out``: (B, round_up4(tail_capacity))
     float32 tails (``tail_out`` None: retain nothing); ``wave`` (B, n) float32 or None; ``out`` (B, ld) receives outputs ``first_out`` ..
     at columns ``col0`` .. (None when ``n_out`` is 0).  Returns ``out``."""
-    b, tail_ld = tail_in.shape
-    if tail_ld != round_up4(tail_capacity) or (tail_out is not None and tuple(tail_out.shape) != (b, tail_ld)):
-        raise HipError(f'resample_stream_step: the tails must be ({b}, {round_up4(tail_capacity)}) tensors')
+    b = _tail_pair(tail_in, tail_out, tail_capacity, 'resample_stream_step')
     n_new, ld_wave = (0, 0) if wave is None else _wave_rows(wave, b, tail_in.device, 'resample_stream_step')
     ld_out = 0
     if n_out:
@@ -1315,22 +1317,31 @@ def _signed64(word):
     return word - (1 << 64) if word >> 63 else word
 
 
+def _detector_step_args(who, x, lengths, state_in, state_out, words, k=None):
+    """The checks the detector steps share: ``x`` (B, n, C) float32 on the device, ``state_out`` and (unless None) ``state_in``
+    contiguous int32 (B, words) or (B, k, words), ``lengths`` None or int32 (B).  -> (B, n, C)."""
+    _dev(x, 'x')
+    shape, dev = x.shape, x.device               # (read once: a step is host-bound)
+    if len(shape) != 3:
+        raise HipError(f'{who}: x must be (batch, frames, classes), got {tuple(shape)}')
+    b = shape[0]
+    record = (b, words) if k is None else (b, k, words)
+    _int_tensor(state_out, 'state_out', dev, record)
+    if state_in is not None:
+        _int_tensor(state_in, 'state_in', dev, record)
+    if lengths is not None:
+        _int_tensor(lengths, 'lengths', dev, (b,))
+    return shape
+
+
 def ctc_endpoint_step(x, lengths, state_in, state_out, rules, speech_lo, speech_hi, margin, mask_out=None):
     """One step of the endpointer (nbasr.h: nbasr_ctc_endpoint_step) over ``x`` (B, n, C) float32 logits or log-probabilities.
     ``lengths``: int32 device tensor (B) or None.  ``state_in`` / ``state_out``: (B, 8) int32 device tensors -- ``state_in`` None starts
     fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.  ``rules``: (n_rules, 3) int32 device
     table; ``speech_lo`` / ``speech_hi``: the class mask's two 64-bit words; ``mask_out``: (B, n) uint8 device tensor or None.
     Returns ``state_out``."""
-    _dev(x, 'x')
-    if x.dim() != 3:
-        raise HipError(f'ctc_endpoint_step: x must be (batch, frames, classes), got {tuple(x.shape)}')
-    b, n, c = x.shape
-    _int_tensor(state_out, 'state_out', x.device, (b, ENDPOINT_STATE_WORDS))
-    if state_in is not None:
-        _int_tensor(state_in, 'state_in', x.device, (b, ENDPOINT_STATE_WORDS))
+    b, n, c = _detector_step_args('ctc_endpoint_step', x, lengths, state_in, state_out, ENDPOINT_STATE_WORDS)
     _int_tensor(rules, 'rules', x.device, (rules.shape[0], 3))
-    if lengths is not None:
-        _int_tensor(lengths, 'lengths', x.device, (b,))
     if mask_out is not None and (mask_out.dtype != torch.uint8 or mask_out.device != x.device or tuple(mask_out.shape) != (b, n)
                                  or not mask_out.is_contiguous()):
         raise HipError(f'ctc_endpoint_step: mask_out must be a contiguous ({b}, {n}) uint8 tensor on {x.device}')
@@ -1357,21 +1368,13 @@ def ctc_keyword_step(x, lengths, tokens, token_counts, thresholds, blank, state_
     (K) int32; ``thresholds``: (K) float32.  ``state_in`` / ``state_out``: (B, K, 136) int32 device tensors -- ``state_in`` None starts
     fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.  ``scores_out`` / ``starts_out``:
     (B, K, n) float32 / int32 device tensors, both or neither.  Returns ``state_out``."""
-    _dev(x, 'x')
-    if x.dim() != 3:
-        raise HipError(f'ctc_keyword_step: x must be (batch, frames, classes), got {tuple(x.shape)}')
-    b, n, c = x.shape
-    _int_tensor(tokens, 'tokens', x.device, (tokens.shape[0], KEYWORD_MAX_TOKENS))
     k = tokens.shape[0]
+    b, n, c = _detector_step_args('ctc_keyword_step', x, lengths, state_in, state_out, KEYWORD_STATE_WORDS, k)
+    _int_tensor(tokens, 'tokens', x.device, (k, KEYWORD_MAX_TOKENS))
     _int_tensor(token_counts, 'token_counts', x.device, (k,))
     _dev(thresholds, 'thresholds')
     if thresholds.device != x.device or tuple(thresholds.shape) != (k,):
         raise HipError(f'ctc_keyword_step: thresholds must have shape ({k},) on {x.device}')
-    _int_tensor(state_out, 'state_out', x.device, (b, k, KEYWORD_STATE_WORDS))
-    if state_in is not None:
-        _int_tensor(state_in, 'state_in', x.device, (b, k, KEYWORD_STATE_WORDS))
-    if lengths is not None:
-        _int_tensor(lengths, 'lengths', x.device, (b,))
     if (scores_out is None) != (starts_out is None):
         raise HipError('ctc_keyword_step: the trace is scores_out and starts_out together: give both or neither')
     if scores_out is not None:

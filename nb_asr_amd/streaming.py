@@ -384,19 +384,20 @@ class StreamingSession:
                 self._resampler = resampler.stream(B)
                 self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
         self._pack()
-        self._endpoint = None
-        if endpoint is not None:
-            classes = model.model[self.specs[-1].layer].out_features
-            if endpoint.classes != classes:
-                raise ValueError(f'the endpoint rules are for {endpoint.classes} classes, the model has {classes}')
-            self._endpoint = EndpointStream(B, endpoint, dev)
-        self._keywords = None
-        if keywords is not None:
-            classes = model.model[self.specs[-1].layer].out_features
-            if keywords.classes != classes:
-                raise ValueError(f'the keywords are for {keywords.classes} classes, the model has {classes}')
-            self._keywords = KeywordStream(B, keywords, dev)
+        self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
+        self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
+        # what hears the logits of every step, in launch order (after the decode launches): a third detector is one more entry
+        self._listeners = [d for d in (self._endpoint, self._keywords) if d is not None]
         self.reset()
+
+    def _listener(self, stream, spec, what):
+        """The ``ctc`` detector stream of this session for ``spec`` (its rules or keywords; None: no such listener)."""
+        if spec is None:
+            return None
+        classes = self.model.model[self.specs[-1].layer].out_features
+        if spec.classes != classes:
+            raise ValueError(f'{what} are for {spec.classes} classes, the model has {classes}')
+        return stream(self.batch, spec, self.device)
 
     @staticmethod
     def resampler_for(frontend, input_rate, device):
@@ -475,8 +476,7 @@ class StreamingSession:
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0)
                 + (self._resampler.state_bytes if self._resampler is not None else 0)
-                + (self._endpoint.state_bytes if self._endpoint is not None else 0)
-                + (self._keywords.state_bytes if self._keywords is not None else 0))
+                + sum(d.state_bytes for d in self._listeners))
 
     @property
     def endpoint(self):
@@ -503,10 +503,8 @@ class StreamingSession:
             self._frontend.reset()
         if self._resampler is not None:
             self._resampler.reset()
-        if self._endpoint is not None:
-            self._endpoint.reset()
-        if self._keywords is not None:
-            self._keywords.reset()
+        for d in self._listeners:
+            d.reset()
 
     def push(self, chunk, decode=False):
         """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
@@ -619,22 +617,22 @@ class StreamingSession:
         committed state -- ``ctc.endpoint`` of the committed and the provisional frames together.  A peeked endpoint is PROVISIONAL:
         the provisional frames are computed as if the audio stopped now and can change when more arrives, so an endpoint seen here
         can disappear; a committed one (``endpoint``) cannot.  The session and its endpointer are left as they were."""
-        if self._endpoint is None:
-            raise ValueError('peek_endpoint needs endpoint rules: StreamingSession(..., endpoint=ctc.EndpointRules(...))')
-        peeked = self.peek(decode)
-        logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
-        return peeked, self._endpoint.peek(logits)
+        return self._peek_with(self._endpoint, 'peek_endpoint needs endpoint rules: StreamingSession(..., endpoint=ctc.EndpointRules(...))', decode)
 
     def peek_keywords(self, decode=False):
         """``(peek(decode), KeywordResult)``: one peek of the model, then the spotter's peek over the provisional logits on top of its
         committed state -- ``ctc.spot_keywords`` of the committed and the provisional frames together.  A peeked hit is PROVISIONAL:
         the provisional frames are computed as if the audio stopped now and can change when more arrives, so a hit seen here can
         disappear; a committed one (``keywords``) cannot.  The session and its spotter are left as they were."""
-        if self._keywords is None:
-            raise ValueError('peek_keywords needs a keyword set: StreamingSession(..., keywords=ctc.KeywordSet(...))')
+        return self._peek_with(self._keywords, 'peek_keywords needs a keyword set: StreamingSession(..., keywords=ctc.KeywordSet(...))', decode)
+
+    def _peek_with(self, listener, refusal, decode):
+        """``(peek(decode), the listener's peek over the provisional logits)``; ``refusal``: what a session without that listener says."""
+        if listener is None:
+            raise ValueError(refusal)
         peeked = self.peek(decode)
         logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
-        return peeked, self._keywords.peek(logits)
+        return peeked, listener.peek(logits)
 
     def _peek_record(self):
         """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
@@ -694,10 +692,8 @@ class StreamingSession:
             result = (logits, dec.finish()) if final else (logits,) + pushed
         else:
             result = (logits, self._greedy(self._carried, logits)) if decode else logits
-        if self._endpoint is not None:           # after the decode launches; a step that emitted no frame launches nothing
-            self._endpoint.push(logits)
-        if self._keywords is not None:           # after the decode and endpoint launches, on the same terms
-            self._keywords.push(logits)
+        for d in self._listeners:                # after the decode launches, endpoint before keywords; a step that emitted no frame launches nothing
+            d.push(logits)
         return result
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
