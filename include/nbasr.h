@@ -565,6 +565,38 @@ int nbasr_ctc_endpoint_step(const float* x, const int* lengths, const int* state
                             long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out, int batch, int frames, int classes,
                             nbasr_stream_t stream);
 
+/* ---- segmentation: where are the stretches of speech in this stream? (nb_asr_amd/ctc.py segment / SegmentStream; DESIGN.md 9 "Segments")
+ * No reference counterpart.  The speech decision of a frame is the endpointer's (steps 1 and 2 above, with the same x, lengths, speech
+ * set and margin); on it runs an automaton with hysteresis that re-arms: it opens and closes segments for as long as frames arrive and
+ * keeps the last `capacity` closed ones in a ring.  Integer-exact after the one float32 compare per frame, so whole = chunked = peeked =
+ * a row alone, bit for bit.
+ *   min_speech >= 1, min_silence >= 1, max_frames (0: none, else > min_speech): frame counts, passed by value;
+ *   capacity S in [1, 64]: the entries of a row's ring.
+ * State: one row of 8 + 4 S int32 per utterance (nbasr_ctc_segment_state_bytes = 4 (8 + 4 S) batch; 0 for a batch that is not positive
+ *   or a capacity outside [1, 64]): frames, speech_run, silence_run (consecutive speech / other frames ending at the last frame; one of
+ *   them is 0), open_start (-1: no segment is open), count (segments closed so far, in all), 0, 0, 0, then the ring: S entries
+ *   (start, end, reason, 0), a segment being the frames [start, end).  A fresh row is (0, 0, 0, -1, 0, 0, 0, 0) and S entries (-1, -1, -1, 0).
+ * Each frame of a row, with global index g = frames and speech decision s, in this order:
+ *   1. if s: speech_run += 1, silence_run = 0; otherwise silence_run += 1, speech_run = 0;
+ *   2. if no segment is open and s and speech_run >= min_speech: open_start = g - min_speech + 1;
+ *   3. else, if a segment is open and not s and silence_run >= min_silence: close it with end = g - silence_run + 1, reason = 0;
+ *   4. else, if a segment is open and max_frames != 0 and g + 1 - open_start >= max_frames: close it with end = g + 1, reason = 1, and
+ *      set both runs to 0;
+ *   5. frames += 1.
+ *   Closing writes (open_start, end, reason, 0) to ring[count % S], then count += 1 and open_start = -1.
+ * nbasr_ctc_segment_step: one launch over the frames of a chunk (or of whole utterances).
+ *   state_in == NULL: the rows start fresh.  state_out == state_in: the step is committed in place.  state_out != state_in: a peek --
+ *   state_in is only read and state_out receives what a commit would have left, the ring included.  frames == 0 succeeds and still
+ *   copies state_in (or fresh rows) to a different state_out.
+ *   mask_out(batch, frames) bytes or NULL: 1 where the frame is speech, 0 elsewhere and in the columns at or beyond a row's length.
+ *   Refused on the host before any device work: negative sizes, classes outside [2, 128], a margin that is negative or NaN, mask bits
+ *   at or above `classes`, an empty speech set or one of every class, min_speech or min_silence below 1, max_frames neither 0 nor above
+ *   min_speech, capacity outside [1, 64] (NBASR_EINVAL); x (with frames > 0) or state_out NULL (NBASR_ENULL). */
+size_t nbasr_ctc_segment_state_bytes(int batch, int capacity);
+int nbasr_ctc_segment_step(const float* x, const int* lengths, const int* state_in, int* state_out, int min_speech, int min_silence,
+                           int max_frames, int capacity, long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out,
+                           int batch, int frames, int classes, nbasr_stream_t stream);
+
 /* ---- keywords: has this phrase just been said? (nb_asr_amd/ctc.py spot_keywords / KeywordStream; DESIGN.md 9 "Keywords") -------------
  * No reference counterpart.  Per (utterance, keyword) and frame: the score of the best CTC path that spells the keyword, ends at this
  * frame and starts anywhere, as a log-likelihood ratio against the unconstrained best path over the same frames.  Every step is a float32

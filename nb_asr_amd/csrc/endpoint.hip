@@ -5,28 +5,23 @@
 // arithmetic, so whole = chunked = a row alone, to the bit.
 //
 // One wave64 per utterance, several waves per workgroup.  A wave takes its row's frames in passes of 64, one lane per frame:
-//   - the pass's 64 x C floats are contiguous in memory: the wave copies them coalesced into its LDS slab with an ODD lane stride (C | 1),
-//     so the 32 lanes of a ds_read_b32 group land on 32 different banks while each lane scans its own frame in ascending class order;
+//   - speech_pass (speech_frames.h, shared with segment.hip) copies the pass's 64 x C floats into the wave's LDS slab and decides each
+//     lane's frame;
 //   - __ballot of the speech decision gives the pass's 64-bit mask m.  With below = m & ((2 << lane) - 1), the frames up to and including
 //     the lane's own: speech_frames = carried + popcount(below); last_speech = g0 + (highest set bit of below), or the carried value;
 //   - each lane evaluates the rules on those values; a second __ballot and a find-first-set give the latching frame, a shuffle its rule;
 //   - the row's state lives in wave-uniform registers between passes and is written once, with ordinary stores.
 // Every wave of a workgroup runs the same number of passes (those of the launch's `frames`), so the two barriers of a pass are uniform;
 // lanes beyond a row's length load nothing -- the columns there may hold anything -- and write 0 to the mask.
-#include "common.h"
-
-#include <cmath>
+#include "speech_frames.h"
 
 namespace nbasr {
 namespace {
 
 constexpr int kStateWords = 8;                   // frames, speech_frames, first_speech, last_speech, endpoint_frame, endpoint_rule, 0, 0
 constexpr int kMaxRules = 8;
-constexpr int kMaxClasses = 128;
-constexpr int kMaxWaves = 4;                     // per workgroup
-constexpr int kLdsBytes = 65536;                 // a workgroup's slabs: waves * 64 * (C | 1) floats fit this
 
-__global__ __launch_bounds__(kMaxWaves * 64) void endpoint_kernel(
+__global__ __launch_bounds__(kSpeechMaxWaves * 64) void endpoint_kernel(
     const float* __restrict__ x, const int* __restrict__ lengths, const int* state_in, int* state_out, const int* __restrict__ rules,
     int n_rules, unsigned long long speech_lo, unsigned long long speech_hi, float margin, unsigned char* __restrict__ mask_out, int batch,
     int frames, int classes, int waves)
@@ -52,27 +47,7 @@ __global__ __launch_bounds__(kMaxWaves * 64) void endpoint_kernel(
 
     for (int f0 = 0; f0 < frames; f0 += 64) {
         const int nf = len - f0 < 0 ? 0 : (len - f0 > 64 ? 64 : len - f0);  // this pass's frames of the row
-        const float* src = xrow + static_cast<size_t>(f0) * classes;
-        int f = lane / classes, c = lane - f * classes;                     // element i = lane + 64 k of the pass is (frame f, class c)
-        const int df = 64 / classes, dc = 64 - df * classes;
-        for (int i = lane; i < nf * classes; i += 64) {
-            slab[f * stride + c] = src[i];
-            f += df; c += dc;
-            if (c >= classes) { c -= classes; ++f; }
-        }
-        __syncthreads();
-
-        bool speech = false;
-        if (lane < nf) {
-            const float* v = slab + lane * stride;
-            float ms = -INFINITY, mn = -INFINITY;                           // maxima over the speech classes and over the others
-            for (int k = 0; k < classes; ++k) {
-                const bool in_s = ((k < 64 ? speech_lo >> k : speech_hi >> (k - 64)) & 1ull) != 0;
-                const float val = v[k];
-                if (in_s) { if (val > ms) ms = val; } else { if (val > mn) mn = val; }     // (a NaN is never taken)
-            }
-            speech = ms > mn + margin;
-        }
+        const bool speech = speech_pass(xrow + static_cast<size_t>(f0) * classes, slab, nf, classes, speech_lo, speech_hi, margin, lane);
         const unsigned long long m = __ballot(speech);
         const unsigned long long below = m & ((2ull << lane) - 1ull);      // (lane 63: 2 << 63 wraps to 0, minus 1 = every bit)
         const int g = g0 + lane;
@@ -125,23 +100,13 @@ extern "C" int nbasr_ctc_endpoint_step(const float* x, const int* lengths, const
 {
     static const char* who = "nbasr_ctc_endpoint_step";
     clear_error();
-    NBASR_REQUIRE(batch >= 0 && frames >= 0, NBASR_EINVAL, "%s: negative sizes (batch=%d, frames=%d)", who, batch, frames);
-    NBASR_REQUIRE(classes >= 2 && classes <= kMaxClasses, NBASR_EINVAL, "%s: classes=%d must lie in [2, %d]", who, classes, kMaxClasses);
-    NBASR_REQUIRE(n_rules >= 1 && n_rules <= kMaxRules, NBASR_EINVAL, "%s: n_rules=%d must lie in [1, %d]", who, n_rules, kMaxRules);
-    NBASR_REQUIRE(margin >= 0.f, NBASR_EINVAL, "%s: margin must be a number >= 0", who);                  // (refuses NaN too)
     const unsigned long long lo = static_cast<unsigned long long>(speech_lo), hi = static_cast<unsigned long long>(speech_hi);
-    const unsigned long long all_lo = classes >= 64 ? ~0ull : (1ull << classes) - 1ull;
-    const unsigned long long all_hi = classes <= 64 ? 0ull : (classes == 128 ? ~0ull : (1ull << (classes - 64)) - 1ull);
-    NBASR_REQUIRE((lo & ~all_lo) == 0 && (hi & ~all_hi) == 0, NBASR_EINVAL, "%s: the speech mask names classes at or above classes=%d", who,
-                  classes);
-    NBASR_REQUIRE(lo != 0 || hi != 0, NBASR_EINVAL, "%s: the speech set is empty", who);
-    NBASR_REQUIRE(lo != all_lo || hi != all_hi, NBASR_EINVAL, "%s: the speech set is every class: no class is left for non-speech", who);
+    if (const int refused = check_speech_args(who, batch, frames, classes, margin, lo, hi)) return refused;
+    NBASR_REQUIRE(n_rules >= 1 && n_rules <= kMaxRules, NBASR_EINVAL, "%s: n_rules=%d must lie in [1, %d]", who, n_rules, kMaxRules);
     NBASR_REQUIRE(state_out && rules && (x || frames == 0 || batch == 0), NBASR_ENULL, "%s: NULL pointer (x, state_out and rules are required)",
                   who);
     if (batch == 0 || (frames == 0 && state_in == state_out)) return NBASR_OK;
-    const int slab_bytes = 64 * (classes | 1) * static_cast<int>(sizeof(float));
-    int waves = kLdsBytes / slab_bytes;
-    waves = waves > kMaxWaves ? kMaxWaves : waves;                       // (128 classes: 33 KB a slab, one wave a workgroup)
+    const int slab_bytes = speech_slab_bytes(classes), waves = speech_waves(classes);
     const int blocks = (batch + waves - 1) / waves;
     hipLaunchKernelGGL(endpoint_kernel, dim3(blocks), dim3(waves * 64), static_cast<size_t>(waves) * slab_bytes, as_stream(stream), x, lengths,
                        state_in, state_out, rules, n_rules, lo, hi, margin, mask_out, batch, frames, classes, waves);

@@ -8,8 +8,9 @@ third-party C++, not in the reference's tree), ``PhonemeEncoder.fold_encoded(., 
 ``fold_table`` (the 48 -> 39 label table, with the reference's relabelling order), ``error_rates`` (label table + blank
 removal + Levenshtein distance) and ``decode_per`` = the whole of ``Trainer.decode``.  ``greedy_decode`` is the cheap
 width-1 relative (per-frame argmax, collapse, drop blank).  Beside the decoders, with no reference counterpart: ``forced_align``
-(which frames belong to which phoneme), ``endpoint`` / ``EndpointStream`` (when has the utterance ended) and ``spot_keywords`` /
-``KeywordStream`` (has this phrase just been said).
+(which frames belong to which phoneme), ``endpoint`` / ``EndpointStream`` (when has the utterance ended), ``spot_keywords`` /
+``KeywordStream`` (has this phrase just been said) and ``segment`` / ``SegmentStream`` (where are the stretches of speech in a stream
+that goes on), with ``decode_spans`` to transcribe them.
 """
 import collections
 import inspect
@@ -357,10 +358,13 @@ def empty_beam_result(batch, beam_width, device, timesteps=False):
     return hip.beam_result(none, scores.to(device), none.clone() if timesteps else None, lens)
 
 
-# ---- detectors over the logits: what the endpointer and the keyword spotter share (DESIGN.md §9 "Endpoint", "Keywords") ----------------
+# ---- detectors over the logits: what the endpointer, the keyword spotter and the segmenter share ------------------------
 class _DeviceTables:
-    """What a detector decides with (``EndpointRules``, ``KeywordSet``) owns its device tables, ``_build(device)``'s, made once.
+    """What a detector decides with (``EndpointRules``, ``KeywordSet``, ``SegmentRules``) owns its device tables, ``_build(device)``'s,
+    made once.  A spec whose step takes everything by value leaves ``_build`` None: it has no tables, and ``_on`` gives None.
     ``OWNER`` / ``THINGS``: the nouns of the refusals ('the endpointer' / 'the rules')."""
+
+    _build = None
 
     def _set_device(self, device):
         self.device = None if device is None else torch.device(device)
@@ -371,6 +375,8 @@ class _DeviceTables:
     def _on(self, device):
         if self.device is not None and self.device.index is not None and self.device != device:
             raise ValueError(f'{self.THINGS} live on {self.device}, not on {device}')
+        if self._build is None:
+            return None
         if self._built is None:
             self.device, self._built = device, self._build(device)
         return self._built
@@ -395,7 +401,8 @@ def _logit_chunk(x, classes, owner, batch=None):
 
 
 class _LogitDetectorStream:
-    """A detector fed the logits chunk by chunk: the push / peek / reset contract of ``EndpointStream`` and ``KeywordStream``.
+    """A detector fed the logits chunk by chunk: the push / peek / reset contract of ``EndpointStream``, ``KeywordStream`` and
+    ``SegmentStream``.
 
     The state is one int32 record per batch, three times: ``state``, the committed one; ``_fresh_state``, constant, what ``result``
     shows until the first frame; ``_peek_state``, which the first peek allocates and every peek overwrites.  ``reset()`` launches
@@ -476,23 +483,11 @@ def default_speech_classes():
     return tuple(i for i, name in enumerate(vocab(48, inc_blank=True)) if i != 0 and name not in NON_SPEECH_PHONEMES)
 
 
-class EndpointRules(_DeviceTables):
-    """What the endpointer decides with: the speech classes, the margin, and up to 8 rules ``(min_speech, min_trailing, min_frames)`` in
-    output frames (40 ms each, ``FRAME_SECONDS``).  A frame is speech iff its largest value over ``speech_classes`` exceeds its largest
-    value over the other classes by more than ``margin`` (logits and log-probabilities give the same answer); a rule holds at a frame
-    when the utterance has at least ``min_speech`` speech frames, ``min_trailing`` frames since the last one (all frames, while there
-    is none) and ``min_frames`` frames in all; the first frame at which a rule holds is the endpoint, the lowest such rule its rule.
+class _SpeechDecision(_DeviceTables):
+    """The per-frame speech decision ``EndpointRules`` and ``SegmentRules`` share: ``classes``, the sorted ``speech_classes``, ``margin``
+    and the class mask's two 64-bit words ``speech_lo`` / ``speech_hi``, validated as the C side does (``ValueError``)."""
 
-    The defaults read: 5 s of silence with nothing said; 1 s of silence after speech; 20 s in all -- Kaldi's online-endpoint rules 1, 3
-    and 5 in 40 ms frames.  They are UNTUNED for this model: starting points, not recommendations.
-
-    Validates as the C side does (``ValueError``): 2..128 classes, a speech set that is neither empty nor every class and names no
-    class outside them, 1..8 rules of three non-negative int32 values, a margin that is a number >= 0.  Owns the device table of the
-    rules, made once, by the first step that needs it (``device`` None: the current HIP device)."""
-
-    OWNER, THINGS = 'the endpointer', 'the rules'
-
-    def __init__(self, rules=((0, 125, 0), (1, 25, 0), (0, 0, 500)), speech_classes=None, margin=0.0, classes=49, device=None):
+    def _set_speech(self, speech_classes, margin, classes):
         classes = int(classes)
         if not 2 <= classes <= MAX_ENDPOINT_CLASSES:
             raise ValueError(f'classes must lie in [2, {MAX_ENDPOINT_CLASSES}] (got {classes})')
@@ -510,19 +505,39 @@ class EndpointRules(_DeviceTables):
             raise ValueError(f'speech_classes must lie in [0, {classes}) (got {speech[0]}..{speech[-1]})')
         if len(speech) == classes:
             raise ValueError('speech_classes is every class: no class is left for non-speech')
+        margin = float(margin)
+        if not margin >= 0.0:
+            raise ValueError(f'margin must be a number >= 0 (got {margin})')
+        self.speech_classes, self.margin, self.classes = tuple(speech), margin, classes
+        word = sum(1 << c for c in speech)
+        self.speech_lo, self.speech_hi = word & (2 ** 64 - 1), word >> 64
+
+
+class EndpointRules(_SpeechDecision):
+    """What the endpointer decides with: the speech classes, the margin, and up to 8 rules ``(min_speech, min_trailing, min_frames)`` in
+    output frames (40 ms each, ``FRAME_SECONDS``).  A frame is speech iff its largest value over ``speech_classes`` exceeds its largest
+    value over the other classes by more than ``margin`` (logits and log-probabilities give the same answer); a rule holds at a frame
+    when the utterance has at least ``min_speech`` speech frames, ``min_trailing`` frames since the last one (all frames, while there
+    is none) and ``min_frames`` frames in all; the first frame at which a rule holds is the endpoint, the lowest such rule its rule.
+
+    The defaults read: 5 s of silence with nothing said; 1 s of silence after speech; 20 s in all -- Kaldi's online-endpoint rules 1, 3
+    and 5 in 40 ms frames.  They are UNTUNED for this model: starting points, not recommendations.
+
+    Validates as the C side does (``ValueError``): 2..128 classes, a speech set that is neither empty nor every class and names no
+    class outside them, 1..8 rules of three non-negative int32 values, a margin that is a number >= 0.  Owns the device table of the
+    rules, made once, by the first step that needs it (``device`` None: the current HIP device)."""
+
+    OWNER, THINGS = 'the endpointer', 'the rules'
+
+    def __init__(self, rules=((0, 125, 0), (1, 25, 0), (0, 0, 500)), speech_classes=None, margin=0.0, classes=49, device=None):
+        self._set_speech(speech_classes, margin, classes)
         rules = tuple(tuple(rule) for rule in rules)
         if not 1 <= len(rules) <= MAX_ENDPOINT_RULES:
             raise ValueError(f'there must be 1 to {MAX_ENDPOINT_RULES} rules (got {len(rules)})')
         for rule in rules:
             if len(rule) != 3 or any(isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 31 for v in rule):
                 raise ValueError(f'a rule is (min_speech, min_trailing, min_frames), non-negative int32 frame counts (got {rule})')
-        margin = float(margin)
-        if not margin >= 0.0:
-            raise ValueError(f'margin must be a number >= 0 (got {margin})')
         self.rules = tuple(tuple(int(v) for v in rule) for rule in rules)
-        self.speech_classes, self.margin, self.classes = tuple(speech), margin, classes
-        word = sum(1 << c for c in speech)
-        self.speech_lo, self.speech_hi = word & (2 ** 64 - 1), word >> 64
         self._set_device(device)
 
     @staticmethod
@@ -629,6 +644,217 @@ class EndpointStream(_LogitDetectorStream):
     def _step(self, x, chunk_lengths, state_out):
         r = self.rules
         hip.ctc_endpoint_step(x, chunk_lengths, None if self._fresh else self.state, state_out, self._tables, r.speech_lo, r.speech_hi, r.margin)
+
+
+# ---- segments: where are the stretches of speech in this stream? (nbasr.h "segmentation"; DESIGN.md §9 "Segments") --------------------
+MAX_SEGMENT_CAPACITY = hip.SEGMENT_MAX_CAPACITY
+
+
+class SegmentRules(_SpeechDecision):
+    """What the segmenter decides with: the endpointer's speech decision (``speech_classes``, ``margin``, ``classes``) and three counts
+    in output frames (40 ms each, ``FRAME_SECONDS``).  ``min_speech`` consecutive speech frames open a segment, at the first of them;
+    ``min_silence`` consecutive other frames close it, at the first of them (reason 0), so shorter pauses stay inside a segment;
+    a segment that reaches ``max_frames`` frames is closed there by force (reason 1) and the next one needs ``min_speech`` new speech
+    frames (0: no limit).  Unlike the endpoint, nothing latches: segments open and close for as long as frames arrive, and each row
+    keeps its last ``capacity`` closed segments in a ring on the device.
+
+    The defaults read: 120 ms of speech open a segment, half a second of silence closes it, no forced close, the last 16 segments.
+    They are UNTUNED for this model: starting points, not recommendations.
+
+    Validates as the C side does (``ValueError``): the speech decision as ``EndpointRules`` does; ``min_speech`` and ``min_silence``
+    int32 values >= 1; ``max_frames`` 0 or an int32 value above ``min_speech``; ``capacity`` in [1, 64].  The counts travel by value:
+    there is no device table (``device`` only names where a stream made from these rules lives by default)."""
+
+    OWNER, THINGS = 'the segmenter', 'the segment rules'
+
+    def __init__(self, min_speech=3, min_silence=13, max_frames=0, capacity=16, speech_classes=None, margin=0.0, classes=49, device=None):
+        self._set_speech(speech_classes, margin, classes)
+        for name, v in (('min_speech', min_speech), ('min_silence', min_silence), ('max_frames', max_frames), ('capacity', capacity)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) < 2 ** 31:
+                raise ValueError(f'{name} must be a non-negative int32 count (got {v})')
+        min_speech, min_silence, max_frames, capacity = int(min_speech), int(min_silence), int(max_frames), int(capacity)
+        if min_speech < 1 or min_silence < 1:
+            raise ValueError(f'min_speech and min_silence must be at least 1 frame (got {min_speech}, {min_silence})')
+        if max_frames and max_frames <= min_speech:
+            raise ValueError(f'max_frames must be 0 (no limit) or above min_speech={min_speech} (got {max_frames})')
+        if not 1 <= capacity <= MAX_SEGMENT_CAPACITY:
+            raise ValueError(f'capacity must lie in [1, {MAX_SEGMENT_CAPACITY}] (got {capacity})')
+        self.min_speech, self.min_silence, self.max_frames, self.capacity = min_speech, min_silence, max_frames, capacity
+        self._set_device(device)
+
+    @classmethod
+    def from_seconds(cls, min_speech=0.12, min_silence=0.5, max_seconds=0.0, **kwargs):
+        """The three counts given in seconds (``EndpointRules.frames_for`` converts each: the smallest frame count that covers them);
+        the other arguments are the constructor's.  The defaults are the constructor's."""
+        return cls(*(EndpointRules.frames_for(v) for v in (min_speech, min_silence, max_seconds)), **kwargs)
+
+    @property
+    def counts(self):
+        """``(min_speech, min_silence, max_frames, capacity)``: what a step is handed by value, in its order."""
+        return self.min_speech, self.min_silence, self.max_frames, self.capacity
+
+    def __repr__(self):
+        return (f'SegmentRules(min_speech={self.min_speech}, min_silence={self.min_silence}, max_frames={self.max_frames}, '
+                f'capacity={self.capacity}, speech_classes={self.speech_classes}, margin={self.margin}, classes={self.classes})')
+
+
+class SegmentResult:
+    """The segmenter's view of a batch.  int32 device tensors (B): ``frames`` (frames seen), ``speech_run`` / ``silence_run`` (the
+    consecutive speech / other frames ending at the last frame; one of them is 0), ``open_start`` (the first frame of the segment that
+    is open, -1: none is) and ``count`` (segments closed so far, in all).  ``ring`` (B, S, 4) int32: the closed segments ``(start, end,
+    reason, 0)``, segment k of a row in entry ``k % S``; a segment is the frames ``[start, end)``, reason 0 = ended by silence, 1 =
+    closed at ``max_frames``; an entry never written is ``(-1, -1, -1, 0)``.  ``dropped`` (B): the segments the ring no longer holds,
+    ``max(count - S, 0)``.  Only ``spans()`` reads the device: ``bool((r.count > seen).any())`` is the caller's synchronisation.  The
+    tensors are views of the state record they were made from: a stream's ``result`` shows its committed record and moves with the
+    next ``push`` or ``reset()``, a peek's shows the peek record until the next ``peek``; ``clone()`` keeps one."""
+
+    FIELDS = ('frames', 'speech_run', 'silence_run', 'open_start', 'count')
+
+    def __init__(self, state):
+        self.state = state                       # (B, 8 + 4 S) int32
+        for k, name in enumerate(self.FIELDS):
+            setattr(self, name, state[:, k])
+        self.capacity = (state.shape[1] - hip.SEGMENT_HEAD_WORDS) // hip.SEGMENT_ENTRY_WORDS
+        self.ring = state[:, hip.SEGMENT_HEAD_WORDS:].unflatten(1, (self.capacity, hip.SEGMENT_ENTRY_WORDS))
+
+    @property
+    def dropped(self):
+        return (self.count - self.capacity).clamp(min=0)
+
+    def clone(self):
+        """A copy that no later step changes (one device copy)."""
+        return SegmentResult(self.state.clone())
+
+    def seconds(self):
+        """(``open_start`` (B), the ring's ``start`` (B, S), the ring's ``end`` (B, S)) as float32 device tensors of seconds from the
+        stream's start: a segment runs from the START of its first frame, ``start * FRAME_SECONDS``, to the END of its last, ``end *
+        FRAME_SECONDS``; -1 (nothing open, an entry never written) stays -1.0."""
+        return tuple(torch.where(t >= 0, t.to(torch.float32) * FRAME_SECONDS, -1.0) for t in (self.open_start, self.ring[:, :, 0], self.ring[:, :, 1]))
+
+    def spans(self, include_open=False):
+        """The segments as host values -- the one method here that reads the device (one copy of the record).  Per row a list of
+        ``(start, end, reason)`` in the order they closed: the last ``min(count, S)`` closed segments (``dropped`` older ones are gone).
+        ``include_open=True`` adds a row's open segment as ``(open_start, frames, -1)``: open up to the last frame seen, the caller's to
+        end there (a stream that stops mid-speech)."""
+        rows = []
+        for rec in self.state.cpu().tolist():
+            frames, open_start, count = rec[0], rec[3], rec[4]
+            kept = min(count, self.capacity)
+            at = [hip.SEGMENT_HEAD_WORDS + hip.SEGMENT_ENTRY_WORDS * (k % self.capacity) for k in range(count - kept, count)]
+            row = [tuple(rec[a:a + 3]) for a in at]
+            if include_open and open_start >= 0:
+                row.append((open_start, frames, -1))
+            rows.append(row)
+        return rows
+
+    def __repr__(self):
+        return 'SegmentResult(' + ', '.join(f'{name}={getattr(self, name).tolist()}' for name in self.FIELDS) + ')'
+
+
+def _fresh_segment_state(batch, capacity):
+    """(B, 8 + 4 S) int32 on the host: the fresh rows of nbasr.h."""
+    entry = [-1, -1, -1, 0]
+    return torch.tensor([[0, 0, 0, -1, 0, 0, 0, 0] + entry * capacity] * batch, dtype=torch.int32)
+
+
+def _segment_rules(rules, device=None):
+    rules = SegmentRules(device=device) if rules is None else rules
+    if not isinstance(rules, SegmentRules):
+        raise ValueError(f'rules must be a SegmentRules (got {type(rules).__name__})')
+    return rules
+
+
+def segment(x, output_len=None, rules=None, return_mask=False):
+    """Where are the stretches of speech in these utterances?  ``x`` (B, T', C) float32 logits or log-probabilities on the device,
+    ``output_len`` their valid frames (tensor, sequence or None), ``rules`` a ``SegmentRules`` (None: the defaults, 49 classes).
+    Returns a ``SegmentResult`` -- with ``return_mask=True`` ``(result, mask)``, mask (B, T') uint8: 1 where the frame is speech, 0
+    beyond an utterance's length.  A segment still open at an utterance's end stays open (``spans(include_open=True)``).  A fresh
+    state and one step of the kernel the streams run (nbasr_ctc_segment_step): the same bits as any chunking of the frames."""
+    rules = _segment_rules(rules)
+    x = _logit_chunk(x, rules.classes, rules.THINGS)
+    b, n, _ = x.shape
+    lengths = _lengths(output_len, b, x.device)
+    state = torch.empty(b, hip.ctc_segment_state_words(rules.capacity), dtype=torch.int32, device=x.device)
+    mask = torch.empty(b, n, dtype=torch.uint8, device=x.device) if return_mask else None
+    if b:
+        hip.ctc_segment_step(x, lengths, None, state, *rules.counts, rules.speech_lo, rules.speech_hi, rules.margin, mask)
+    result = SegmentResult(state)
+    return (result, mask) if return_mask else result
+
+
+class SegmentStream(_LogitDetectorStream):
+    """``segment`` fed chunk by chunk, for as long as the stream lasts (nbasr_ctc_segment_step with a carried state; DESIGN.md §9
+    "Segments").
+
+        sg = SegmentStream(batch, rules, device=dev)
+        r = sg.push(logits_chunk, lengths=None)  # SegmentResult of everything pushed: == segment(all frames), bit for bit
+        r = sg.peek(next_chunk)                  # what push(next_chunk) would return; the stream stays as it was
+        r.spans()                                # per row [(start, end, reason), ...]: the one read of the device
+        sg.result                                # the committed result; sg.reset() starts new streams
+
+    The contract is ``EndpointStream``'s: both are ``_LogitDetectorStream``s, and this class adds only its record and its launch.
+    Nothing latches, so there is nothing to reset between utterances: ``count`` tells a listener how many segments have closed, the
+    ring holds the last ``capacity`` of them."""
+
+    RESULT = SegmentResult
+
+    def __init__(self, batch, rules=None, device=None):
+        batch = _positive(batch)
+        self.rules = _segment_rules(rules, device)
+        super().__init__(batch, self.rules, device)
+
+    def _fresh_rows(self):
+        return _fresh_segment_state(self.batch, self.rules.capacity)
+
+    def _step(self, x, chunk_lengths, state_out):
+        r = self.rules
+        hip.ctc_segment_step(x, chunk_lengths, None if self._fresh else self.state, state_out, *r.counts, r.speech_lo, r.speech_hi, r.margin)
+
+
+def decode_spans(log_probs, spans, pad=0, beam_width=12, cutoff_top_n=40, *, lm=None, alpha=1.0, beta=0.0):
+    """Transcribe segments: ``log_probs`` (B, T', C) float32 log-probabilities on the device, ``spans`` per row a list of ``(start,
+    end, ...)`` frame spans of that tensor -- what ``SegmentResult.spans()`` returns.  Each span is widened by ``pad`` frames on both
+    sides and clipped to the tensor; all spans of all rows are gathered into one padded batch by a single index operation and decoded
+    by ONE ``beam_decode`` call (``beam_width``, ``cutoff_top_n``, ``lm``, ``alpha``, ``beta`` are its arguments), whose search runs one
+    workgroup per utterance: each result is, to the bit, ``beam_decode`` of its slice alone.  Returns per row a list of ``(start, end,
+    tokens, score)``: the span as given, the best beam's tokens (1-D int32 CPU tensor) and its score (-log P, a float).  No spans:
+    empty lists, no launch."""
+    if not isinstance(log_probs, torch.Tensor) or log_probs.dim() != 3:
+        raise ValueError(f'log_probs must be (batch, frames, classes), got {tuple(getattr(log_probs, "shape", ()))}')
+    b, t, _ = log_probs.shape
+    spans = [list(row) for row in spans]
+    if len(spans) != b:
+        raise ValueError(f'expected the spans of {b} rows, got {len(spans)}')
+    pad = int(pad)
+    if pad < 0:
+        raise ValueError(f'pad must not be negative (got {pad})')
+    rows, first, last = [], [], []
+    for i, row in enumerate(spans):
+        for span in row:
+            start, end = int(span[0]), int(span[1])
+            if not 0 <= start <= end:
+                raise ValueError(f'a span is (start, end, ...) with 0 <= start <= end (got {tuple(span)})')
+            rows.append(i)
+            first.append(min(max(start - pad, 0), t))
+            last.append(min(end + pad, t))
+    out = [[] for _ in range(b)]
+    if not rows:
+        return out
+    lengths = torch.tensor([hi - lo for lo, hi in zip(first, last)], dtype=torch.int32)
+    width = max(int(lengths.max()), 1)
+    frames = (torch.tensor(first)[:, None] + torch.arange(width)[None, :]).clamp(max=max(t - 1, 0)).to(log_probs.device)
+    if t:
+        batch = log_probs[torch.tensor(rows, device=log_probs.device)[:, None], frames]     # (spans, width, C): frames past a span's end are not read
+    else:
+        batch = log_probs.new_zeros(len(rows), width, log_probs.shape[2])                   # (no frame to gather: every span is empty)
+    beams, scores, out_len = beam_decode(batch, lengths, beam_width, 0, cutoff_top_n, lm=lm, alpha=alpha, beta=beta)
+    beams, scores, out_len = beams[:, 0].cpu(), scores[:, 0].cpu(), out_len[:, 0].cpu()
+    at = 0
+    for i, row in enumerate(spans):
+        for span in row:
+            out[i].append((int(span[0]), int(span[1]), beams[at, :int(out_len[at])].clone(), float(scores[at])))
+            at += 1
+    return out
 
 
 # ---- keywords: has this phrase just been said? (nbasr.h "keywords"; DESIGN.md §9 "Keywords") -------------------------------------------

@@ -127,6 +127,9 @@ SIGNATURES = {
     'nbasr_ctc_endpoint_state_bytes': (ctypes.c_size_t, [_c_int]),
     'nbasr_ctc_endpoint_step': (_c_int, [_c_float_p] * 5 + [_c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
                                 + [_c_int] * 3 + [_c_stream]),
+    'nbasr_ctc_segment_state_bytes': (ctypes.c_size_t, [_c_int, _c_int]),
+    'nbasr_ctc_segment_step': (_c_int, [_c_float_p] * 4 + [_c_int] * 4 + [ctypes.c_longlong, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p]
+                               + [_c_int] * 3 + [_c_stream]),
     'nbasr_ctc_keyword_state_bytes': (ctypes.c_size_t, [_c_int, _c_int]),
     'nbasr_ctc_keyword_step': (_c_int, [_c_float_p] * 5 + [_c_int] * 2 + [_c_float_p] * 4 + [_c_int] * 3 + [_c_stream]),
     # streaming windows
@@ -1342,13 +1345,53 @@ def ctc_endpoint_step(x, lengths, state_in, state_out, rules, speech_lo, speech_
     Returns ``state_out``."""
     b, n, c = _detector_step_args('ctc_endpoint_step', x, lengths, state_in, state_out, ENDPOINT_STATE_WORDS)
     _int_tensor(rules, 'rules', x.device, (rules.shape[0], 3))
-    if mask_out is not None and (mask_out.dtype != torch.uint8 or mask_out.device != x.device or tuple(mask_out.shape) != (b, n)
-                                 or not mask_out.is_contiguous()):
-        raise HipError(f'ctc_endpoint_step: mask_out must be a contiguous ({b}, {n}) uint8 tensor on {x.device}')
     _check(load_library().nbasr_ctc_endpoint_step(
         x.data_ptr() if x.numel() else None, None if lengths is None else lengths.data_ptr(), None if state_in is None else state_in.data_ptr(),
         state_out.data_ptr(), rules.data_ptr(), rules.shape[0], _signed64(speech_lo), _signed64(speech_hi), float(margin),
-        mask_out.data_ptr() if mask_out is not None and mask_out.numel() else None, b, n, c, _stream(x)), 'nbasr_ctc_endpoint_step')
+        _speech_mask_arg('ctc_endpoint_step', mask_out, x), b, n, c, _stream(x)), 'nbasr_ctc_endpoint_step')
+    return state_out
+
+
+def _speech_mask_arg(who, mask_out, x):
+    """The address of a step's ``mask_out`` -- None, or a contiguous (B, n) uint8 tensor beside ``x`` (B, n, C) -- or None."""
+    if mask_out is None:
+        return None
+    b, n = x.shape[:2]
+    if mask_out.dtype != torch.uint8 or mask_out.device != x.device or tuple(mask_out.shape) != (b, n) or not mask_out.is_contiguous():
+        raise HipError(f'{who}: mask_out must be a contiguous ({b}, {n}) uint8 tensor on {x.device}')
+    return mask_out.data_ptr() if mask_out.numel() else None
+
+
+SEGMENT_HEAD_WORDS = 8           # int32 per utterance ahead of the ring: frames, speech_run, silence_run, open_start, count, 0, 0, 0
+SEGMENT_ENTRY_WORDS = 4          # a ring entry: start, end, reason, 0
+SEGMENT_MAX_CAPACITY = 64
+
+
+def ctc_segment_state_words(capacity):
+    """int32 words of one utterance's segment record with a ring of ``capacity`` entries: 8 + 4 capacity."""
+    return SEGMENT_HEAD_WORDS + SEGMENT_ENTRY_WORDS * int(capacity)
+
+
+def ctc_segment_state_bytes(batch, capacity):
+    """Bytes of the segment state of ``batch`` utterances with rings of ``capacity`` entries (nbasr.h: nbasr_ctc_segment_state_bytes);
+    0 for a batch that is not positive or a capacity outside [1, 64]."""
+    return int(load_library().nbasr_ctc_segment_state_bytes(int(batch), int(capacity)))
+
+
+def ctc_segment_step(x, lengths, state_in, state_out, min_speech, min_silence, max_frames, capacity, speech_lo, speech_hi, margin, mask_out=None):
+    """One step of the segmenter (nbasr.h: nbasr_ctc_segment_step) over ``x`` (B, n, C) float32 logits or log-probabilities.
+    ``lengths``: int32 device tensor (B) or None.  ``state_in`` / ``state_out``: (B, 8 + 4 capacity) int32 device tensors -- ``state_in``
+    None starts fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.  ``min_speech``,
+    ``min_silence``, ``max_frames``, ``capacity``: the counts, by value; ``speech_lo`` / ``speech_hi``: the class mask's two 64-bit
+    words; ``mask_out``: (B, n) uint8 device tensor or None.  Returns ``state_out``."""
+    capacity = int(capacity)
+    if not 1 <= capacity <= SEGMENT_MAX_CAPACITY:
+        raise HipError(f'ctc_segment_step: capacity={capacity} must lie in [1, {SEGMENT_MAX_CAPACITY}]')
+    b, n, c = _detector_step_args('ctc_segment_step', x, lengths, state_in, state_out, ctc_segment_state_words(capacity))
+    _check(load_library().nbasr_ctc_segment_step(
+        x.data_ptr() if x.numel() else None, None if lengths is None else lengths.data_ptr(), None if state_in is None else state_in.data_ptr(),
+        state_out.data_ptr(), int(min_speech), int(min_silence), int(max_frames), capacity, _signed64(speech_lo), _signed64(speech_hi),
+        float(margin), _speech_mask_arg('ctc_segment_step', mask_out, x), b, n, c, _stream(x)), 'nbasr_ctc_segment_step')
     return state_out
 
 

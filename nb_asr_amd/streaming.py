@@ -23,6 +23,9 @@
     sess = StreamingSession(model.eval(), B, keywords=ctc.KeywordSet.from_phonemes([['sh', 'iy']]))      # ... and a keyword spotter:
     sess.keywords.hit_frame                      # (B, K) int32 on the device, -1 until keyword k's score reached its threshold; latched
     provisional, ahead = sess.peek_keywords()    # peek(), and the spotter's view with the provisional frames included
+    sess = StreamingSession(model.eval(), B, segments=ctc.SegmentRules())        # ... and a segmenter, which never latches:
+    sess.segments.count                          # (B) int32 on the device: segments closed so far; sess.segments.spans() reads them
+    provisional, ahead = sess.peek_segments()    # peek(), and the segmenter's view with the provisional frames included
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -38,7 +41,8 @@ utterance's true start / end, where the full forward's padding is the same zeros
 import torch
 
 from . import hip
-from .ctc import BeamSearchStream, EndpointRules, EndpointStream, KeywordSet, KeywordStream, empty_beam_result, fusion_table
+from .ctc import (BeamSearchStream, EndpointRules, EndpointStream, KeywordSet, KeywordStream, SegmentRules, SegmentStream, empty_beam_result,
+                  fusion_table)
 from .frontend import LogMelFrontend, Resampler, end_frames_bound, frames_final
 
 FEATURES = 80
@@ -297,16 +301,22 @@ class StreamingSession:
     ``peek_endpoint``; DESIGN.md 9 "Endpoint").  ``None`` is the session without the argument: nothing allocated, nothing launched.
     ``keywords``: a ``ctc.KeywordSet``; the session then keeps a ``ctc.KeywordStream`` and hands it the same logits after the decode
     and endpoint launches, again one more launch when the step emitted a frame (``keywords``, ``peek_keywords``; DESIGN.md 9
-    "Keywords").  ``None``: nothing allocated, nothing launched."""
+    "Keywords").  ``None``: nothing allocated, nothing launched.
+    ``segments``: a ``ctc.SegmentRules``; the session then keeps a ``ctc.SegmentStream`` and hands it the same logits after the decode,
+    endpoint and keyword launches, again one more launch when the step emitted a frame (``segments``, ``peek_segments``; DESIGN.md 9
+    "Segments").  Its frames are logit frames since ``reset()``; ``flush()`` leaves an open segment open, and the caller ends it at
+    ``frames``.  ``None``: nothing allocated, nothing launched."""
 
     def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, endpoint=None,
-                 keywords=None, lm=None, alpha=1.0, beta=0.0):
+                 keywords=None, segments=None, lm=None, alpha=1.0, beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
         if endpoint is not None and not isinstance(endpoint, EndpointRules):
             raise ValueError(f'endpoint must be a ctc.EndpointRules or None (got {type(endpoint).__name__})')
         if keywords is not None and not isinstance(keywords, KeywordSet):
             raise ValueError(f'keywords must be a ctc.KeywordSet or None (got {type(keywords).__name__})')
+        if segments is not None and not isinstance(segments, SegmentRules):
+            raise ValueError(f'segments must be a ctc.SegmentRules or None (got {type(segments).__name__})')
         resampler = self.resampler_for(frontend, input_rate, getattr(frontend, 'device', None))
         self.end_frames = self.check_max_chunk(max_chunk, frontend, resampler)
         p0 = model.model[0].conv.weight
@@ -386,8 +396,9 @@ class StreamingSession:
         self._pack()
         self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
         self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
-        # what hears the logits of every step, in launch order (after the decode launches): a third detector is one more entry
-        self._listeners = [d for d in (self._endpoint, self._keywords) if d is not None]
+        self._segments = self._listener(SegmentStream, segments, 'the segment rules')
+        # what hears the logits of every step, in launch order (after the decode launches): another detector is one more entry
+        self._listeners = [d for d in (self._endpoint, self._keywords, self._segments) if d is not None]
         self.reset()
 
     def _listener(self, stream, spec, what):
@@ -470,8 +481,8 @@ class StreamingSession:
     @property
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
-        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's, and from
-        the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
+        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's, with ``segments=``
+        the segmenter's, and from the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0)
@@ -489,6 +500,13 @@ class StreamingSession:
         """The ``ctc.KeywordResult`` of the logit frames returned so far in this utterance ((B, K) device tensors, no synchronisation);
         None for a session made without ``keywords=``.  Once ``hit_frame >= 0`` the hit stays until ``reset()``; ``best_*`` go on improving."""
         return None if self._keywords is None else self._keywords.result
+
+    @property
+    def segments(self):
+        """The ``ctc.SegmentResult`` of the logit frames returned since ``reset()`` (device tensors; only its ``spans()`` reads the
+        device); None for a session made without ``segments=``.  Frames are logit frames since ``reset()``.  A closed segment stays as
+        it is (until the ring of ``capacity`` entries turns over it); ``flush()`` leaves an open segment open: it ends at ``frames``."""
+        return None if self._segments is None else self._segments.result
 
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
@@ -626,6 +644,14 @@ class StreamingSession:
         disappear; a committed one (``keywords``) cannot.  The session and its spotter are left as they were."""
         return self._peek_with(self._keywords, 'peek_keywords needs a keyword set: StreamingSession(..., keywords=ctc.KeywordSet(...))', decode)
 
+    def peek_segments(self, decode=False):
+        """``(peek(decode), SegmentResult)``: one peek of the model, then the segmenter's peek over the provisional logits on top of its
+        committed state -- ``ctc.segment`` of the committed and the provisional frames together.  A peeked segment is PROVISIONAL:
+        the provisional frames are computed as if the audio stopped now and can change when more arrives, so a segment seen opening
+        or closing here can do so elsewhere, or not at all; the committed ones (``segments``) cannot.  The session and its segmenter
+        are left as they were."""
+        return self._peek_with(self._segments, 'peek_segments needs segment rules: StreamingSession(..., segments=ctc.SegmentRules(...))', decode)
+
     def _peek_with(self, listener, refusal, decode):
         """``(peek(decode), the listener's peek over the provisional logits)``; ``refusal``: what a session without that listener says."""
         if listener is None:
@@ -692,7 +718,7 @@ class StreamingSession:
             result = (logits, dec.finish()) if final else (logits,) + pushed
         else:
             result = (logits, self._greedy(self._carried, logits)) if decode else logits
-        for d in self._listeners:                # after the decode launches, endpoint before keywords; a step that emitted no frame launches nothing
+        for d in self._listeners:                # after the decode launches: endpoint, keywords, segments; a step that emitted no frame launches nothing
             d.push(logits)
         return result
 
