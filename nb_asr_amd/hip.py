@@ -1146,7 +1146,7 @@ def ctc_beam_search(log_probs, lengths=None, beam_width=12, blank=0, cutoff_top_
     beams, scores, steps, lens = outs = _beam_outputs(b, beam_width, t, timesteps, dev)
     lib = load_library()
     ws_bytes = lib.nbasr_ctc_beam_timed_workspace_bytes if timesteps else lib.nbasr_ctc_beam_workspace_bytes
-    ws = torch.empty(max(ws_bytes(b, t, c, beam_width), 8) // 8, dtype=torch.int64, device=dev)
+    ws = torch.empty((max(ws_bytes(b, t, c, beam_width), 8) + 7) // 8, dtype=torch.int64, device=dev)   # rounded UP: B * T' * C floats may be odd
     _beam_call(lib, 'search', timesteps, fusion is not None, {
         'log_probs': log_probs.data_ptr(), 'lengths': _ptr(lengths), 'fusion': _ptr(fusion), 'ws': ws.data_ptr(), 'beams': beams.data_ptr(),
         'scores': scores.data_ptr(), 'timesteps': _ptr(steps), 'beam_lens': lens.data_ptr(), 'batch': b, 'frames': t, 'classes': c,
@@ -1222,7 +1222,7 @@ def ctc_beam_stream_peek(log_probs, chunk_lengths, state, beam_width, pool_nodes
     b, t, c, dev = _check_stream_chunk('ctc_beam_stream_peek', log_probs, chunk_lengths, fusion, state, beam_width, pool_nodes, timesteps)
     need = ctc_beam_stream_peek_workspace_bytes(b, t, c, beam_width, pool_nodes)
     if ws is None:
-        ws = torch.empty(max(need, 8) // 8, dtype=torch.int64, device=dev)
+        ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=dev)
     elif ws.device != dev or not ws.is_contiguous() or ws.numel() * ws.element_size() < need:
         raise HipError(f'ctc_beam_stream_peek: the workspace must be a contiguous tensor of {need} bytes on {dev}')
     beams, scores, steps, lens = outs = _beam_outputs(b, beam_width, max(int(ld), 1), timesteps, dev)

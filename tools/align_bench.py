@@ -11,9 +11,7 @@ its full length with 40 random labels on the log-softmax of random logits.  Ever
 ``--calls`` consecutive launches, after a warm-up window, divided by the calls; the median of ``--reps`` such windows with the smallest and
 largest next to it; (a) and (b) alternate window by window.  Recorded, not gated: no test holds a threshold against these numbers."""
 import argparse
-import json
 import pathlib
-import statistics
 import sys
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -21,28 +19,10 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 from nb_asr_amd import hip                       # noqa: E402
 
 SHAPES = [(64, 250, 49, 40), (8, 250, 49, 40)]  # batch, frames, classes, labels
-
-
-def window_ms(fn):
-    """Device milliseconds of one call of fn (HIP events on the current stream)."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
-
-
-def alternate(fns, reps):
-    """[median, min, max] ms per function over ``reps`` windows each, the functions taking turns."""
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            times[i].append(window_ms(fn))
-    return [(statistics.median(t), min(t), max(t)) for t in times]
 
 
 def measure(shape, calls, reps, dev):
@@ -74,12 +54,10 @@ def measure(shape, calls, reps, dev):
                                          losses.data_ptr(), grad.data_ptr(), b, frames, classes, labels, 0, stream)
             assert rc == 0, lib.nbasr_last_error()
 
-    for fn in (align, loss_grad):                # warm-up: code objects, clocks
-        fn()
-    torch.cuda.synchronize()
+    benchlib.warm((align, loss_grad), 1)         # code objects, clocks
     if not bool(torch.isfinite(scores).all()) or not bool(torch.isfinite(losses).all()):
         raise SystemExit('align_bench.py: the inputs were meant to align; the figures would time the early exit')
-    (a, a_lo, a_hi), (g, g_lo, g_hi) = alternate([align, loss_grad], reps)
+    (a, a_lo, a_hi), (g, g_lo, g_hi) = (benchlib.summary(t) for t in benchlib.alternate([align, loss_grad], reps=reps))
     per = lambda ms: round(ms / calls * 1e3, 2)
     return {'batch': b, 'frames': frames, 'classes': classes, 'labels': labels, 'calls_per_window': calls, 'windows': reps,
             'forced_align_us': per(a), 'forced_align_us_range': [per(a_lo), per(a_hi)],
@@ -93,17 +71,11 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('align_bench.py needs a HIP device: there is nothing to measure without one')
+    benchlib.need_device('align_bench.py')
     rows = []
     for shape in SHAPES:
-        row = dict(measure(shape, args.calls, args.reps, 'cuda:0'), build_id=hip.build_id())
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if args.out:
-        out = pathlib.Path(args.out)
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(rows, indent=1) + '\n')
+        benchlib.emit(rows, dict(measure(shape, args.calls, args.reps, 'cuda:0'), build_id=hip.build_id()))
+    benchlib.write_out(args.out, rows)
 
 
 if __name__ == '__main__':

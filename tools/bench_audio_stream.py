@@ -12,9 +12,7 @@ Every figure is device time between two HIP events around ``--pushes`` consecuti
 after a warm-up pass over the same shapes; the median of ``--reps`` such windows, with the smallest and largest next to it.  (a) and (b),
 and the two sides of (c), alternate window by window.  One JSON line per configuration; with --out also the list as a JSON file."""
 import argparse
-import json
 import pathlib
-import statistics
 import sys
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -23,31 +21,15 @@ sys.path.insert(0, str(REPO))
 import numpy as np                               # noqa: E402
 import torch                                     # noqa: E402
 
-import nb_asr_amd as nb                          # noqa: E402
+import benchlib                                  # noqa: E402
 from nb_asr_amd import frontend                  # noqa: E402
-from nb_asr_amd.weights import keyed_fill_       # noqa: E402
 
-ARCH = [[1, 0], [1, 0, 0], [1, 0, 0, 0]]        # bench.py's default architecture
 HOP = 160
 
 
-def window_ms(fn):
-    """Device milliseconds of one call of fn (HIP events on the current stream)."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
-
-
 def alternate(fns, reps):
-    """[median, min, max] ms per function over ``reps`` windows each, the functions taking turns."""
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            times[i].append(window_ms(fn))
-    return [(statistics.median(t), min(t), max(t)) for t in times]
+    """(median, min, max) ms per function over ``reps`` windows each, the functions taking turns."""
+    return [benchlib.summary(t) for t in benchlib.alternate(fns, reps=reps)]
 
 
 def main():
@@ -58,13 +40,10 @@ def main():
     ap.add_argument('--chunks', default='40,160')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_audio_stream.py needs a HIP device: there is nothing to measure without one')
+    benchlib.need_device('bench_audio_stream.py')
     dev = 'cuda:0'
     fe = frontend.LogMelFrontend(device=dev)
-    model = nb.get_model(ARCH, use_rnn=True, dropout_rate=0.0)
-    keyed_fill_(model, seed=1235, mode='lively')
-    model = model.to(dev).eval()
+    model = benchlib.session_model(dev)
     rng = np.random.default_rng(0)
     rows = []
     with torch.no_grad():
@@ -102,10 +81,7 @@ def main():
                     for p in feat_pieces:
                         plain.push(p)
 
-                for fn in (fused, chain, from_audio, from_features):                # warm-up: code objects, cached chains, allocator
-                    fn()
-                    fn()
-                torch.cuda.synchronize()
+                benchlib.warm((fused, chain, from_audio, from_features), 2)         # code objects, cached chains, allocator
                 (a, a_lo, a_hi), (c, c_lo, c_hi) = alternate([fused, chain], args.reps)
                 (pa, pa_lo, pa_hi), (pf, pf_lo, pf_hi) = alternate([from_audio, from_features], args.reps)
                 us = lambda ms: round(ms * 1e3 / pushes, 1)
@@ -119,13 +95,9 @@ def main():
                        'feature_pushes_per_window': len(feat_pieces),
                        'audio_over_features': round((pa / pushes) / (pf / len(feat_pieces)), 3),
                        'frontend_state_bytes': fs.state_bytes}
-                print(json.dumps(row), flush=True)
-                rows.append(row)
+                benchlib.emit(rows, row)
                 del audio, plain, fs
-    if args.out:
-        out = pathlib.Path(args.out)
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps(rows, indent=1) + '\n')
+    benchlib.write_out(args.out, rows)
 
 
 if __name__ == '__main__':

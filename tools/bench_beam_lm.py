@@ -14,7 +14,6 @@ timed (fused_zero): it walks exactly the unfused search's beams, so its ratio is
 changes which prefixes live, merge and get rescanned."""
 import argparse
 import ctypes
-import json
 import pathlib
 import sys
 
@@ -23,7 +22,8 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
-from bench_beam_timesteps import Search, alternate, inputs      # noqa: E402
+import benchlib                                  # noqa: E402
+from bench_beam_timesteps import Search, alternate, inputs, write_out      # noqa: E402
 from nb_asr_amd import hip                       # noqa: E402
 
 P, I = ctypes.c_void_p, ctypes.c_int
@@ -144,15 +144,8 @@ def main():
             if not same(variants['fused_zero'].result(), want_s) or (other is not None and not same(variants['other_unfused'].result(), want_s)):
                 raise SystemExit('the streams disagree')
             row['streams'].append({'push_frames': push, 'pushes': len(variants['unfused'].chunks), **timed_row(variants, a.iters)})
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if a.out:
-        out = {'build_id': hip.build_id(), 'device': torch.cuda.get_device_name(0), 'rows': rows}
-        if other is not None:
-            other.nbasr_build_id.restype = ctypes.c_char_p
-            out['other_build_id'] = other.nbasr_build_id().decode()
-        pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + '\n')
+        benchlib.emit(rows, row)
+    write_out(a.out, rows, other)
 
 
 if __name__ == '__main__':

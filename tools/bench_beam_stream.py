@@ -10,7 +10,6 @@ loop with its read-backs and finish().  Also: state bytes per utterance, the lar
 token of the final best beam that was committed before finish(), the frames between the push after which the best hypothesis (committed +
 partial) first held that token for good and the push that committed it, measured with pushes of 1 frame and of the timed sizes."""
 import argparse
-import json
 import pathlib
 import statistics
 import sys
@@ -21,6 +20,7 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 from nb_asr_amd import ctc, hip                  # noqa: E402
 
 
@@ -32,14 +32,7 @@ def inputs(batch, frames, sharp, seed=0):
 
 
 def gpu_ms(fn, iters):
-    out = []
-    for _ in range(iters + 2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
+    (out,) = benchlib.alternate([fn], reps=iters + 2)
     return statistics.median(out[2:])
 
 
@@ -53,17 +46,13 @@ def stream_gpu_ms(lp, push, iters, width=12):
         hip.ctc_beam_stream_init(state, b, width, pool)
         total = 0.0
         for at in range(0, t, push):
-            chunk = lp[:, at:at + push].contiguous()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            _, _, counts = hip.ctc_beam_stream_step(chunk, None, state, width, pool)
-            e1.record()
-            counts = counts.cpu()                                # the host's read-back between pushes
+            chunk, outs = lp[:, at:at + push].contiguous(), []
+            total += benchlib.window(lambda: outs.append(hip.ctc_beam_stream_step(chunk, None, state, width, pool)))
+            counts = outs[0][2].cpu()                            # the host's read-back between pushes
             usage = int(counts[2].max())
             if usage < 0 or usage + width * push + 1 > pool:
                 raise SystemExit(f'pool of {pool} nodes too small for this input (usage {usage})')
             usage_max = max(usage_max, usage)
-            total += e0.elapsed_time(e1)
         totals.append(total)
     return statistics.median(totals[2:]), usage_max, pool
 
@@ -135,11 +124,8 @@ def main():
                                    'gpu_overhead_us_per_push': round((g - whole) * 1e3 / pushes, 1), 'wall_us_with_readbacks': round(wall * 1e3, 1),
                                    'state_bytes_per_utterance': per_utt, 'max_pool_usage': usage_max, 'timed_pool_nodes': pool})
         row['commit_lag'] = [commit_lag(lp, p) for p in [1] + list(a.pushes)]
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if a.out:
-        pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        pathlib.Path(a.out).write_text(json.dumps({'build_id': hip.build_id(), 'device': torch.cuda.get_device_name(0), 'rows': rows}, indent=1) + '\n')
+        benchlib.emit(rows, row)
+    benchlib.write_out(a.out, {'build_id': hip.build_id(), 'device': torch.cuda.get_device_name(0), 'rows': rows})
 
 
 if __name__ == '__main__':

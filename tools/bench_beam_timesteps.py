@@ -10,7 +10,6 @@ in alternation, round by round, so that a drift of the machine falls on all of t
 the same preallocated buffers; the results of the two untimed searches are compared bit for bit, and the timed one's beams with them."""
 import argparse
 import ctypes
-import json
 import pathlib
 import statistics
 import sys
@@ -20,6 +19,7 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 from nb_asr_amd import ctc, hip                  # noqa: E402
 
 
@@ -63,16 +63,8 @@ class Search:
 
 def alternate(variants, iters, warmup=5):
     """{name: median GPU ms} of the variants' ``run``, one call of each per round."""
-    times = {name: [] for name in variants}
-    for k in range(warmup + iters):
-        for name, v in variants.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            v.run()
-            e1.record()
-            e1.synchronize()
-            if k >= warmup:
-                times[name].append(e0.elapsed_time(e1))
+    rounds = benchlib.alternate([v.run for v in variants.values()], reps=warmup + iters)
+    times = {name: t[warmup:] for name, t in zip(variants, rounds)}
     return {name: statistics.median(t) for name, t in times.items()}, {name: (min(t), max(t)) for name, t in times.items()}
 
 
@@ -104,15 +96,17 @@ def main():
         if other is not None:
             row['other_untimed_us'] = round(med['other_untimed'] * 1e3, 1)
             row['untimed_vs_other'] = round(med['untimed'] / med['other_untimed'], 4)
-        print(json.dumps(row), flush=True)
-        rows.append(row)
-    if a.out:
-        out = {'build_id': hip.build_id(), 'device': torch.cuda.get_device_name(0), 'rows': rows}
-        if other is not None:
-            other.nbasr_build_id.restype = ctypes.c_char_p
-            out['other_build_id'] = other.nbasr_build_id().decode()
-        pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
-        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + '\n')
+        benchlib.emit(rows, row)
+    write_out(a.out, rows, other)
+
+
+def write_out(path, rows, other):
+    """The rows under this build's id and the device's name, and the other library's id where there is one."""
+    out = {'build_id': hip.build_id(), 'device': torch.cuda.get_device_name(0), 'rows': rows}
+    if other is not None:
+        other.nbasr_build_id.restype = ctypes.c_char_p
+        out['other_build_id'] = other.nbasr_build_id().decode()
+    benchlib.write_out(path, out)
 
 
 if __name__ == '__main__':

@@ -4,6 +4,7 @@ pending LayerNorm on load and the statistics by-product as in the model.
 
 usage: python tools/bench_cell.py [--batch 64] [--frames 1000] [--kd 5,1] [--mask 0] [--iters 30]"""
 import argparse
+import itertools
 import pathlib
 import statistics
 import sys
@@ -11,6 +12,7 @@ import sys
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 
 DEV = 'cuda:0'
@@ -46,17 +48,8 @@ def main():
 
         def step(i):
             hip.grouped_cell_fused(bufs[i % nbuf], nodes, a.mask, bufs[(i + 1) % nbuf], tt, 100, ln, ws)
-        for i in range(5):
-            step(i)
-        torch.cuda.synchronize()
-        ts = []
-        for i in range(a.iters):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            step(i)
-            e1.record()
-            e1.synchronize()
-            ts.append(e0.elapsed_time(e1) * 1e3)
+        benchlib.warm([lambda i=itertools.count(): step(next(i))], 5)
+        ts = [1e3 * ms for ms in benchlib.alternate([lambda i=itertools.count(): step(next(i))], reps=a.iters)[0]]      # the chain restarts at 0
         fl = 3 * 2.0 * b * tt * c * (c // 100) * k
         med = statistics.median(ts)
         out.append(med)

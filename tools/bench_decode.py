@@ -3,27 +3,18 @@
 usage: python tools/bench_decode.py [--batch 64] [--frames 1000] [--iters 20]"""
 import argparse
 import pathlib
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parents[1]))
+import benchlib  # noqa: E402
 from nb_asr_amd import ctc  # noqa: E402
 
 
 def timeit(fn, iters):
-    for _ in range(3):
-        fn()
-    out = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1))
-    return statistics.median(out), min(out)
+    (times,) = benchlib.alternate([fn], reps=iters, warmup=3)
+    return benchlib.summary(times)[:2]
 
 
 def main():

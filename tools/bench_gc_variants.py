@@ -8,7 +8,6 @@ LayerNorm on load / statistics epilogue / three skips) time each variant `--roun
 algorithmic bytes.  Results are bit-identical across variants (tests/test_bf16_ops_gpu.py); this is speed only.
 """
 import argparse
-import json
 import pathlib
 import statistics
 import sys
@@ -16,6 +15,7 @@ import sys
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 
 
@@ -57,32 +57,18 @@ def main():
             for fname, f in flavours.items():
                 nbytes = elem * a.batch * c * t * (2 + len(f['skips'])) + 4 * (c * (c // 100) * a.kernel + c)
                 variants = (0, 1, 2, 3)
-                times = {v: [] for v in variants}
 
                 def run(v):
                     hip.grouped_conv1d_node(x, wp if v & hip.GC_WPERM else w, bias, f['skips'], y, t, 100, a.kernel, a.dilation,
                                             f['ln'], f['on_x'], False, f['ws'], v)
-                for v in variants:
-                    run(v)
-                torch.cuda.synchronize()
-                for _ in range(a.rounds):
-                    for v in variants:
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for _ in range(a.reps):
-                            run(v)
-                        e1.record()
-                        e1.synchronize()
-                        times[v].append(e0.elapsed_time(e1) * 1e3 / a.reps)
+                times = benchlib.alternate([lambda v=v: run(v) for v in variants], a.reps, a.rounds, warmup=1)
                 row = {'block': blk, 'C': c, 'T': t, 'dtype': dname, 'flavour': fname, 'MB': nbytes / 1e6}
                 for v in variants:
-                    us = statistics.median(times[v])
+                    us = 1e3 * statistics.median(times[v])
                     row[f'v{v}_us'] = round(us, 1)
                     row[f'v{v}_TBps'] = round(nbytes / us / 1e6, 2)
-                out.append(row)
-                print(json.dumps(row), flush=True)
-    if a.json:
-        pathlib.Path(a.json).write_text(json.dumps(out, indent=1) + '\n')
+                benchlib.emit(out, row)
+    benchlib.write_out(a.json, out)
 
 
 if __name__ == '__main__':

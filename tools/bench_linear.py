@@ -4,6 +4,7 @@ the `linear` node op at the four block shapes (fp32 rows: beside the exact-fp32 
 import pathlib, statistics, sys
 import torch
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 DEV = 'cuda:0'
 BF16 = torch.bfloat16
@@ -11,14 +12,7 @@ B = 64
 
 
 def timeit(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(10):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); e1.synchronize(); ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts)
+    return statistics.median(benchlib.alternate([fn], reps=10, warmup=3)[0])
 
 
 def report(what, c, t, gf, times):

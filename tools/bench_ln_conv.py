@@ -4,19 +4,13 @@ the staging fp16 conv, vs LayerNorm written as the pre-split image followed by t
 import pathlib, statistics, sys
 import torch
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 DEV = 'cuda:0'
 
 
 def timeit(fn):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(10):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(); fn(); e1.record(); e1.synchronize(); ts.append(e0.elapsed_time(e1) * 1e3)
-    return statistics.median(ts)
+    return 1e3 * statistics.median(benchlib.alternate([fn], reps=10, warmup=3)[0])
 
 
 BATCH = int(sys.argv[1]) if len(sys.argv) > 1 else 64

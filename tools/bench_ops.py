@@ -6,30 +6,20 @@ Prints per-op time (HIP events on the launch stream, median over iters), TFLOP/s
 """
 import argparse
 import pathlib
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 
 DEV = 'cuda:0'
 
 
 def timeit(fn, iters):
-    for _ in range(3):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(iters):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts)
+    (ts,) = benchlib.alternate([fn], reps=iters, warmup=3)
+    return benchlib.summary(ts)[:2]
 
 
 def main():

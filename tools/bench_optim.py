@@ -15,9 +15,7 @@ The two sides start from the same values and do not stay the same tensors: nothi
 regulariser's backward and the clip keep accumulating into it, while (a) only reads it.  Restoring it would add a 105 MB copy to the baseline;
 none of the kernels' time depends on the values."""
 import argparse
-import json
 import pathlib
-import statistics
 import sys
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -25,29 +23,9 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 import nb_asr_amd as nb                          # noqa: E402
 from nb_asr_amd import hip, ops, optim           # noqa: E402
-
-ARCH = [[1, 0], [1, 0, 0], [1, 0, 0, 0]]        # bench.py's default architecture
-
-
-def window_ms(fn):
-    """Device milliseconds of one call of fn (HIP events on the current stream)."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
-
-
-def alternate(fns, reps):
-    """[median, min, max] ms per function over ``reps`` windows each, the functions taking turns."""
-    times = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            times[i].append(window_ms(fn))
-    return [(statistics.median(t), min(t), max(t)) for t in times]
 
 
 def main():
@@ -56,11 +34,9 @@ def main():
     ap.add_argument('--reps', type=int, default=7)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit('bench_optim.py needs a HIP device: there is nothing to measure without one')
-    dev = 'cuda:0'
+    benchlib.need_device('bench_optim.py')
     torch.manual_seed(0)
-    model = nb.get_model(ARCH, use_rnn=True, dropout_rate=0.0, gpu=0)
+    model = nb.get_model(benchlib.ARCH, use_rnn=True, dropout_rate=0.0, gpu=0)
     params = list(model.parameters())
     flagged = [i for i, p in enumerate(params) if any(p is m.conv.weight for m in model.modules() if isinstance(m, ops.PadConvRelu))]
     grads = [1e-2 * torch.randn_like(p) for p in params]
@@ -83,10 +59,8 @@ def main():
             torch.nn.utils.clip_grad_norm_(twin, 5)
             theirs.step()
 
-    for fn in (hip_steps, torch_steps):          # warm-up: code objects, allocator, optimiser state
-        fn()
-    torch.cuda.synchronize()
-    (a, a_lo, a_hi), (b, b_lo, b_hi) = alternate([hip_steps, torch_steps], args.reps)
+    # warm-up: code objects, allocator, optimiser state
+    (a, a_lo, a_hi), (b, b_lo, b_hi) = (benchlib.summary(t) for t in benchlib.alternate([hip_steps, torch_steps], reps=args.reps, warmup=1))
     n_bytes = 4 * sum(p.numel() for p in params)
     per = lambda ms: round(ms / args.calls, 4)
     row = {'tensors': len(params), 'weight_norm_tensors': len(flagged), 'parameter_MB': round(n_bytes / 1e6, 1), 'calls_per_window': args.calls,
@@ -96,11 +70,7 @@ def main():
            'hip_over_torch': round(a / b, 3), 'bytes_per_step': 9 * n_bytes,
            'hip_TB_per_s': round(9 * n_bytes / (a / args.calls * 1e-3) / 1e12, 3),
            'torch_TB_per_s': round(9 * n_bytes / (b / args.calls * 1e-3) / 1e12, 3)}
-    print(json.dumps(row), flush=True)
-    if args.out:
-        out = pathlib.Path(args.out)
-        out.parent.mkdir(parents=True, exist_ok=True)
-        out.write_text(json.dumps([row], indent=1) + '\n')
+    benchlib.write_out(args.out, [benchlib.emit([], row)])
 
 
 if __name__ == '__main__':

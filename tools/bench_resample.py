@@ -10,9 +10,7 @@ Every figure is device time between two HIP events around ``--pushes`` consecuti
 after a warm-up pass over the same shapes; the median of ``--reps`` such windows, with the smallest and largest next to it.  One JSON
 line per configuration; with --out also the list as a JSON file.  There is no CPU path: without a HIP device this fails."""
 import argparse
-import json
 import pathlib
-import statistics
 import sys
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
@@ -20,27 +18,15 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 from nb_asr_amd import frontend                  # noqa: E402
 
 RATES = (8000, 11025, 44100, 48000)
 
 
-def window_us(fn, calls):
-    """Device microseconds per call over ``calls`` consecutive calls of fn (HIP events on the current stream)."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    for _ in range(calls):
-        fn()
-    stop.record()
-    stop.synchronize()
-    return 1e3 * start.elapsed_time(stop) / calls
-
-
 def timed(fn, calls, reps):
-    fn()
-    torch.cuda.synchronize()
-    times = [window_us(fn, calls) for _ in range(reps)]
-    return {'us': round(statistics.median(times), 2), 'us_min': round(min(times), 2), 'us_max': round(max(times), 2)}
+    (times,) = benchlib.alternate([fn], calls, reps, warmup=1)
+    return benchlib.summary(times, 'us', scale=1e3)
 
 
 def main():
@@ -50,6 +36,7 @@ def main():
     ap.add_argument('--batches', default='1,16,64')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    benchlib.need_device('bench_resample.py')
     dev = 'cuda:0'
     gen = torch.Generator().manual_seed(0)
     rows = []
@@ -58,18 +45,14 @@ def main():
         for b in (int(v) for v in args.batches.split(',')):
             chunk = torch.randn(b, rate * 2 // 5, generator=gen).to(dev)
             rs = r.stream(b)
-            rows.append({'what': 'ResamplerStream.push', 'rate': rate, 'batch': b, 'samples_per_push': chunk.shape[1],
-                         **timed(lambda: rs.push(chunk), args.pushes, args.reps)})
-            print(json.dumps(rows[-1]), flush=True)
+            benchlib.emit(rows, {'what': 'ResamplerStream.push', 'rate': rate, 'batch': b, 'samples_per_push': chunk.shape[1],
+                                 **timed(lambda: rs.push(chunk), args.pushes, args.reps)})
         wave = torch.randn(64, 10 * rate, generator=gen).to(dev)
         row = {'what': 'Resampler.__call__', 'rate': rate, 'batch': 64, 'samples': wave.shape[1], **timed(lambda: r(wave), args.pushes, args.reps)}
         row['bytes'] = 4 * 64 * (wave.shape[1] + r.out_len(wave.shape[1]))
         row['gb_per_s'] = round(row['bytes'] / row['us'] / 1e3, 1)
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-    if args.out:
-        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        pathlib.Path(args.out).write_text(json.dumps(rows, indent=1) + '\n')
+        benchlib.emit(rows, row)
+    benchlib.write_out(args.out, rows)
 
 
 if __name__ == '__main__':

@@ -4,6 +4,7 @@ import pathlib, statistics, sys
 import torch
 import torch.nn.functional as F
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
+import benchlib
 from nb_asr_amd import hip
 DEV = 'cuda:0'
 
@@ -48,13 +49,7 @@ def run(cin, cout, tin, s, b, time_it):
         for name, fn in (('fp32-mfma', lambda: hip.dense_conv1d_fused(xd, tin, wd, bd, (), y32, s)),
                          ('bf16x3', lambda: hip.dense_conv1d_fused_packed(xd, tin, packed, cout, 8, bd, (), y16, s)),
                          ('f16x2', lambda: hip.dense_conv1d_fused_packed(xd, tin, packed_h, cout, 8, bd, (), yh, s, scheme='f16x2', x_absmax=amax))):
-            for _ in range(3): fn()
-            torch.cuda.synchronize()
-            ts = []
-            for _ in range(10):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); fn(); e1.record(); e1.synchronize(); ts.append(e0.elapsed_time(e1))
-            med = statistics.median(ts)
+            med = statistics.median(benchlib.alternate([fn], reps=10, warmup=3)[0])
             msg += f'{name} {med * 1e3:8.1f} us {2.0 * b * tout * cout * cin * 8 / med / 1e9:6.1f} TF   '
     print(msg, flush=True)
 

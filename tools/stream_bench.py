@@ -19,7 +19,6 @@ import json
 import pathlib
 import statistics
 import sys
-import time
 
 REPO = pathlib.Path(__file__).resolve().parent.parent
 if '--package-root' in sys.argv:
@@ -28,33 +27,9 @@ sys.path.insert(0, str(REPO))
 
 import torch                                     # noqa: E402
 
+import benchlib                                  # noqa: E402
 import nb_asr_amd as nb                          # noqa: E402
-from nb_asr_amd.weights import keyed_fill_, keyed_input   # noqa: E402
-
-ARCH = [[1, 0], [1, 0, 0], [1, 0, 0, 0]]        # bench.py's default architecture
-
-
-def timed(fn, reps):
-    """Best wall time (ms) of ``reps`` runs of fn, each bracketed by device synchronisations."""
-    best = None
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ms = (time.perf_counter() - t0) * 1e3
-        best = ms if best is None else min(best, ms)
-    return best
-
-
-def window_ms(fn):
-    """Device milliseconds of one call of fn (HIP events on the current stream)."""
-    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    stop.record()
-    stop.synchronize()
-    return start.elapsed_time(stop)
+from nb_asr_amd.weights import keyed_input       # noqa: E402
 
 
 def peek_rows(model, args):
@@ -80,18 +55,13 @@ def peek_rows(model, args):
                     for p in pieces[:lead]:
                         sess.push(p, decode=decode)
                     assert sess.frames_out > 0
-                    return window_ms(fn)
+                    return benchlib.window(fn)
                 return window
             loops = {'push': loop(False, False), 'push_beam': loop('beam', False)}
             if can_peek:
                 loops.update({'push_peek': loop(False, True), 'push_beam_peek': loop('beam', True)})
-            for w in loops.values():                                            # warm-up: code objects, cached chains, allocator
-                w()
-                w()
-            times = {k: [] for k in loops}
-            for _ in range(args.reps):
-                for k, w in loops.items():
-                    times[k].append(w())
+            # a loop resets and feeds its session before its window opens, so it brings its own window; two of each warm up
+            times = dict(zip(loops, benchlib.alternate(list(loops.values()), reps=args.reps, warmup=2, window=lambda w, calls: w())))
             med = {k: statistics.median(t) / pairs for k, t in times.items()}
             row = {'batch': b, 'chunk': chunk, 'pairs_per_window': pairs, 'windows': args.reps, 'lookahead_frames': sess.lookahead_frames,
                    'build_id': nb.hip.load_library().nbasr_build_id().decode(),
@@ -103,8 +73,7 @@ def peek_rows(model, args):
                             'peek_ms': round(peek, 3), 'peek_beam_ms': round(peek_beam, 3),
                             'peek_over_push': round(peek / med['push'], 2), 'peek_beam_over_push_beam': round(peek_beam / med['push_beam'], 2),
                             'provisional_frames': int(sess.peek().shape[1]), 'session_mib': round(sess.buffer_bytes / 2**20, 1)})
-            print(json.dumps(row), flush=True)
-            rows.append(row)
+            benchlib.emit(rows, row)
             del sess
     if args.baseline:
         base = {(r['batch'], r['chunk']): r for r in json.loads(pathlib.Path(args.baseline).read_text())}
@@ -128,10 +97,9 @@ def main():
     ap.add_argument('--chunks', default='40,160')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    benchlib.need_device('stream_bench.py')
     dev = 'cuda:0'
-    model = nb.get_model(ARCH, use_rnn=True, dropout_rate=0.0)
-    keyed_fill_(model, seed=1235, mode='lively')
-    model = model.to(dev).eval()
+    model = benchlib.session_model(dev)
     rows = []
     if args.peek:
         if '--reps' not in sys.argv:
@@ -143,7 +111,7 @@ def main():
             x = keyed_input(b, args.frames, seed=0).to(dev)
             model(x)                                                            # warm the whole forward (tapes, packed weights)
             model(x)
-            whole_ms = timed(lambda: model(x), args.reps)
+            whole_ms = benchlib.best_wall_ms(lambda: model(x), args.reps)
             for chunk in (int(v) for v in args.chunks.split(',')):
                 sess = model.stream(batch=b, max_chunk=chunk)
                 pieces = [x[:, :, i:i + chunk].contiguous() for i in range(0, args.frames, chunk)]
@@ -154,18 +122,15 @@ def main():
                         sess.push(p)
                     sess.flush()
                 run()                                                           # warm-up (cached recurrence chains)
-                ms = timed(run, args.reps)
+                ms = benchlib.best_wall_ms(run, args.reps)
                 pushes = len(pieces) + 1
                 row = {'batch': b, 'chunk': chunk, 'frames': args.frames, 'pushes': pushes, 'ms_per_push': round(ms / pushes, 3),
                        'stream_ms': round(ms, 2), 'whole_ms': round(whole_ms, 2), 'streamed_over_whole': round(ms / whole_ms, 2),
                        'rtf': round(ms / (args.frames * 10.0), 4), 'lookahead_frames': sess.lookahead_frames,
                        'session_mib': round(sess.buffer_bytes / 2**20, 1)}
-                print(json.dumps(row), flush=True)
-                rows.append(row)
+                benchlib.emit(rows, row)
                 del sess
-    if args.out:
-        pathlib.Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-        pathlib.Path(args.out).write_text(json.dumps(rows, indent=1) + '\n')
+    benchlib.write_out(args.out, rows)
 
 
 if __name__ == '__main__':
