@@ -6,10 +6,22 @@
 //
 // Mapping: a 256-thread workgroup owns 64 consecutive frames of one utterance as 16 lanes x 16-byte
 // chunks (256-byte contiguous row segments) times 16 channel rows in flight; channels are strided
-// over the 16 row slots.  Pass 1 accumulates shifted sums per lane (shift = first sample, so the
-// single pass is cancellation-safe), the 16 row partials are merged with Chan's parallel-variance
-// formula through LDS, pass 2 re-reads the tile (L2 / Infinity-Cache warm) and writes the result.
+// over the 16 row slots.  Pass 1 accumulates shifted sums per lane (shift = the lane's first sample), the
+// 16 row partials are merged with Chan's parallel-variance formula through LDS, pass 2 re-reads the
+// tile (L2 / Infinity-Cache warm) and writes the result.
 // HBM-bound: 2 reads + 1 write of the tensor (algorithmic minimum 1 read + 1 write).
+//
+// Accuracy (tests/ln_stats_model.py restates this order in numpy fp32; tests/test_ln_stats_host.py measures it against fp64,
+// tests/test_layernorm_edges_gpu.py holds the kernels to it).  The shift makes a LANE's sums safe against a common offset of
+// its samples: d = x - shift is small and exact enough whatever the mean.  It does not make the single pass as good as two
+// passes everywhere:
+//   * the merge of the 16 row partials carries UNSHIFTED fp32 means, so delta = mean_b - mean is known to 2^-24 |mean| only and
+//     rstd is off by about 2^-24 |mean| sd / (var + eps) relative (1000 + N(0, 1): 3e-5 at 17 channels, 3e-6 at 1200; two-pass
+//     fp32: 1e-7); the mean itself is as good as two-pass;
+//   * a lane whose first sample is an outlier sums d d of that outlier's size for every later channel, and s2 - dm s1 cancels:
+//     the error grows with the channels per lane (one channel at 20 among ReLU-sparse ones: 1e-5 at 1200 channels).
+// With |mean| of the order of sd, as behind every ReLU node of the model, rstd is within 2e-7 ... 4e-7 of fp64.  Every producer of
+// statistics (stats_finalize_kernel, the node and cell epilogues, the dense by-product) merges unshifted means in the same way.
 #include "storage.h"
 
 namespace nbasr {

@@ -145,6 +145,7 @@ def pow2_scale(bound):
 
 
 IMAGE_CASES = [(c, ld, b) for c, ld, b in itertools.product((17, 40, 600), (4, 252, 260), (1, 9))] + [(17, 260, 64)]   # 64 x 2 tiles: grid z = 4
+IMAGE_CASES += [(c, 260, 1) for c in (1, 16, 113, 129, 241)]                     # the channel loop of tile_statistics: empty row slots, 4 and 8 rows in flight, tails
 
 
 @pytest.mark.parametrize('c,ld,b', IMAGE_CASES)
