@@ -1,7 +1,7 @@
 """The differentiable path: one ``torch.autograd.Function`` per op of the model, forward AND backward through the
 C ABI, and ``model_forward`` which strings them together -- what ``ASRModel.forward`` runs in training mode with gradients enabled,
 so that the reference's ``loss.backward()`` (trainer.py:220-223) reaches every parameter.  The backward passes that are host algorithms
-(the dense / linear maps, the LSTM's BPTT) live in backward.py; the others are single wrappers of hip.py.
+(the dense / linear maps, the LSTM's BPTT) live in backward.py; the others are single wrappers of hip/train.py.
 
 * ``grouped_pad_conv_relu``  reference ``ops.PadConvRelu`` with groups > 1 (ops.py:24-30): vector-ALU dgrad, MFMA wgrad
 * ``dense_pad_conv_relu``    the dense k = 8 downsample convs (model.py:82-89) and the per-frame ``linear`` op (ops.py:42-50)

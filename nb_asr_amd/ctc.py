@@ -320,7 +320,7 @@ class BeamSearchStream:
         once; ``peek`` calls it with its own chunk, so the workspace only ever grows)."""
         need = hip.ctc_beam_stream_peek_workspace_bytes(self.batch, frames, classes or self.classes or 1, self.beam_width, self.pool_nodes)
         if self._peek_ws is None or self._peek_ws.numel() * 8 < need:
-            self._peek_ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=self.device)
+            self._peek_ws = hip._scratch(need, self.device, torch.int64)
 
     @property
     def peek_bytes(self):

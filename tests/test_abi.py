@@ -1,4 +1,4 @@
-"""The C-ABI library loads and exports exactly what include/nbasr.h declares, and hip.py binds every entry point with the header's
+"""The C-ABI library loads and exports exactly what include/nbasr.h declares, and the package hip binds every entry point with the header's
 types (no GPU needed)."""
 import ctypes
 import re
