@@ -642,6 +642,53 @@ int nbasr_ctc_keyword_step(const float* x, const int* lengths, const int* tokens
                            int n_keywords, int blank, const int* state_in, int* state_out, float* scores_out, int* starts_out, int batch,
                            int frames, int classes, nbasr_stream_t stream);
 
+/* ---- confidence: how sure is the recogniser of each token? (nb_asr_amd/ctc.py confidence / ConfidenceStream; DESIGN.md 9 "Confidence")
+ * No reference counterpart.  The frame measures are Laptev and Ginsburg's: each frame's softmax becomes a number in [0, 1],
+ * quantised at once to an integer, and the integers are aggregated over the frames of each token.  Everything after the quantisation is
+ * integer arithmetic, so whole = chunked = peeked = a row alone, bit for bit.
+ *   x(batch, frames, classes) float32, contiguous: logits or log-probabilities (the result is the same for both), 2 <= classes <= 128;
+ *   -inf entries (masked classes) are legal, NaN and +inf inside a row's length are not defined input;
+ *   lengths(batch) int32 or NULL: row b takes its first lengths[b] <= frames frames; nothing at or beyond them is read;
+ *   path(batch, frames) int32 or NULL: the labels of a hypothesis other than the greedy one (nbasr_ctc_forced_align's path).
+ * Each frame of a row, with global index g = frames:
+ *   1. label c_t: with a path, path[b][t]; a path label outside [0, classes) at a frame within the row's length counts as `blank` and
+ *      sets the row's sticky `bad` word to 1.  Without a path the smallest index among the largest values: m starts as x[0], c_t as 0, and
+ *      `if (x[c] > m) { m = x[c]; c_t = c; }` in ascending c -- the token rule of nbasr_ctc_greedy_stream;
+ *   2. frame confidence, in float32: m = max_c x[c], lp_c = x[c] - (m + log(sum_c exp(x[c] - m))), p_c = exp(lp_c); then by `measure`
+ *        0 (prob)     p at c_t;
+ *        1 (entropy)  1 + (sum_c p_c lp_c) / ln(classes), terms with p_c == 0 counting as 0;
+ *        2 (tsallis)  (k - sum_c exp(alpha lp_c)) / (k - 1) with k = classes^(1 - alpha), 0 < alpha < 1; the host computes k once in double
+ *                     precision and hands the kernel its float32 value; terms with lp_c = -inf count as 0;
+ *      clamped to [0, 1] (a NaN clamps to 0).  One lane computes a frame, scanning the classes in ascending order: a frame's value is a
+ *      function of that frame's `classes` values alone;
+ *   3. q_t = rint(conf * 2^24), an integer in [0, 2^24];
+ *   4. tokens: a token is a maximal run of consecutive frames with the same non-blank label; a blank frame or another label ends the
+ *      run, the same label after a blank is a new token, blank frames belong to no token.  A token is (label, start, end, min_q, sum_q)
+ *      over its frames [start, end), sum_q in 64 bits.  It is CLOSED by the first frame that does not continue it, and, when the step
+ *      is called with final != 0, by the end of the row's frames;
+ *   5. frames += 1; a non-blank frame also takes part in utt_min_q, utt_sum and utt_frames.
+ * State: one row of 16 int32 per utterance (nbasr_ctc_confidence_state_bytes = 64 batch; 0 for a batch that is not positive), fresh
+ *   values in parentheses: frames (0), prev_label (the last frame's label; -1), open_start (-1: no token is open), open_min_q (2^24),
+ *   open_sum_lo, open_sum_hi (0, 0), tokens (tokens closed so far; 0), utt_min_q (2^24), utt_sum_lo, utt_sum_hi (0, 0), utt_frames (the
+ *   non-blank frames so far; 0), bad (0), 0, 0, 0, 0.  A 64-bit sum is (lo, hi), lo the low 32 bits as a bit pattern.  A step with
+ *   final != 0 leaves prev_label = -1 and no token open: whatever follows it starts a new token.
+ * Floats are the caller's to derive, in one way: min = float32(min_q) * 2^-24, mean = float32(double(sum_q) / (double(end - start) * 2^24)).
+ * nbasr_ctc_confidence_step: one launch over the frames of a chunk (or of whole utterances).
+ *   state_in == NULL: the rows start fresh.  state_out == state_in: the step is committed in place.  state_out != state_in: a peek --
+ *   state_in is only read and state_out receives what a commit would have left.  frames == 0 succeeds and still copies state_in (or
+ *   fresh rows) to a different state_out, and with final != 0 still closes an open token.
+ *   tokens_out(batch, frames + 1, 8) int32 and token_counts(batch), both or neither: the tokens this step closed, in order, as (label,
+ *   start, end, min_q, sum_lo, sum_hi, 0, 0), start and end global frame indices; entries past the row's count are -1 in every word.
+ *   frames + 1 is the most a step can close: a carried token, a new run at every frame, and final.
+ *   frame_q(batch, frames) int32 or NULL: every frame's q_t, blanks included; -1 at and beyond a row's length.
+ *   Refused on the host before any device work: negative sizes, classes outside [2, 128], blank outside [0, classes), an unknown
+ *   measure, for tsallis an alpha that is not strictly between 0 and 1 (NaN included), exactly one of tokens_out and token_counts
+ *   (NBASR_EINVAL); x (with frames > 0) or state_out NULL (NBASR_ENULL). */
+size_t nbasr_ctc_confidence_state_bytes(int batch);
+int nbasr_ctc_confidence_step(const float* x, const int* lengths, const int* path, const int* state_in, int* state_out, int measure,
+                              float alpha, int blank, int final, int* tokens_out, int* token_counts, int* frame_q, int batch, int frames,
+                              int classes, nbasr_stream_t stream);
+
 /* Copy (batch, channels, frames) `dtype` rows with pitch ld_src into pitch ld_dst, zero-filling columns
  * frames..ld_dst-1 (used to bring caller tensors into the pitched internal layout). */
 int nbasr_repitch(const void* src, void* dst, int rows, int frames, int ld_src, int ld_dst, int dtype, nbasr_stream_t stream);

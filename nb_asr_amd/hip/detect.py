@@ -1,4 +1,4 @@
-"""The detectors over CTC logits: the endpoint, segment and keyword steps and the sizes of their states."""
+"""The detectors over CTC logits: the endpoint, segment, keyword and confidence steps and the sizes of their states."""
 import ctypes
 
 import torch
@@ -14,6 +14,8 @@ SIGNATURES.update({
                                + [_c_int] * 3 + [_c_stream]),
     'nbasr_ctc_keyword_state_bytes': (ctypes.c_size_t, [_c_int, _c_int]),
     'nbasr_ctc_keyword_step': (_c_int, [_c_float_p] * 5 + [_c_int] * 2 + [_c_float_p] * 4 + [_c_int] * 3 + [_c_stream]),
+    'nbasr_ctc_confidence_state_bytes': (ctypes.c_size_t, [_c_int]),
+    'nbasr_ctc_confidence_step': (_c_int, [_c_float_p] * 5 + [_c_int, ctypes.c_float, _c_int, _c_int] + [_c_float_p] * 3 + [_c_int] * 3 + [_c_stream]),
 })
 
 ENDPOINT_STATE_WORDS = 8         # int32 per utterance: frames, speech_frames, first_speech, last_speech, endpoint_frame, endpoint_rule, 0, 0
@@ -133,4 +135,37 @@ def ctc_keyword_step(x, lengths, tokens, token_counts, thresholds, blank, state_
     _call('nbasr_ctc_keyword_step', x.data_ptr() if x.numel() else None, _ptr(lengths), tokens.data_ptr(), token_counts.data_ptr(),
           thresholds.data_ptr(), k, int(blank), _ptr(state_in), state_out.data_ptr(), scores_out.data_ptr() if trace else None,
           starts_out.data_ptr() if trace else None, b, n, c, _stream(x))
+    return state_out
+
+
+CONFIDENCE_STATE_WORDS = 16      # int32 per utterance: frames, prev_label, open_start, open_min_q, open_sum (lo, hi), tokens, utt_min_q, utt_sum (lo, hi), utt_frames, bad, 0 x 4
+CONFIDENCE_TOKEN_WORDS = 8       # a closed token: label, start, end, min_q, sum_lo, sum_hi, 0, 0
+CONFIDENCE_MEASURES = ('prob', 'entropy', 'tsallis')         # ``measure`` by value: the index
+
+
+def ctc_confidence_state_bytes(batch):
+    """Bytes of the confidence state of ``batch`` utterances (nbasr.h: nbasr_ctc_confidence_state_bytes); 0 for a batch that is not positive."""
+    return int(load_library().nbasr_ctc_confidence_state_bytes(int(batch)))
+
+
+def ctc_confidence_step(x, lengths, path, state_in, state_out, measure, alpha, blank, final, tokens_out=None, token_counts=None, frame_q=None):
+    """One step of the confidence estimator (nbasr.h: nbasr_ctc_confidence_step) over ``x`` (B, n, C) float32 logits or log-probabilities.  ``lengths``: int32
+    device tensor (B) or None; ``path``: (B, n) int32 device tensor, the labels of a hypothesis, or None (the greedy labels).  ``state_in`` / ``state_out``:
+    (B, 16) int32 device tensors -- ``state_in`` None starts fresh rows, the same tensor twice commits in place, two tensors leave ``state_in`` as it was.
+    ``measure`` (0 prob, 1 entropy, 2 tsallis), ``alpha``, ``blank``, ``final``: by value.  ``tokens_out`` (B, n + 1, 8) and ``token_counts`` (B) int32, both or
+    neither: the tokens this step closed; ``frame_q``: (B, n) int32 or None, every frame's quantised confidence.  Returns ``state_out``."""
+    b, n, c = _detector_step_args('ctc_confidence_step', x, lengths, state_in, state_out, CONFIDENCE_STATE_WORDS)
+    if path is not None:
+        _int_tensor(path, 'path', x.device, (b, n))
+    if (tokens_out is None) != (token_counts is None):
+        raise HipError('ctc_confidence_step: the tokens are tokens_out and token_counts together: give both or neither')
+    if tokens_out is not None:
+        _int_tensor(tokens_out, 'tokens_out', x.device, (b, n + 1, CONFIDENCE_TOKEN_WORDS))
+        _int_tensor(token_counts, 'token_counts', x.device, (b,))
+    if frame_q is not None:
+        _int_tensor(frame_q, 'frame_q', x.device, (b, n))
+    some = x.numel() > 0
+    _call('nbasr_ctc_confidence_step', x.data_ptr() if some else None, _ptr(lengths), path.data_ptr() if path is not None and some else None,
+          _ptr(state_in), state_out.data_ptr(), int(measure), float(alpha), int(blank), int(bool(final)), _ptr(tokens_out), _ptr(token_counts),
+          frame_q.data_ptr() if frame_q is not None and some else None, b, n, c, _stream(x))
     return state_out

@@ -26,6 +26,9 @@
     sess = StreamingSession(model.eval(), B, segments=ctc.SegmentRules())        # ... and a segmenter, which never latches:
     sess.segments.count                          # (B) int32 on the device: segments closed so far; sess.segments.spans() reads them
     provisional, ahead = sess.peek_segments()    # peek(), and the segmenter's view with the provisional frames included
+    sess = StreamingSession(model.eval(), B, confidence=ctc.ConfidenceRules())   # ... and per-token confidence:
+    sess.confidence.last.tokens_list()           # per row [(label, start, end, mean, min)]: the tokens the latest push / flush closed
+    provisional, ahead = sess.peek_confidence()  # peek(), and the tokens that would close if the audio stopped now
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -41,8 +44,8 @@ utterance's true start / end, where the full forward's padding is the same zeros
 import torch
 
 from . import hip
-from .ctc import (BeamSearchStream, EndpointRules, EndpointStream, KeywordSet, KeywordStream, SegmentRules, SegmentStream, empty_beam_result,
-                  fusion_table)
+from .ctc import (BeamSearchStream, ConfidenceRules, ConfidenceStream, EndpointRules, EndpointStream, KeywordSet, KeywordStream, SegmentRules,
+                  SegmentStream, empty_beam_result, fusion_table)
 from .frontend import LogMelFrontend, Resampler, end_frames_bound, frames_final
 
 FEATURES = 80
@@ -305,12 +308,18 @@ class StreamingSession:
     ``segments``: a ``ctc.SegmentRules``; the session then keeps a ``ctc.SegmentStream`` and hands it the same logits after the decode,
     endpoint and keyword launches, again one more launch when the step emitted a frame (``segments``, ``peek_segments``; DESIGN.md 9
     "Segments").  Its frames are logit frames since ``reset()``; ``flush()`` leaves an open segment open, and the caller ends it at
-    ``frames``.  ``None``: nothing allocated, nothing launched."""
+    ``frames``.  ``None``: nothing allocated, nothing launched.
+    ``confidence``: a ``ctc.ConfidenceRules``; the session then keeps a ``ctc.ConfidenceStream`` and hands it the same logits after the
+    decode launches and BEFORE the other listeners -- one more launch when the step emitted a frame; ``flush()`` hands it ``final=True``,
+    which closes the token still open and is one launch even with no frame (``confidence``, ``peek_confidence``; DESIGN.md 9
+    "Confidence").  ``None``: nothing allocated, nothing launched."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, endpoint=None,
-                 keywords=None, segments=None, lm=None, alpha=1.0, beta=0.0):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, confidence=None,
+                 endpoint=None, keywords=None, segments=None, lm=None, alpha=1.0, beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
+        if confidence is not None and not isinstance(confidence, ConfidenceRules):
+            raise ValueError(f'confidence must be a ctc.ConfidenceRules or None (got {type(confidence).__name__})')
         if endpoint is not None and not isinstance(endpoint, EndpointRules):
             raise ValueError(f'endpoint must be a ctc.EndpointRules or None (got {type(endpoint).__name__})')
         if keywords is not None and not isinstance(keywords, KeywordSet):
@@ -394,6 +403,7 @@ class StreamingSession:
                 self._resampler = resampler.stream(B)
                 self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
         self._pack()
+        self._confidence = self._listener(ConfidenceStream, confidence, 'the confidence rules')    # (steps ahead of the listeners, and knows the end)
         self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
         self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
         self._segments = self._listener(SegmentStream, segments, 'the segment rules')
@@ -482,12 +492,12 @@ class StreamingSession:
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
         front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's, with ``segments=``
-        the segmenter's, and from the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
+        the segmenter's, with ``confidence=`` the estimator's, and from the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
         return (sum(t.numel() * t.element_size() for t in self._bufs)
                 + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
                 + (self._frontend.state_bytes if self._frontend is not None else 0)
                 + (self._resampler.state_bytes if self._resampler is not None else 0)
-                + sum(d.state_bytes for d in self._listeners))
+                + sum(d.state_bytes for d in self._listeners) + (self._confidence.state_bytes if self._confidence is not None else 0))
 
     @property
     def endpoint(self):
@@ -508,6 +518,13 @@ class StreamingSession:
         it is (until the ring of ``capacity`` entries turns over it); ``flush()`` leaves an open segment open: it ends at ``frames``."""
         return None if self._segments is None else self._segments.result
 
+    @property
+    def confidence(self):
+        """The session's ``ctc.ConfidenceStream``; None for a session made without ``confidence=``.  Its ``last`` is the
+        ``ctc.ConfidenceResult`` of the latest push / push_audio / flush: the tokens that step closed (device tensors; only
+        ``tokens_list()`` reads the device).  A token closes at the first frame that does not continue it; ``flush()`` closes the last."""
+        return self._confidence
+
     def reset(self):
         """Start a new batch of utterances; the buffers are re-used."""
         self._carried.reset()
@@ -521,6 +538,8 @@ class StreamingSession:
             self._frontend.reset()
         if self._resampler is not None:
             self._resampler.reset()
+        if self._confidence is not None:
+            self._confidence.reset()
         for d in self._listeners:
             d.reset()
 
@@ -652,6 +671,15 @@ class StreamingSession:
         are left as they were."""
         return self._peek_with(self._segments, 'peek_segments needs segment rules: StreamingSession(..., segments=ctc.SegmentRules(...))', decode)
 
+    def peek_confidence(self, decode=False):
+        """``(peek(decode), ConfidenceResult)``: one peek of the model, then the estimator's final peek over the provisional logits on top
+        of its committed state -- the tokens that would close if the audio stopped now, the open one included.  What it shows is
+        PROVISIONAL: the provisional frames are computed as if the audio stopped now and can change when more arrives, so a token
+        seen here can end elsewhere, with another confidence, or not be there at all; the tokens of ``confidence.last`` cannot.  The
+        session and its estimator are left as they were."""
+        return self._peek_with(self._confidence, 'peek_confidence needs confidence rules: StreamingSession(..., confidence=ctc.ConfidenceRules(...))',
+                               decode)
+
     def _peek_with(self, listener, refusal, decode):
         """``(peek(decode), the listener's peek over the provisional logits)``; ``refusal``: what a session without that listener says."""
         if listener is None:
@@ -718,7 +746,9 @@ class StreamingSession:
             result = (logits, dec.finish()) if final else (logits,) + pushed
         else:
             result = (logits, self._greedy(self._carried, logits)) if decode else logits
-        for d in self._listeners:                # after the decode launches: endpoint, keywords, segments; a step that emitted no frame launches nothing
+        if self._confidence is not None:         # after the decode launches, ahead of the listeners; the only one that is told the end
+            self._confidence.push(logits, final=final)
+        for d in self._listeners:                # endpoint, keywords, segments; a step that emitted no frame launches nothing
             d.push(logits)
         return result
 
