@@ -29,9 +29,9 @@
 //   * h_t is stored as it is consumed: the image IS the B operand of the MFMA, [k-step][hi | lo'][lane] x 8 halves; a wave
 //     writes the 4 units of its row tile as one 8-byte piece per utterance and term.  A non-finite h travels as lo' = NaN, which
 //     every product it meets turns into NaN: a diverged utterance stays visible;
-//   * the gates use the hardware exp2 / rcp (1 ulp each) -- sigmoid(x) = rcp(1 + exp2(-x log2 e)); tanh(x) = (1 - e) rcp(1 + e),
-//     e = exp2(-2 |x| log2 e), and an odd polynomial below |x| = 0.35 where that form would cancel: ~55 vector instructions per
-//     frame instead of the ~200 of the library calls, at <= 2 ulp;
+//   * the gates use the hardware exp2 / rcp (1 ulp each) -- sigmoid(x) = rcp(1 + exp2(-x log2 e)), the rounding of that product handed
+//     on to the result (lx_exp_neg); tanh(x) = (1 - e) rcp(1 + e), e = exp2(-2 |x| log2 e), and an odd polynomial below |x| = 0.35
+//     where that form would cancel: ~70 vector instructions per frame instead of the ~200 of the library calls, at <= 2 ulp;
 //   * every wait is bounded (1 s of the 100 MHz clock); a timeout raises the status word (nbasr_lstm_seq_status, or the
 //     executor's asynchronous read-back) and fills the rest of that slice's h rows with NaN.
 #include "common.h"
@@ -81,9 +81,21 @@ constexpr size_t LX_STAMP_BYTES = NBASR_LX_STAMPS ? static_cast<size_t>(32) * LX
 #endif
 
 // sigmoid and tanh on the hardware exp2 / rcp (v_exp_f32, v_rcp_f32: 1 ulp each).  Saturation is exact: exp2 -> 0 or +inf, rcp(inf) = 0.
+// exp(-v) for the sigmoid.  The product v log2 e is rounded to 2^-24 of ITSELF, which exp2 turns into |v| 2^-24 ln 2 of the result, and
+// the fp32 constant lacks 1.9e-8 of log2 e, another |v| 1.3e-8: together 21 ulp at v = -30, where sigmoid(v) ~ exp(v) carries all of
+// it (tests/test_recurrent_edges_gpu.py, D: 20.6 ulp of h at i = o = -30 before this).  What the rounded product lacks -- exact, by one
+// fma -- and the constant's remainder go to the result as the factor 1 + r ln 2.  (The median keeps the factor a number where v is +-Inf
+// and r therefore NaN: exp2 is 0 or Inf there and the sigmoid 1 or 0 as before.  A NaN v still gives NaN through exp2.)
+__device__ __forceinline__ float lx_exp_neg(float v)
+{
+    const float t = v * -1.4426950408889634f;
+    const float r = __builtin_fmaf(v, -1.92596299e-8f, __builtin_fmaf(v, -1.4426950408889634f, -t));
+    const float m = __builtin_amdgcn_fmed3f(__builtin_fmaf(r, 0.6931471805599453f, 1.0f), 0.5f, 2.0f);
+    return __builtin_amdgcn_exp2f(t) * m;
+}
 __device__ __forceinline__ float lx_sigmoid(float v)
 {
-    return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
+    return __builtin_amdgcn_rcpf(1.0f + lx_exp_neg(v));
 }
 __device__ __forceinline__ float lx_tanh(float v)
 {
