@@ -839,6 +839,18 @@ int nbasr_lstm_backward_step(const float* dh_out, const float* w_hh_t, float* dc
 int nbasr_stream_window(const float* hist, int hist_ld, int hist_off, int n_hist, const float* src, int src_ld, int src_off, int n_new,
                         float* dst, int dst_ld, int batch, int channels, float* absmax, nbasr_stream_t stream);
 
+/* nbasr_stream_window_bf16: the same window with a bfloat16 destination (a session of a bfloat16 model).  Per row r < batch * channels:
+ *   dst[r][0 .. n_hist)              = hist[r][hist_off ..]   (bf16 -> bf16, bits copied; hist != dst)
+ *   dst[r][n_hist .. n_hist + n_new) = src[r][src_off ..]     (src_dtype = NBASR_BF16: bits copied; NBASR_F32: the fp32 frames of a
+ *                                                              waveform session's front-end rounded to nearest even, NaN stays NaN)
+ *   dst[r][n_hist + n_new .. dst_ld) = 0
+ * dst follows the rule of bf16 rows: dst_ld % 8 == 0, 16-byte aligned, written as whole 16-byte chunks.  hist_off, src_off, n_hist,
+ * n_new, hist_ld and src_ld are arbitrary element counts (the reads are element-sized and touch nothing outside the named ranges).
+ * No absmax: the bf16 path has no range pass.  Refusals as nbasr_stream_window's, and NBASR_EALIGN for dst_ld % 8 != 0 or a dst that
+ * is not 16-byte aligned, NBASR_EINVAL for a src_dtype that is neither storage type. */
+int nbasr_stream_window_bf16(const void* hist, int hist_ld, int hist_off, int n_hist, const void* src, int src_dtype, int src_ld, int src_off,
+                             int n_new, void* dst, int dst_ld, int batch, int channels, nbasr_stream_t stream);
+
 /* ---- front-end of a waveform stream (nb_asr_amd/frontend.py FrontendStream) --------------------------------------------------
  * The feature front-end above, push by push, as ONE launch: frame t covers samples [t*hop - win/2, t*hop + win/2), negative
  * indices reflected (i -> -i) and, in the final step only, i >= total_len -> 2 (total_len - 1) - i.  The CALLER decides which

@@ -246,6 +246,11 @@ def round_up4(n):
     return (n + 3) & ~3
 
 
+def round_up8(n):
+    """The row pitch of bfloat16 rows: whole 16-byte chunks of 8 frames."""
+    return (n + 7) & ~7
+
+
 def dense_mode():
     """NBASR_DENSE_MODE as it is set NOW, validated; the one place that reads it.  Dense k = 8 convs, fp32-accurate in every mode: 'auto' (default)
     = 2-way fp16 split (3 MFMAs per product) wherever the input has just been written by the LayerNorm kernel (which also emits the per-utterance

@@ -6,7 +6,7 @@ import ctypes
 import torch
 
 from . import (SIGNATURES, HipError, load_library, _call, _scratch, _opaque, _stream, _dev, _opt, _act, _act_opt, _ln, _skips3, dtype_code,
-               _c_float_p, _c_int, _c_stream, _c_ln_p)
+               BF16, _c_float_p, _c_int, _c_stream, _c_ln_p)
 
 SIGNATURES.update({
     # LayerNorm, statistics, node ops (storage-type generic: a trailing dtype code)
@@ -39,6 +39,7 @@ SIGNATURES.update({
     'nbasr_bf16_image_bytes': (ctypes.c_size_t, [_c_int] * 3),
     'nbasr_bf16_image': (_c_int, [_c_float_p] * 5 + [_c_int] * 4 + [ctypes.c_float, _c_int, _c_stream]),
     'nbasr_stream_window': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 3 + [_c_float_p, _c_stream]),
+    'nbasr_stream_window_bf16': (_c_int, [_c_float_p] + [_c_int] * 3 + [_c_float_p] + [_c_int] * 4 + [_c_float_p] + [_c_int] * 3 + [_c_stream]),
 })
 
 GC_FPL8, GC_WPERM, GC_OSPLIT, GC_PIPE, GC_RING = 1, 2, 4, 8, 16         # NBASR_GC_* variant bits of nbasr_grouped_conv1d_node
@@ -360,4 +361,18 @@ def stream_window(hist, hist_off, n_hist, src, src_off, n_new, dst, absmax=None)
     _call('nbasr_stream_window', _opt(hist, 'hist') if n_hist else None, hist.shape[2] if hist is not None else 0, int(hist_off), int(n_hist),
           _opt(src, 'src') if n_new else None, src.shape[2] if src is not None else 0, int(src_off), int(n_new), _dev(dst, 'dst'), dst_ld, b, c,
           _opt(absmax, 'absmax'), _stream(dst))
+    return dst
+
+
+def stream_window_bf16(hist, hist_off, n_hist, src, src_off, n_new, dst):
+    """One bfloat16 stage window of a streaming session (nbasr.h: nbasr_stream_window_bf16).  ``hist`` / ``dst``: (batch, channels, ld)
+    bfloat16 tensors, ``src`` bfloat16 or float32 (rounded on the way: the front-end's frames), each with its own row pitch (``hist`` /
+    ``src`` may be None when their frame count is 0); ``dst``'s pitch is a multiple of 8."""
+    b, c, dst_ld = dst.shape
+    for t, what in ((hist, 'hist'), (src, 'src')):
+        if t is not None and (t.shape[0] != b or t.shape[1] != c):
+            raise HipError(f'stream_window_bf16: {what} has shape {tuple(t.shape)}, dst {tuple(dst.shape)}')
+    _call('nbasr_stream_window_bf16', _act_opt(hist, 'hist', torch.bfloat16) if n_hist else None, hist.shape[2] if hist is not None else 0,
+          int(hist_off), int(n_hist), _act_opt(src, 'src', None) if n_new else None, dtype_code(src.dtype) if src is not None else BF16,
+          src.shape[2] if src is not None else 0, int(src_off), int(n_new), _act(dst, 'dst', torch.bfloat16), dst_ld, b, c, _stream(dst))
     return dst

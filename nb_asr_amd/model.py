@@ -279,7 +279,11 @@ class ASRModel(nn.Module):
         ``frontend``: a ``frontend.LogMelFrontend`` on the model's device; the session then also takes the waveform,
         ``sess.push_audio(wave_chunk)`` with (batch, n) float32 samples, and ``flush`` ends the front-end's stream first.  Samples at
         another rate than the front-end's, like an LM for the session's beam searches, are arguments of the constructor:
-        ``streaming.StreamingSession(model, batch, ..., frontend=fe, input_rate=48000)``."""
+        ``streaming.StreamingSession(model, batch, ..., frontend=fe, input_rate=48000)``.
+        A bfloat16 model is streamed the same way, opted into with the constructor's ``dtype``:
+        ``streaming.StreamingSession(model.to(torch.bfloat16), batch, dtype=torch.bfloat16)`` takes bfloat16 chunks (``push_audio``
+        float32 samples), keeps bfloat16 windows and returns bfloat16 logits, as ``model(x)`` does (DESIGN.md 9 "bf16 sessions");
+        ``stream`` itself keeps its parameter list and refuses a bfloat16 model."""
         from .streaming import StreamingSession
         return StreamingSession(self, batch, max_chunk, beam_width, cutoff_top_n, frontend)
 

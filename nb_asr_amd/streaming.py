@@ -29,6 +29,8 @@
     sess = StreamingSession(model.eval(), B, confidence=ctc.ConfidenceRules())   # ... and per-token confidence:
     sess.confidence.last.tokens_list()           # per row [(label, start, end, mean, min)]: the tokens the latest push / flush closed
     provisional, ahead = sess.peek_confidence()  # peek(), and the tokens that would close if the audio stopped now
+    sess = StreamingSession(model.to(torch.bfloat16).eval(), B, dtype=torch.bfloat16)      # the bf16 storage path, live: bfloat16 chunks in,
+    logits = sess.push(chunk.to(torch.bfloat16))                                           # bfloat16 logits out; everything above applies
 
 Why this is exact: every convolution of the model pads at most ``context / stride`` frames on the right (reference
 ops.py:8-17), LayerNorm, ``linear`` and ``zero`` have no time extent and the LSTM is unidirectional, so an output frame depends on a
@@ -289,6 +291,26 @@ class _Carried:
             self.h.copy_(other.h)
 
 
+class _Bf16Copies:
+    """What ``executor.node_into(..., copies=)`` reads of a bfloat16 session's derived weights: the four lookups of a ``ForwardPlan`` it
+    uses, answered from what the session packed once (``kept``: fp32 copies by ``id(parameter)``; ``packed``: the session's images)."""
+
+    def __init__(self, kept, packed, pointwise_ws):
+        self.kept, self.packed, self.pointwise_ws = kept, packed, pointwise_ws
+
+    def _f32(self, param):
+        return self.kept[id(param)]
+
+    def _packed_grouped(self, op):
+        return self.packed[id(op)]
+
+    def _packed_linear_bf16(self, w):
+        return self.packed[id(w)]
+
+    def _pointwise_bf16_ws(self, batch, c_in, ld):
+        return self.pointwise_ws
+
+
 # ------------------------------------------------------------------------------------------------------------------------------------
 class StreamingSession:
     """Chunk-by-chunk forward of ``model`` for a lockstep batch of ``batch`` utterances (``ASRModel.stream``).  Owns its windows, LSTM
@@ -312,10 +334,18 @@ class StreamingSession:
     ``confidence``: a ``ctc.ConfidenceRules``; the session then keeps a ``ctc.ConfidenceStream`` and hands it the same logits after the
     decode launches and BEFORE the other listeners -- one more launch when the step emitted a frame; ``flush()`` hands it ``final=True``,
     which closes the token still open and is one launch even with no frame (``confidence``, ``peek_confidence``; DESIGN.md 9
-    "Confidence").  ``None``: nothing allocated, nothing launched."""
+    "Confidence").  ``None``: nothing allocated, nothing launched.
+    ``dtype``: None (float32) or the storage type of the model's parameters; anything else, or a model stored otherwise, is refused.
+    ``dtype=torch.bfloat16`` with a bfloat16 model (``model.to(torch.bfloat16)``) is the bfloat16 session (DESIGN.md 9 "bf16 sessions"):
+    the windows in front of every encoder stage and the LSTM hold bfloat16 rows (pitch 8 frames, built by nbasr_stream_window_bf16), the
+    stages run the bf16 matrix-core kernels with every LayerNorm where ``walk.WalkBf16`` places it, gates, h, c and the logits ahead of
+    their one rounding stay float32.  ``push`` takes bfloat16 chunks, ``push_audio`` float32 samples as ever (the front-end's float32
+    frames are rounded while the first window is built); ``push`` / ``flush`` / ``peek`` return bfloat16 logits, as ``model(x)`` does,
+    and the decoders and listeners read ``logits.float()`` of exactly those (one more conversion per result).  A float32 session is
+    launch for launch the session without the argument; a bfloat16 model without it is refused."""
 
-    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, input_rate=None, confidence=None,
-                 endpoint=None, keywords=None, segments=None, lm=None, alpha=1.0, beta=0.0):
+    def __init__(self, model, batch, max_chunk=160, beam_width=12, cutoff_top_n=40, frontend=None, *, dtype=None, input_rate=None,
+                 confidence=None, endpoint=None, keywords=None, segments=None, lm=None, alpha=1.0, beta=0.0):
         if frontend is not None and not isinstance(frontend, LogMelFrontend):
             raise ValueError(f'frontend must be a LogMelFrontend or None (got {type(frontend).__name__})')
         if confidence is not None and not isinstance(confidence, ConfidenceRules):
@@ -329,8 +359,14 @@ class StreamingSession:
         resampler = self.resampler_for(frontend, input_rate, getattr(frontend, 'device', None))
         self.end_frames = self.check_max_chunk(max_chunk, frontend, resampler)
         p0 = model.model[0].conv.weight
-        if p0.dtype != torch.float32:
-            raise ValueError(f'streaming runs float32 models only (this one is {p0.dtype})')
+        if dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f'dtype must be torch.float32, torch.bfloat16 or None (float32), got {dtype!r}')
+        if dtype is None and p0.dtype != torch.float32:
+            raise ValueError(f'streaming runs float32 models unless asked: StreamingSession(model, batch, dtype=torch.bfloat16) streams a bfloat16 model '
+                             f'(this one is {p0.dtype})')
+        self.dtype = torch.float32 if dtype is None else dtype
+        if p0.dtype != self.dtype:
+            raise ValueError(f'dtype={self.dtype} does not match the model, whose parameters are {p0.dtype}: a session runs the model as it is stored')
         if model.training and model.dropout_rate > 0:
             raise ValueError('streaming has no dropout masks: call model.eval() or build the model with dropout_rate=0.0')
         if not p0.is_cuda:
@@ -357,6 +393,46 @@ class StreamingSession:
             self._bufs.append(t)
             return t
 
+        if self.dtype == torch.bfloat16:
+            h, c = self._allocate16(names, buf)
+        else:
+            h, c = self._allocate(names, buf)
+        self._carried = _Carried(planner, [bufs[0] for bufs in self.windows], h, c, buf(B, torch.int32)[:B])
+        # per stage kind (its body and what builds its window, None: no window -- the functions: bound methods would make the session hold itself)
+        cls = StreamingSession
+        if self.dtype == torch.bfloat16:
+            bodies = {'dense': (cls._dense16, cls._window16), 'cell': (cls._cell16, cls._window16), 'lstm': (cls._lstm16, cls._window16),
+                      'head': (cls._head_of_lstm16, None) if model.use_rnn else (cls._head16, cls._window)}
+        else:
+            bodies = {'dense': (cls._dense, cls._window), 'cell': (cls._cell, cls._window), 'lstm': (cls._lstm, cls._window),
+                      'head': (cls._head_of_lstm, None) if model.use_rnn else (cls._head, cls._window)}
+        self._bodies = [bodies[sp.kind] for sp in self.specs]
+        # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
+        self._frontend, self._resampler, self.lookahead_samples = None, None, None
+        if frontend is not None:
+            if frontend.device != dev:
+                raise ValueError(f'the front-end lives on {frontend.device}, the model on {dev}')
+            if frontend.n_mels != FEATURES:
+                raise ValueError(f'the model reads {FEATURES} features per frame, the front-end makes {frontend.n_mels}')
+            self._frontend = frontend.stream(B)
+            ld = hip.round_up4(max_chunk)
+            self._staging = buf(B * FEATURES * ld).view(B, FEATURES, ld)
+            self.lookahead_samples = self._frontend.lookahead_samples + frontend.hop_length * self.lookahead_frames
+            if resampler is not None:            # in samples at the input rate: the front-end's share converted, plus the resampler's own
+                self._resampler = resampler.stream(B)
+                self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
+        self._pack16() if self.dtype == torch.bfloat16 else self._pack()
+        self._confidence = self._listener(ConfidenceStream, confidence, 'the confidence rules')    # (steps ahead of the listeners, and knows the end)
+        self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
+        self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
+        self._segments = self._listener(SegmentStream, segments, 'the segment rules')
+        # what hears the logits of every step, in launch order (after the decode launches): another detector is one more entry
+        self._listeners = [d for d in (self._endpoint, self._keywords, self._segments) if d is not None]
+        self.reset()
+
+    def _allocate(self, names, buf):
+        """The float32 session's windows and scratch (``buf``: the constructor's allocator); returns the LSTM's (h, c) or (None, None)."""
+        model, caps, B = self.model, self.caps, self.batch
         # a pair of windows per stage (the head / LSTM input: one buffer, nothing is retained), scratch for outputs and node results
         self.windows = []
         out_elems = node_elems = need_pw = 0
@@ -382,34 +458,59 @@ class StreamingSession:
             self.h_out = buf(B * lstm_cap * LSTM_HIDDEN)
             h, c = buf(B * LSTM_HIDDEN), buf(B * LSTM_HIDDEN)
             self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
-        self._carried = _Carried(planner, [bufs[0] for bufs in self.windows], h, c, buf(B, torch.int32)[:B])
-        # per stage kind (its body -- the function: bound methods would make the session hold itself --, whether it builds a window)
-        cls = StreamingSession
-        bodies = {'dense': (cls._dense, True), 'cell': (cls._cell, True), 'lstm': (cls._lstm, True),
-                  'head': (cls._head_of_lstm, False) if model.use_rnn else (cls._head, True)}
-        self._bodies = [bodies[sp.kind] for sp in self.specs]
-        # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
-        self._frontend, self._resampler, self.lookahead_samples = None, None, None
-        if frontend is not None:
-            if frontend.device != dev:
-                raise ValueError(f'the front-end lives on {frontend.device}, the model on {dev}')
-            if frontend.n_mels != FEATURES:
-                raise ValueError(f'the model reads {FEATURES} features per frame, the front-end makes {frontend.n_mels}')
-            self._frontend = frontend.stream(B)
-            ld = hip.round_up4(max_chunk)
-            self._staging = buf(B * FEATURES * ld).view(B, FEATURES, ld)
-            self.lookahead_samples = self._frontend.lookahead_samples + frontend.hop_length * self.lookahead_frames
-            if resampler is not None:            # in samples at the input rate: the front-end's share converted, plus the resampler's own
-                self._resampler = resampler.stream(B)
-                self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
-        self._pack()
-        self._confidence = self._listener(ConfidenceStream, confidence, 'the confidence rules')    # (steps ahead of the listeners, and knows the end)
-        self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
-        self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
-        self._segments = self._listener(SegmentStream, segments, 'the segment rules')
-        # what hears the logits of every step, in launch order (after the decode launches): another detector is one more entry
-        self._listeners = [d for d in (self._endpoint, self._keywords, self._segments) if d is not None]
-        self.reset()
+        return h, c
+
+    def _allocate16(self, names, buf):
+        """The bfloat16 session's windows and scratch: bf16 rows pitched to 8 frames in front of every encoder stage and the LSTM (fp32
+        rows in front of a head without LSTM: the last LayerNorm writes fp32), bf16 scratch; LayerNorm statistics, gates, h, c and the
+        logits ahead of their rounding in fp32.  Fixes what must not depend on a push's frame count: whether the cells run on the
+        matrix cores (they do where the stage's largest window fits; else every window takes the node launches)."""
+        from .walk import _CELL_SKIPS
+        from .ops import PadConvRelu, Identity
+        model, caps, B, lib = self.model, self.caps, self.batch, hip.load_library()
+        bf16 = torch.bfloat16
+        cells = [(sp, hip.round_up8(cap)) for sp, cap in zip(self.specs, caps) if sp.kind == 'cell']
+        nodes = model.model[cells[0][0].layer].nodes
+        conv_only = len(nodes) == 3 and all(isinstance(n.op, PadConvRelu) and n.op.groups > 1 for n in nodes)
+        self._cell_mfma = conv_only and all(hip.grouped_cell_mfma_fits(sp.c_in, ld, model.model[sp.layer].nodes[-1].op.groups) for sp, ld in cells)
+        self._skip_mask = sum(1 << bit for bit, (j, i) in enumerate(_CELL_SKIPS) if isinstance(nodes[j].branch_ops[i], Identity)) if conv_only else 0
+        self.windows = []
+        out_elems = node_elems = need_pw = image_bytes = 0
+        has_linear = any(n[0] == 'linear' for n in names)
+        for sp, cap in zip(self.specs, caps):
+            ld = hip.round_up8(cap)
+            n = B * sp.c_in * ld
+            if sp.kind == 'head':                # behind the LSTM: no window; without it: fp32 rows
+                self.windows.append([buf(0 if model.use_rnn else B * sp.c_in * hip.round_up4(cap))])
+                continue
+            self.windows.append([buf(n, bf16), buf(n, bf16)] if sp.kind in ('dense', 'cell') else [buf(n, bf16)])
+            if sp.kind in ('dense', 'cell'):
+                out_elems = max(out_elems, B * sp.c_out * hip.round_up8(out_length(cap, sp.stride)))
+            if sp.kind == 'dense':
+                image_bytes = max(image_bytes, lib.nbasr_bf16_image_bytes(B, sp.c_in, ld))
+            if sp.kind == 'cell' and not self._cell_mfma:
+                node_elems = max(node_elems, B * sp.c_out * ld)
+            if sp.kind == 'lstm' or (sp.kind == 'cell' and has_linear):
+                need_pw = max(need_pw, lib.nbasr_pointwise_bf16_workspace_bytes(B, sp.c_in, ld))
+        ld_max = hip.round_up8(max(caps))
+        self.scratch = buf(out_elems, bf16)
+        self.node_scratch = [buf(node_elems, bf16), buf(node_elems, bf16)] if node_elems else None
+        self.stats = buf(B * 2 * ld_max)         # per-frame (mean, rstd) of the LayerNorm a stage applies while it loads its window
+        self.image = buf(max(image_bytes, 16), torch.uint8)
+        self.pointwise_ws = buf(max(need_pw, 16), torch.uint8) if need_pw else None
+        classes = model.model[self.specs[-1].layer].out_features
+        self.logits32 = buf(hip.round_up8(B * max(caps[-2:]) * classes))
+        h = c = None
+        if model.use_rnn:
+            lstm_cap = caps[[sp.kind for sp in self.specs].index('lstm')]
+            self.gates = buf(lstm_cap * B * 4 * LSTM_HIDDEN)
+            self.h_out = buf(B * lstm_cap * LSTM_HIDDEN)
+            h, c = buf(B * LSTM_HIDDEN), buf(B * LSTM_HIDDEN)
+            self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
+        else:
+            sp, ld = cells[-1]
+            self.enc32 = buf(B * sp.c_out * ld)  # the encoder output as the head reads it
+        return h, c
 
     def _listener(self, stream, spec, what):
         """The ``ctc`` detector stream of this session for ``spec`` (its rules or keywords; None: no such listener)."""
@@ -475,6 +576,73 @@ class StreamingSession:
                     self._packed['w_hh16'] = hip.lstm_pack_whh16(lstm.weight_hh_l0.detach().contiguous())
         self._bufs.extend(t for t in self._packed.values() if isinstance(t, torch.Tensor))
         self._bufs.extend(t for _, t in (v for v in self._packed.values() if isinstance(v, tuple)))
+
+    def _pack16(self):
+        """The bfloat16 session's derived weights, made once: the operand images the matrix-core kernels take (packed from fp32 copies
+        that are dropped again) and fp32 copies of what the kernels read as fp32 -- biases, gamma / beta, the head.  Also settles, per
+        stage, where its LayerNorm is applied (``walk.WalkBf16``'s placement): ``_ln_in[k]`` = (gamma, beta, eps) of the LayerNorm stage k
+        applies while it loads its un-normalised window, ``_ln_out[k]`` = (how, gamma, beta, eps) of the one it applies to its output
+        ('inplace': bf16 rows for a cell that starts with `linear`; 'f32': fp32 rows for the head, gamma None: only widened)."""
+        import torch.nn as nn
+        from . import tiles
+        from .ops import PadConvRelu, Linear
+        from .walk import cheap_consumer
+        m, B = self.model.model, self.batch
+        self._versions = [(p, p.data_ptr(), p._version) for p in self.model.parameters()]
+        self._packed, kept = {}, {}
+
+        def f32(p):
+            return p.detach().float().contiguous()
+
+        def keep(p):
+            if id(p) not in kept:
+                kept[id(p)] = f32(p)
+            return kept[id(p)]
+
+        norms = [None] * len(self.specs)         # the LayerNorm behind each stage
+        with torch.no_grad():
+            for k, (sp, cap) in enumerate(zip(self.specs, self.caps)):
+                if sp.kind == 'dense':
+                    conv, norms[k] = m[sp.layer], m[sp.layer + 1]
+                    # the row tile of the stage's largest window, for every push: one packed image (every tiling gives the same bits)
+                    rows, ftile = tiles.bf16_tile(B, sp.c_out, out_length(cap, sp.stride))
+                    self._packed[sp.layer] = (hip.pack_dense_weights_bf16(f32(conv.conv.weight), conv.strides, rows), rows, ftile)
+                    keep(conv.conv.bias)
+                elif sp.kind == 'cell':
+                    cell = m[sp.layer]
+                    norms[k] = cell.norm_layer if cell.use_norm else None
+                    for node in cell.nodes:
+                        op = node.op
+                        if isinstance(op, PadConvRelu):
+                            w = f32(op.conv.weight)
+                            self._packed[id(op)] = hip.grouped_cell_mfma_pack(w, op.groups) if self._cell_mfma else hip.pack_grouped_weights(w, op.groups)
+                            keep(op.conv.bias)
+                        elif isinstance(op, Linear):
+                            self._packed[id(op.linear.weight)] = hip.pack_pointwise_weights_bf16(f32(op.linear.weight))
+                            keep(op.linear.bias)
+                elif sp.kind == 'lstm':
+                    lstm = m[sp.layer]
+                    assert isinstance(lstm, nn.LSTM)
+                    self._packed['w_ih'] = hip.pack_pointwise_weights_bf16(f32(lstm.weight_ih_l0))
+                    self._packed['w_hh16'] = hip.lstm_pack_whh16(f32(lstm.weight_hh_l0))
+                    keep(lstm.bias_ih_l0), keep(lstm.bias_hh_l0)
+                else:
+                    keep(m[sp.layer].weight), keep(m[sp.layer].bias)
+            self._ln_in, self._ln_out = [None] * len(self.specs), [None] * len(self.specs)
+            for k, norm in enumerate(norms):
+                if self.specs[k].kind not in ('dense', 'cell'):
+                    continue
+                nxt = self.specs[k + 1]
+                affine = (None, None, 0.0) if norm is None else (keep(norm.weight), keep(norm.bias), norm.eps)
+                if nxt.kind == 'head':
+                    self._ln_out[k] = ('f32',) + affine
+                elif norm is not None and nxt.kind == 'cell' and not cheap_consumer(m[nxt.layer]):
+                    self._ln_out[k] = ('inplace',) + affine
+                elif norm is not None:           # a conv-only cell, a dense conv's operand image, the LSTM's projection: on load
+                    self._ln_in[k + 1] = affine
+        self._copies = _Bf16Copies(kept, self._packed, self.pointwise_ws)
+        self._bufs.extend(kept.values())
+        self._bufs.extend(v[0] if isinstance(v, tuple) else v for v in self._packed.values())
 
     def _check_params(self):
         for p, ptr, ver in self._versions:
@@ -544,7 +712,7 @@ class StreamingSession:
             d.reset()
 
     def push(self, chunk, decode=False):
-        """Feed (batch, 80, n) float32 frames; returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
+        """Feed (batch, 80, n) frames of the session's dtype (float32; bfloat16 in a bfloat16 session); returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
         the greedy CTC tokens of those frames (a list of int32 CPU tensors), repeats collapsed across pushes.  ``decode='beam'`` returns
         ``(logits, committed, partial)``: the prefix beam search of ``ctc.beam_decode`` run over the log-probabilities of the final frames
         (``ctc.BeamSearchStream``): tokens that are now final, and the best beam's tokens after all committed ones.
@@ -555,8 +723,9 @@ class StreamingSession:
             raise ValueError('push after flush: call reset() to start the next utterance')
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or chunk.shape[0] != self.batch or chunk.shape[1] != FEATURES:
             raise ValueError(f'expected a ({self.batch}, {FEATURES}, frames) chunk, got {tuple(getattr(chunk, "shape", ()))}')
-        if chunk.dtype != torch.float32 or chunk.device != self.device:
-            raise ValueError(f'the chunk must be float32 on {self.device} (got {chunk.dtype} on {chunk.device})')
+        if chunk.dtype != self.dtype or chunk.device != self.device:
+            name = 'bfloat16' if self.dtype == torch.bfloat16 else 'float32'
+            raise ValueError(f'the chunk must be {name} on {self.device} (got {chunk.dtype} on {chunk.device})')
         if self._fed == 'audio':
             raise ValueError('push after push_audio: an utterance is fed features or samples, not both (reset() starts the next one)')
         self._begin(decode)
@@ -641,13 +810,13 @@ class StreamingSession:
         elif self._fed == 'audio':               # the front-end's end frames as uncommitted pushes, then the final step
             m = self._frontend.peek(out=(self._staging, 0)).shape[2]
             outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(self._cuts(m))]
-        outs.append(self._step(pk, None, 0, 0, True, lambda k, current: self._peek_window))
-        logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+        outs.append(self._step(pk, None, 0, 0, True, self._place_peek))
+        logits = self._join(outs)
         if decode in BEAM_DECODES:
             dec = self._decoder(decode)
             dec.reserve_peek(self._peek_frames, logits.shape[2])
-            return logits, dec.peek(self._log_probs(logits))
-        return (logits, self._greedy(pk, logits)) if decode else logits
+            return logits, dec.peek(self._log_probs(self._heard(logits)))
+        return (logits, self._greedy(pk, self._heard(logits))) if decode else logits
 
     def peek_endpoint(self, decode=False):
         """``(peek(decode), EndpointResult)``: one peek of the model, then the endpointer's peek over the provisional logits on top of its
@@ -686,7 +855,7 @@ class StreamingSession:
             raise ValueError(refusal)
         peeked = self.peek(decode)
         logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
-        return peeked, listener.peek(logits)
+        return peeked, listener.peek(self._heard(logits))
 
     def _peek_record(self):
         """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
@@ -696,7 +865,8 @@ class StreamingSession:
             if self._frontend is not None and (self.max_chunk < 2 or self._resampler is not None):
                 self._peek_thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
                 self._bufs.extend(self._peek_thirds)
-            self._peek_window = torch.empty(max(bufs[0].numel() for bufs in self.windows), device=self.device, dtype=torch.float32)
+            nbytes = max(bufs[0].numel() * bufs[0].element_size() for bufs in self.windows)
+            self._peek_window = torch.empty(-(-nbytes // 4), device=self.device, dtype=torch.float32)
             h, c = (None if t is None else torch.empty_like(t) for t in (self._carried.h, self._carried.c))
             prev_token = torch.empty(max(self.batch, 4), device=self.device, dtype=torch.int32)
             self._bufs.extend(t for t in (self._peek_window, h, c, prev_token) if t is not None)
@@ -738,19 +908,56 @@ class StreamingSession:
 
     def _result(self, outs, decode, final=False):
         """What push / push_audio / flush return for their steps' logits."""
-        logits = outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+        logits = self._join(outs)
         if decode in BEAM_DECODES:
             dec = self._decoder(decode)
             self._beam_frames += logits.shape[1]
-            pushed = dec.push(self._log_probs(logits))
+            pushed = dec.push(self._log_probs(self._heard(logits)))
             result = (logits, dec.finish()) if final else (logits,) + pushed
         else:
-            result = (logits, self._greedy(self._carried, logits)) if decode else logits
+            result = (logits, self._greedy(self._carried, self._heard(logits))) if decode else logits
         if self._confidence is not None:         # after the decode launches, ahead of the listeners; the only one that is told the end
-            self._confidence.push(logits, final=final)
+            self._confidence.push(self._heard(logits), final=final)
         for d in self._listeners:                # endpoint, keywords, segments; a step that emitted no frame launches nothing
-            d.push(logits)
+            d.push(self._heard(logits))
         return result
+
+    def _join(self, outs):
+        """The logits of several steps as one tensor.  bfloat16: over a buffer padded to 8 elements (``nbasr_flat``), as a step's are."""
+        if len(outs) == 1:
+            return outs[0]
+        if self.dtype != torch.bfloat16:
+            return torch.cat(outs, 1)
+        frames = sum(o.shape[1] for o in outs)
+        if frames == 0:
+            return outs[0]
+        logits = self._rounded(frames)
+        torch.cat(outs, 1, out=logits)
+        return logits
+
+    def _rounded(self, frames):
+        """(batch, frames, classes) bfloat16 logits over a buffer of whole 8-element chunks (``nbasr_flat``): what nbasr_convert works in."""
+        shape = (self.batch, frames, self.model.model[self.specs[-1].layer].out_features)
+        n = shape[0] * shape[1] * shape[2]
+        flat = torch.empty(max(hip.round_up8(n), 8), device=self.device, dtype=torch.bfloat16)
+        logits = flat[:n].view(shape)
+        logits.nbasr_flat = flat
+        return logits
+
+    def _heard(self, logits):
+        """What the decoders and listeners read: the logits themselves; of a bfloat16 session their fp32 widening (one nbasr_convert,
+        made once per result), so that every decode result is the offline function's on ``logits.float()``."""
+        if logits.dtype == torch.float32:
+            return logits
+        wide = getattr(logits, 'nbasr_wide', None)
+        if wide is None:
+            if logits.shape[1] == 0:
+                wide = torch.empty(logits.shape, device=self.device, dtype=torch.float32)
+            else:
+                flat = logits.nbasr_flat
+                wide = hip.convert(flat, torch.empty(flat.shape, device=self.device, dtype=torch.float32))[:logits.numel()].view(logits.shape)
+            logits.nbasr_wide = wide
+        return wide
 
     # ---- one step ----------------------------------------------------------------------------------------------------------------
     # Where a step builds stage k's new window is all that tells a committed step from the steps of a peek: ``place(k, current)``,
@@ -766,7 +973,11 @@ class StreamingSession:
         return [(off, min(self.max_chunk, n - off)) for off in range(0, n, self.max_chunk)]
 
     def _logits(self, frames):
-        return torch.empty(self.batch, frames, self.model.model[self.specs[-1].layer].out_features, device=self.device, dtype=torch.float32)
+        return torch.empty(self.batch, frames, self.model.model[self.specs[-1].layer].out_features, device=self.device, dtype=self.dtype)
+
+    def _place_peek(self, k, current):
+        """A peek's final step: every window in the one scratch window, seen as the stage's storage type."""
+        return self._peek_window if current.dtype == torch.float32 else self._peek_window.view(current.dtype)
 
     def _commit(self, chunk, off, n, final=False):
         return self._step(self._carried, chunk, off, n, final, self._place_other)
@@ -774,21 +985,33 @@ class StreamingSession:
     def _window(self, rec, k, plan, src, place):
         """Build stage k's window [a, b) from the retained frames of its current one and the new frames at ``src`` = (tensor, first
         column), in the buffer ``place`` names; returns (the window view, its frames)."""
+        sp = self.specs[k]
+        hist, dst, n_w = self._window_views(rec, k, plan, place, hip.round_up4)
+        absmax = self.absmax if (sp.kind == 'dense' and sp.blk > 0) else None
+        hip.stream_window(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst, absmax)
+        return dst, n_w
+
+    def _window16(self, rec, k, plan, src, place):
+        """``_window`` for bfloat16 rows (pitch: 8 frames; no range bound).  ``src`` is bfloat16, or the front-end's float32 frames at stage 0."""
+        hist, dst, n_w = self._window_views(rec, k, plan, place, hip.round_up8)
+        hip.stream_window_bf16(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst)
+        return dst, n_w
+
+    def _window_views(self, rec, k, plan, place, pitch):
+        """(the retained window or None, the new window in the buffer ``place`` names, its frames) of stage k; ``rec`` moves to the new one."""
         sp, B = self.specs[k], self.batch
         n_w = plan.b - plan.a
         if n_w > self.caps[k]:
             raise RuntimeError(f'stage {k}: window of {n_w} frames exceeds its capacity {self.caps[k]} (planner bound)')
         if len(self.windows[k]) == 1 and plan.n_hist:
             raise RuntimeError(f'stage {k} ({sp.kind}) has no context but retains {plan.n_hist} frames')
-        ld = hip.round_up4(n_w)
+        ld = pitch(n_w)
         old, ld_old = rec.window[k]
         new = place(k, old)
         rec.window[k] = (new, ld)
         dst = new[: B * sp.c_in * ld].view(B, sp.c_in, ld)
         hist = old[: B * sp.c_in * ld_old].view(B, sp.c_in, ld_old) if plan.n_hist else None
-        absmax = self.absmax if (sp.kind == 'dense' and sp.blk > 0) else None
-        hip.stream_window(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst, absmax)
-        return dst, n_w
+        return hist, dst, n_w
 
     def _step(self, rec, chunk, off, n, final, place):
         """One step of ``rec``'s planner on the device, ``rec`` advanced by it, every new window built where ``place`` says; returns the
@@ -796,11 +1019,11 @@ class StreamingSession:
         plans = rec.planner.step(n, final)
         rec.frames_in += n
         out = (chunk, off)                       # (tensor, first column) of the frames the next stage appends to its window
-        for k, (sp, plan, (body, windowed)) in enumerate(zip(self.specs, plans, self._bodies)):
+        for k, (sp, plan, (body, windower)) in enumerate(zip(self.specs, plans, self._bodies)):
             if plan is None:                     # nothing arrives, nothing is released (a later stage may still release at flush)
                 out = (None, 0)
                 continue
-            window = self._window(rec, k, plan, out, place) if windowed else out
+            window = windower(self, rec, k, plan, out, place) if windower is not None else out
             out = body(self, rec, k, sp, plan, window) if plan.compute else (None, 0)      # (not: only the window moves)
         logits = out if isinstance(out, torch.Tensor) else self._logits(0)
         rec.frames_out += logits.shape[1]
@@ -850,6 +1073,11 @@ class StreamingSession:
         gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
         hip.lstm_input_projection_packed(win, nf, self._packed['w_ih'], lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), gates,
                                          LSTM_HIDDEN, self.pointwise_ws)
+        return self._recur(rec, gates, nf)
+
+    def _recur(self, rec, gates, nf):
+        """The recurrence over ``nf`` frames of gates from the carried (h, c), which it advances; returns (h rows, 0)."""
+        B = self.batch
         h = self.h_out[: B * nf * LSTM_HIDDEN].view(B, nf, LSTM_HIDDEN)
         h_state, c_state, cont = rec.h[: B * LSTM_HIDDEN], rec.c[: B * LSTM_HIDDEN], rec.lstm_started
         hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], c_state, h, self.xcd_ws,
@@ -867,3 +1095,86 @@ class StreamingSession:
         win, n_w = window                        # without the LSTM: reads the encoder output's pitched rows
         head = self.model.model[sp.layer]
         return hip.linear_head_bct(win, n_w, head.weight.detach(), head.bias.detach(), self._logits(n_w))
+
+    # the bfloat16 session's bodies: bf16 rows, every LayerNorm where walk.WalkBf16 places it (_pack16)
+    def _pending(self, k, win, n_w):
+        """(stats, gamma, beta) of the LayerNorm stage k applies while it loads ``win``, its per-frame statistics taken here (one read
+        pass; per frame, so the chunking does not reach them), and its eps; (None, 0.0) where the window holds normalised rows."""
+        if self._ln_in[k] is None:
+            return None, 0.0
+        gamma, beta, eps = self._ln_in[k]
+        B, _, ld = win.shape
+        stats = self.stats[: B * 2 * ld].view(B, 2, ld)
+        return (stats, gamma, beta), eps
+
+    def _norm_out(self, k, out, frames):
+        """Stage k's own LayerNorm, where it is not left to the consumer's load: in place, or as the fp32 rows the head reads."""
+        if self._ln_out[k] is None:
+            return out
+        how, gamma, beta, eps = self._ln_out[k]
+        if how == 'inplace':
+            return hip.layernorm_channels(out, gamma, beta, out, frames, eps)
+        enc = self.enc32[: out.numel()].view(out.shape)
+        return hip.convert(out, enc) if gamma is None else hip.layernorm_channels(out, gamma, beta, enc, frames, eps)
+
+    def _dense16(self, rec, k, sp, plan, window):
+        win, n_w = window
+        conv, B = self.model.model[sp.layer], self.batch
+        t_out = out_length(n_w, sp.stride)
+        ld = hip.round_up8(t_out)
+        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
+        ln, eps = self._pending(k, win, n_w)     # (the image pass fills the statistics itself)
+        image = hip.bf16_image(win, self.image, n_w, ln and ln[1:], ln and ln[0], eps)
+        packed, rows, ftile = self._packed[sp.layer]
+        hip.dense_conv1d_bf16_img(image, B, sp.c_in, n_w, win.shape[2], packed, sp.c_out, conv.kernel_size, self._copies._f32(conv.conv.bias), out,
+                                  conv.strides, rows, ftile)
+        return self._norm_out(k, out, t_out), plan.c - plan.a // sp.stride
+
+    def _cell16(self, rec, k, sp, plan, window):
+        from .executor import node_into
+        win, n_w = window
+        cell, B = self.model.model[sp.layer], self.batch
+        ld = win.shape[2]
+        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
+        ln0, eps = self._pending(k, win, n_w)
+        if ln0 is not None:
+            hip.channel_stats(win, ln0[0], n_w, eps)
+        nodes = cell.nodes
+        if self._cell_mfma:
+            specs = [(self._packed[id(nd.op)], self._copies._f32(nd.op.conv.bias), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
+            hip.grouped_cell_mfma(win, specs, self._skip_mask, out, n_w, nodes[-1].op.groups, ln0)
+        else:                                    # one variant for every window: GC_FPL8 is the whole forward's choice for long rows
+            outs = [win]
+            for j, node in enumerate(nodes):
+                dst = out if j == len(nodes) - 1 else self.node_scratch[j % 2][: B * sp.c_out * ld].view(B, sp.c_out, ld)
+                outs.append(node_into(node, outs, n_w, dst, ln0, None, None, hip.GC_WPERM, self._copies))
+        return self._norm_out(k, out, n_w), plan.c - plan.a
+
+    def _lstm16(self, rec, k, sp, plan, window):
+        win, nf = window                         # un-normalised bf16 rows: the projection applies the last cell's LayerNorm on load
+        lstm, B, f32 = self.model.model[sp.layer], self.batch, self._copies._f32
+        ln, eps = self._pending(k, win, nf)
+        if ln is not None:
+            hip.channel_stats(win, ln[0], nf, eps)
+        gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
+        hip.lstm_input_projection_bf16(win, nf, self._packed['w_ih'], f32(lstm.bias_ih_l0), f32(lstm.bias_hh_l0), gates, LSTM_HIDDEN,
+                                       self.pointwise_ws, ln)
+        return self._recur(rec, gates, nf)
+
+    def _round_logits(self, frames, head_into):
+        """The head's fp32 logits (``head_into(out)`` writes them) rounded once to bfloat16, in whole 8-element chunks as ``WalkBf16.head``
+        does: the last chunk's padding is converted too and never returned."""
+        logits = self._rounded(frames)
+        n8 = logits.nbasr_flat.numel()
+        head_into(self.logits32[: logits.numel()].view(logits.shape))
+        hip.convert(self.logits32[:n8], logits.nbasr_flat)
+        return logits
+
+    def _head_of_lstm16(self, rec, k, sp, plan, source):
+        head, h, f32 = self.model.model[sp.layer], source[0], self._copies._f32
+        return self._round_logits(h.shape[1], lambda out: hip.linear_head(h, f32(head.weight), f32(head.bias), out))
+
+    def _head16(self, rec, k, sp, plan, window):
+        win, n_w = window                        # fp32 rows: the last LayerNorm's, or the widened encoder output
+        head, f32 = self.model.model[sp.layer], self._copies._f32
+        return self._round_logits(n_w, lambda out: hip.linear_head_bct(win, n_w, f32(head.weight), f32(head.bias), out))

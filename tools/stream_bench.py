@@ -1,11 +1,13 @@
 """Streaming inference cost (nb_asr_amd/streaming.py) on one GPU: ms per push and real-time factor at B in {1, 16, 64} and chunks of
 {40, 160} input frames, the benchmark's default architecture, against the whole-utterance forward of the same 1 000 frames.
 
-    python tools/stream_bench.py [--frames 1000] [--reps 3] [--out profiles/stream_bench.json]
+    python tools/stream_bench.py [--frames 1000] [--reps 3] [--dtype fp32|bf16] [--out profiles/stream_bench.json]
 
 A frame is 10 ms of audio (the reference's 10 ms hop): 1 000 frames = 10 s.  Real-time factor = GPU time of the session over the utterance
 / 10 s (lower is better; below 1 keeps up with live audio).  Streamed / whole = GPU time of every push + the flush over one model(x).
-One JSON line per configuration; with --out also the list as a JSON file.
+One JSON line per configuration; with --out also the list as a JSON file.  ``--dtype bf16``: the model cast to bfloat16 and its
+bfloat16 session (``StreamingSession(model, B, dtype=torch.bfloat16)``) against the bfloat16 whole forward; a row then also says so.
+``--launches``: also ``launches_per_push``, the library launches of one full-size mid-stream push, counted on a launch tape.
 
     python tools/stream_bench.py --peek [--pairs 50] [--reps 7] [--out profiles/streaming/peek_bench.json] [--baseline parent.json]
 
@@ -32,14 +34,33 @@ import nb_asr_amd as nb                          # noqa: E402
 from nb_asr_amd.weights import keyed_input       # noqa: E402
 
 
+def session_of(model, batch, chunk):
+    """The session of ``model`` as it is stored: the bfloat16 one for a bfloat16 model."""
+    from nb_asr_amd.streaming import StreamingSession
+    if next(model.parameters()).dtype == torch.bfloat16:
+        return StreamingSession(model, batch, chunk, dtype=torch.bfloat16)
+    return model.stream(batch=batch, max_chunk=chunk)
+
+
+def launches_of(call):
+    """Library launches ``call`` enqueues."""
+    entries = []
+    nb.hip.start_tape(entries)
+    try:
+        call()
+    finally:
+        nb.hip.stop_tape()
+    return len(entries)
+
+
 def peek_rows(model, args):
     """One row per (batch, chunk): ms per push, per peek() and per peek(decode='beam') in mid-stream, and their ratios."""
     dev, pairs, rows = 'cuda:0', args.pairs, []
     for b in (int(v) for v in args.batches.split(',')):
         for chunk in (int(v) for v in args.chunks.split(',')):
-            sess = model.stream(batch=b, max_chunk=chunk)
+            sess = session_of(model, b, chunk)
             lead = -(-(sess.lookahead_frames + chunk) // chunk)                  # pushes until every push emits frames
-            x = keyed_input(b, (lead + pairs) * chunk, seed=0).to(dev)
+            x = keyed_input(b, (lead + pairs) * chunk, seed=0).to(dev).to(next(model.parameters()).dtype)
             pieces = [x[:, :, i * chunk:(i + 1) * chunk].contiguous() for i in range(lead + pairs)]
             can_peek = hasattr(sess, 'peek')
 
@@ -95,11 +116,15 @@ def main():
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--batches', default='1,16,64')
     ap.add_argument('--chunks', default='40,160')
+    ap.add_argument('--dtype', choices=('fp32', 'bf16'), default='fp32')
+    ap.add_argument('--launches', action='store_true')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     benchlib.need_device('stream_bench.py')
     dev = 'cuda:0'
     model = benchlib.session_model(dev)
+    if args.dtype == 'bf16':
+        model = model.to(torch.bfloat16)
     rows = []
     if args.peek:
         if '--reps' not in sys.argv:
@@ -108,12 +133,12 @@ def main():
             rows = peek_rows(model, args)
     with torch.no_grad():
         for b in (int(v) for v in args.batches.split(',') if not args.peek):
-            x = keyed_input(b, args.frames, seed=0).to(dev)
+            x = keyed_input(b, args.frames, seed=0).to(dev).to(next(model.parameters()).dtype)
             model(x)                                                            # warm the whole forward (tapes, packed weights)
             model(x)
             whole_ms = benchlib.best_wall_ms(lambda: model(x), args.reps)
             for chunk in (int(v) for v in args.chunks.split(',')):
-                sess = model.stream(batch=b, max_chunk=chunk)
+                sess = session_of(model, b, chunk)
                 pieces = [x[:, :, i:i + chunk].contiguous() for i in range(0, args.frames, chunk)]
 
                 def run():
@@ -128,6 +153,13 @@ def main():
                        'stream_ms': round(ms, 2), 'whole_ms': round(whole_ms, 2), 'streamed_over_whole': round(ms / whole_ms, 2),
                        'rtf': round(ms / (args.frames * 10.0), 4), 'lookahead_frames': sess.lookahead_frames,
                        'session_mib': round(sess.buffer_bytes / 2**20, 1)}
+                if args.dtype != 'fp32':
+                    row['dtype'] = args.dtype
+                if args.launches:                                               # a full-size push in mid-stream, every stage at work
+                    sess.reset()
+                    for p in pieces[:-2]:
+                        sess.push(p)
+                    row['launches_per_push'] = launches_of(lambda: sess.push(pieces[-2]))
                 benchlib.emit(rows, row)
                 del sess
     benchlib.write_out(args.out, rows)
