@@ -291,26 +291,6 @@ class _Carried:
             self.h.copy_(other.h)
 
 
-class _Bf16Copies:
-    """What ``executor.node_into(..., copies=)`` reads of a bfloat16 session's derived weights: the four lookups of a ``ForwardPlan`` it
-    uses, answered from what the session packed once (``kept``: fp32 copies by ``id(parameter)``; ``packed``: the session's images)."""
-
-    def __init__(self, kept, packed, pointwise_ws):
-        self.kept, self.packed, self.pointwise_ws = kept, packed, pointwise_ws
-
-    def _f32(self, param):
-        return self.kept[id(param)]
-
-    def _packed_grouped(self, op):
-        return self.packed[id(op)]
-
-    def _packed_linear_bf16(self, w):
-        return self.packed[id(w)]
-
-    def _pointwise_bf16_ws(self, batch, c_in, ld):
-        return self.pointwise_ws
-
-
 # ------------------------------------------------------------------------------------------------------------------------------------
 class StreamingSession:
     """Chunk-by-chunk forward of ``model`` for a lockstep batch of ``batch`` utterances (``ASRModel.stream``).  Owns its windows, LSTM
@@ -378,35 +358,19 @@ class StreamingSession:
         self.beam_width, self.cutoff_top_n = int(beam_width), int(cutoff_top_n)
         self._lm = None if lm is None else fusion_table(lm, alpha, beta, p0.device)              # validated here; handed on as built
         self._beams = {}                          # decode value -> ctc.BeamSearchStream, made by the first push / peek that decodes so
-        self._peek = None                         # the _Carried a peek steps on; with its windows below, made by the first peek
-        self._peek_window = self._peek_thirds = self._peek_frames = None
+        self._peek = None                         # the _Carried a peek steps on; with the engine's peek windows, made by the first peek
+        self._peek_frames = None
         names = node_names(model.model[2])
         self.specs = stage_specs(names, model.use_rnn, model.use_norm)
         planner = StreamPlanner(self.specs)
         self.lookahead_frames = planner.lookahead
         self.caps = caps = planner.capacities(max_chunk)
         dev, B = self.device, batch
-        self._bufs = []
-
-        def buf(numel, dtype=torch.float32):
-            t = torch.empty(max(int(numel), 4), device=dev, dtype=dtype)
-            self._bufs.append(t)
-            return t
-
-        if self.dtype == torch.bfloat16:
-            h, c = self._allocate16(names, buf)
-        else:
-            h, c = self._allocate(names, buf)
-        self._carried = _Carried(planner, [bufs[0] for bufs in self.windows], h, c, buf(B, torch.int32)[:B])
-        # per stage kind (its body and what builds its window, None: no window -- the functions: bound methods would make the session hold itself)
-        cls = StreamingSession
-        if self.dtype == torch.bfloat16:
-            bodies = {'dense': (cls._dense16, cls._window16), 'cell': (cls._cell16, cls._window16), 'lstm': (cls._lstm16, cls._window16),
-                      'head': (cls._head_of_lstm16, None) if model.use_rnn else (cls._head16, cls._window)}
-        else:
-            bodies = {'dense': (cls._dense, cls._window), 'cell': (cls._cell, cls._window), 'lstm': (cls._lstm, cls._window),
-                      'head': (cls._head_of_lstm, None) if model.use_rnn else (cls._head, cls._window)}
-        self._bodies = [bodies[sp.kind] for sp in self.specs]
+        # everything a step touches on the device: the stage engine of the storage type.  The session holds it, it never holds the
+        # session, and no bound method of either is stored: a dropped session frees its memory at once (stream_stages.py)
+        from .stream_stages import StagesBf16, StagesF32
+        self._stages = stages = (StagesBf16 if self.dtype == torch.bfloat16 else StagesF32)(model, self.specs, caps, B, dev)
+        self._carried = _Carried(planner, [bufs[0] for bufs in stages.windows], stages.h, stages.c, stages.buf(B, torch.int32)[:B])
         # from the waveform: the front-end's stream and the staging buffer its frames are written to (one model step at a time)
         self._frontend, self._resampler, self.lookahead_samples = None, None, None
         if frontend is not None:
@@ -416,101 +380,20 @@ class StreamingSession:
                 raise ValueError(f'the model reads {FEATURES} features per frame, the front-end makes {frontend.n_mels}')
             self._frontend = frontend.stream(B)
             ld = hip.round_up4(max_chunk)
-            self._staging = buf(B * FEATURES * ld).view(B, FEATURES, ld)
+            self._staging = stages.buf(B * FEATURES * ld).view(B, FEATURES, ld)
             self.lookahead_samples = self._frontend.lookahead_samples + frontend.hop_length * self.lookahead_frames
             if resampler is not None:            # in samples at the input rate: the front-end's share converted, plus the resampler's own
                 self._resampler = resampler.stream(B)
                 self.lookahead_samples = -(-self.lookahead_samples * resampler.o // resampler.n) + resampler.lookahead_samples
-        self._pack16() if self.dtype == torch.bfloat16 else self._pack()
         self._confidence = self._listener(ConfidenceStream, confidence, 'the confidence rules')    # (steps ahead of the listeners, and knows the end)
         self._endpoint = self._listener(EndpointStream, endpoint, 'the endpoint rules')
         self._keywords = self._listener(KeywordStream, keywords, 'the keywords')
         self._segments = self._listener(SegmentStream, segments, 'the segment rules')
         # what hears the logits of every step, in launch order (after the decode launches): another detector is one more entry
         self._listeners = [d for d in (self._endpoint, self._keywords, self._segments) if d is not None]
+        # everything with ``state_bytes`` (the decoders join it as they are made): what ``buffer_bytes`` adds up
+        self._stateful = [d for d in (stages, self._frontend, self._resampler, self._confidence, *self._listeners) if d is not None]
         self.reset()
-
-    def _allocate(self, names, buf):
-        """The float32 session's windows and scratch (``buf``: the constructor's allocator); returns the LSTM's (h, c) or (None, None)."""
-        model, caps, B = self.model, self.caps, self.batch
-        # a pair of windows per stage (the head / LSTM input: one buffer, nothing is retained), scratch for outputs and node results
-        self.windows = []
-        out_elems = node_elems = need_pw = 0
-        has_linear = any(n[0] == 'linear' for n in names)
-        for sp, cap in zip(self.specs, caps):
-            ld = hip.round_up4(cap)
-            n = B * sp.c_in * ld
-            self.windows.append([buf(n), buf(n)] if sp.kind in ('dense', 'cell') else [buf(n)])
-            if sp.kind in ('dense', 'cell'):
-                out_elems = max(out_elems, B * sp.c_out * hip.round_up4(out_length(cap, sp.stride)))
-            if sp.kind == 'cell':
-                node_elems = max(node_elems, B * sp.c_out * ld)
-            if sp.kind == 'lstm' or (sp.kind == 'cell' and has_linear):
-                need_pw = max(need_pw, hip.load_library().nbasr_pointwise_workspace_bytes(B, sp.c_in, ld))
-        self.scratch = buf(out_elems)
-        self.node_scratch = [buf(node_elems), buf(node_elems)]
-        self.absmax = buf(B)[:B]
-        self.pointwise_ws = buf(need_pw, torch.uint8) if need_pw else None
-        h = c = None
-        if model.use_rnn:
-            lstm_cap = caps[[sp.kind for sp in self.specs].index('lstm')]
-            self.gates = buf(lstm_cap * B * 4 * LSTM_HIDDEN)
-            self.h_out = buf(B * lstm_cap * LSTM_HIDDEN)
-            h, c = buf(B * LSTM_HIDDEN), buf(B * LSTM_HIDDEN)
-            self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
-        return h, c
-
-    def _allocate16(self, names, buf):
-        """The bfloat16 session's windows and scratch: bf16 rows pitched to 8 frames in front of every encoder stage and the LSTM (fp32
-        rows in front of a head without LSTM: the last LayerNorm writes fp32), bf16 scratch; LayerNorm statistics, gates, h, c and the
-        logits ahead of their rounding in fp32.  Fixes what must not depend on a push's frame count: whether the cells run on the
-        matrix cores (they do where the stage's largest window fits; else every window takes the node launches)."""
-        from .walk import _CELL_SKIPS
-        from .ops import PadConvRelu, Identity
-        model, caps, B, lib = self.model, self.caps, self.batch, hip.load_library()
-        bf16 = torch.bfloat16
-        cells = [(sp, hip.round_up8(cap)) for sp, cap in zip(self.specs, caps) if sp.kind == 'cell']
-        nodes = model.model[cells[0][0].layer].nodes
-        conv_only = len(nodes) == 3 and all(isinstance(n.op, PadConvRelu) and n.op.groups > 1 for n in nodes)
-        self._cell_mfma = conv_only and all(hip.grouped_cell_mfma_fits(sp.c_in, ld, model.model[sp.layer].nodes[-1].op.groups) for sp, ld in cells)
-        self._skip_mask = sum(1 << bit for bit, (j, i) in enumerate(_CELL_SKIPS) if isinstance(nodes[j].branch_ops[i], Identity)) if conv_only else 0
-        self.windows = []
-        out_elems = node_elems = need_pw = image_bytes = 0
-        has_linear = any(n[0] == 'linear' for n in names)
-        for sp, cap in zip(self.specs, caps):
-            ld = hip.round_up8(cap)
-            n = B * sp.c_in * ld
-            if sp.kind == 'head':                # behind the LSTM: no window; without it: fp32 rows
-                self.windows.append([buf(0 if model.use_rnn else B * sp.c_in * hip.round_up4(cap))])
-                continue
-            self.windows.append([buf(n, bf16), buf(n, bf16)] if sp.kind in ('dense', 'cell') else [buf(n, bf16)])
-            if sp.kind in ('dense', 'cell'):
-                out_elems = max(out_elems, B * sp.c_out * hip.round_up8(out_length(cap, sp.stride)))
-            if sp.kind == 'dense':
-                image_bytes = max(image_bytes, lib.nbasr_bf16_image_bytes(B, sp.c_in, ld))
-            if sp.kind == 'cell' and not self._cell_mfma:
-                node_elems = max(node_elems, B * sp.c_out * ld)
-            if sp.kind == 'lstm' or (sp.kind == 'cell' and has_linear):
-                need_pw = max(need_pw, lib.nbasr_pointwise_bf16_workspace_bytes(B, sp.c_in, ld))
-        ld_max = hip.round_up8(max(caps))
-        self.scratch = buf(out_elems, bf16)
-        self.node_scratch = [buf(node_elems, bf16), buf(node_elems, bf16)] if node_elems else None
-        self.stats = buf(B * 2 * ld_max)         # per-frame (mean, rstd) of the LayerNorm a stage applies while it loads its window
-        self.image = buf(max(image_bytes, 16), torch.uint8)
-        self.pointwise_ws = buf(max(need_pw, 16), torch.uint8) if need_pw else None
-        classes = model.model[self.specs[-1].layer].out_features
-        self.logits32 = buf(hip.round_up8(B * max(caps[-2:]) * classes))
-        h = c = None
-        if model.use_rnn:
-            lstm_cap = caps[[sp.kind for sp in self.specs].index('lstm')]
-            self.gates = buf(lstm_cap * B * 4 * LSTM_HIDDEN)
-            self.h_out = buf(B * lstm_cap * LSTM_HIDDEN)
-            h, c = buf(B * LSTM_HIDDEN), buf(B * LSTM_HIDDEN)
-            self.xcd_ws = buf(hip.lstm_xcd_workspace_bytes(B, LSTM_HIDDEN), torch.uint8)
-        else:
-            sp, ld = cells[-1]
-            self.enc32 = buf(B * sp.c_out * ld)  # the encoder output as the head reads it
-        return h, c
 
     def _listener(self, stream, spec, what):
         """The ``ctc`` detector stream of this session for ``spec`` (its rules or keywords; None: no such listener)."""
@@ -549,108 +432,6 @@ class StreamingSession:
                              f'({resampler.max_pending} outputs can be pending): a peek has no place for more steps')
         return bound
 
-    # ---- weights ---------------------------------------------------------------------------------------------------------------
-    def _pack(self):
-        """Derived weight copies, made once; ``push`` refuses to run once a parameter has changed (its version counter moved)."""
-        import torch.nn as nn
-        from .ops import PadConvRelu, Linear
-        m = self.model.model
-        self._versions = [(p, p.data_ptr(), p._version) for p in self.model.parameters()]
-        self._packed = {}
-        with torch.no_grad():
-            for sp in self.specs:
-                if sp.kind == 'dense':
-                    conv = m[sp.layer]
-                    scheme = 'bf16x3' if sp.blk == 0 else 'f16x2'
-                    self._packed[sp.layer] = (scheme, hip.pack_dense_weights(conv.conv.weight.detach(), conv.strides, scheme))
-                elif sp.kind == 'cell':
-                    for node in m[sp.layer].nodes:
-                        if isinstance(node.op, PadConvRelu):
-                            self._packed[id(node.op)] = hip.pack_grouped_weights(node.op.conv.weight.detach().contiguous(), node.op.groups)
-                        elif isinstance(node.op, Linear):
-                            self._packed[id(node.op.linear)] = hip.pack_pointwise_weights(node.op.linear.weight.detach())
-                elif sp.kind == 'lstm':
-                    lstm = m[sp.layer]
-                    assert isinstance(lstm, nn.LSTM)
-                    self._packed['w_ih'] = hip.pack_pointwise_weights(lstm.weight_ih_l0.detach())
-                    self._packed['w_hh16'] = hip.lstm_pack_whh16(lstm.weight_hh_l0.detach().contiguous())
-        self._bufs.extend(t for t in self._packed.values() if isinstance(t, torch.Tensor))
-        self._bufs.extend(t for _, t in (v for v in self._packed.values() if isinstance(v, tuple)))
-
-    def _pack16(self):
-        """The bfloat16 session's derived weights, made once: the operand images the matrix-core kernels take (packed from fp32 copies
-        that are dropped again) and fp32 copies of what the kernels read as fp32 -- biases, gamma / beta, the head.  Also settles, per
-        stage, where its LayerNorm is applied (``walk.WalkBf16``'s placement): ``_ln_in[k]`` = (gamma, beta, eps) of the LayerNorm stage k
-        applies while it loads its un-normalised window, ``_ln_out[k]`` = (how, gamma, beta, eps) of the one it applies to its output
-        ('inplace': bf16 rows for a cell that starts with `linear`; 'f32': fp32 rows for the head, gamma None: only widened)."""
-        import torch.nn as nn
-        from . import tiles
-        from .ops import PadConvRelu, Linear
-        from .walk import cheap_consumer
-        m, B = self.model.model, self.batch
-        self._versions = [(p, p.data_ptr(), p._version) for p in self.model.parameters()]
-        self._packed, kept = {}, {}
-
-        def f32(p):
-            return p.detach().float().contiguous()
-
-        def keep(p):
-            if id(p) not in kept:
-                kept[id(p)] = f32(p)
-            return kept[id(p)]
-
-        norms = [None] * len(self.specs)         # the LayerNorm behind each stage
-        with torch.no_grad():
-            for k, (sp, cap) in enumerate(zip(self.specs, self.caps)):
-                if sp.kind == 'dense':
-                    conv, norms[k] = m[sp.layer], m[sp.layer + 1]
-                    # the row tile of the stage's largest window, for every push: one packed image (every tiling gives the same bits)
-                    rows, ftile = tiles.bf16_tile(B, sp.c_out, out_length(cap, sp.stride))
-                    self._packed[sp.layer] = (hip.pack_dense_weights_bf16(f32(conv.conv.weight), conv.strides, rows), rows, ftile)
-                    keep(conv.conv.bias)
-                elif sp.kind == 'cell':
-                    cell = m[sp.layer]
-                    norms[k] = cell.norm_layer if cell.use_norm else None
-                    for node in cell.nodes:
-                        op = node.op
-                        if isinstance(op, PadConvRelu):
-                            w = f32(op.conv.weight)
-                            self._packed[id(op)] = hip.grouped_cell_mfma_pack(w, op.groups) if self._cell_mfma else hip.pack_grouped_weights(w, op.groups)
-                            keep(op.conv.bias)
-                        elif isinstance(op, Linear):
-                            self._packed[id(op.linear.weight)] = hip.pack_pointwise_weights_bf16(f32(op.linear.weight))
-                            keep(op.linear.bias)
-                elif sp.kind == 'lstm':
-                    lstm = m[sp.layer]
-                    assert isinstance(lstm, nn.LSTM)
-                    self._packed['w_ih'] = hip.pack_pointwise_weights_bf16(f32(lstm.weight_ih_l0))
-                    self._packed['w_hh16'] = hip.lstm_pack_whh16(f32(lstm.weight_hh_l0))
-                    keep(lstm.bias_ih_l0), keep(lstm.bias_hh_l0)
-                else:
-                    keep(m[sp.layer].weight), keep(m[sp.layer].bias)
-            self._ln_in, self._ln_out = [None] * len(self.specs), [None] * len(self.specs)
-            for k, norm in enumerate(norms):
-                if self.specs[k].kind not in ('dense', 'cell'):
-                    continue
-                nxt = self.specs[k + 1]
-                affine = (None, None, 0.0) if norm is None else (keep(norm.weight), keep(norm.bias), norm.eps)
-                if nxt.kind == 'head':
-                    self._ln_out[k] = ('f32',) + affine
-                elif norm is not None and nxt.kind == 'cell' and not cheap_consumer(m[nxt.layer]):
-                    self._ln_out[k] = ('inplace',) + affine
-                elif norm is not None:           # a conv-only cell, a dense conv's operand image, the LSTM's projection: on load
-                    self._ln_in[k + 1] = affine
-        self._copies = _Bf16Copies(kept, self._packed, self.pointwise_ws)
-        self._bufs.extend(kept.values())
-        self._bufs.extend(v[0] if isinstance(v, tuple) else v for v in self._packed.values())
-
-    def _check_params(self):
-        for p, ptr, ver in self._versions:
-            if p.data_ptr() != ptr or p._version != ver:
-                raise ValueError('a parameter of the model changed after the session packed its weights: create a new session')
-        if len(self._versions) != len(list(self.model.parameters())):
-            raise ValueError('the model\'s parameters changed after the session packed its weights: create a new session')
-
     # ---- public ----------------------------------------------------------------------------------------------------------------
     frames_in = property(lambda self: self._carried.frames_in, doc='input frames taken in this utterance')
     frames_out = property(lambda self: self._carried.frames_out, doc='logit frames returned in this utterance')
@@ -659,13 +440,10 @@ class StreamingSession:
     @property
     def buffer_bytes(self):
         """Device bytes the session owns (windows, scratch, LSTM state, packed weights, the beam search state once it exists, with a
-        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's, with ``segments=``
-        the segmenter's, with ``confidence=`` the estimator's, and from the first ``peek`` on the peek's scratch window, state copies and beam workspace)."""
-        return (sum(t.numel() * t.element_size() for t in self._bufs)
-                + sum(d.state_bytes + d.peek_bytes for d in self._beams.values())
-                + (self._frontend.state_bytes if self._frontend is not None else 0)
-                + (self._resampler.state_bytes if self._resampler is not None else 0)
-                + sum(d.state_bytes for d in self._listeners) + (self._confidence.state_bytes if self._confidence is not None else 0))
+        front-end its sample tails and the staging buffer, with ``endpoint=`` the endpointer's state, with ``keywords=`` the spotter's,
+        with ``segments=`` the segmenter's, with ``confidence=`` the estimator's, and from the first ``peek`` on the peek's scratch
+        window, state copies and beam workspace)."""
+        return sum(d.state_bytes for d in self._stateful) + sum(d.peek_bytes for d in self._beams.values())
 
     @property
     def endpoint(self):
@@ -712,8 +490,9 @@ class StreamingSession:
             d.reset()
 
     def push(self, chunk, decode=False):
-        """Feed (batch, 80, n) frames of the session's dtype (float32; bfloat16 in a bfloat16 session); returns the logits (batch, m, 49) that became final (m >= 0) -- with ``decode=True`` also
-        the greedy CTC tokens of those frames (a list of int32 CPU tensors), repeats collapsed across pushes.  ``decode='beam'`` returns
+        """Feed (batch, 80, n) frames of the session's dtype (float32; bfloat16 in a bfloat16 session); returns the logits (batch, m, 49)
+        that became final (m >= 0) -- with ``decode=True`` also the greedy CTC tokens of those frames (a list of int32 CPU tensors),
+        repeats collapsed across pushes.  ``decode='beam'`` returns
         ``(logits, committed, partial)``: the prefix beam search of ``ctc.beam_decode`` run over the log-probabilities of the final frames
         (``ctc.BeamSearchStream``): tokens that are now final, and the best beam's tokens after all committed ones.
         ``decode='beam-timed'`` returns ``(logits, committed, partial, committed_frames, partial_frames)``: the same search with each
@@ -723,9 +502,8 @@ class StreamingSession:
             raise ValueError('push after flush: call reset() to start the next utterance')
         if not isinstance(chunk, torch.Tensor) or chunk.dim() != 3 or chunk.shape[0] != self.batch or chunk.shape[1] != FEATURES:
             raise ValueError(f'expected a ({self.batch}, {FEATURES}, frames) chunk, got {tuple(getattr(chunk, "shape", ()))}')
-        if chunk.dtype != self.dtype or chunk.device != self.device:
-            name = 'bfloat16' if self.dtype == torch.bfloat16 else 'float32'
-            raise ValueError(f'the chunk must be {name} on {self.device} (got {chunk.dtype} on {chunk.device})')
+        if not self._stages.accepts(chunk):
+            raise ValueError(f'the chunk must be {self._stages.name} on {self.device} (got {chunk.dtype} on {chunk.device})')
         if self._fed == 'audio':
             raise ValueError('push after push_audio: an utterance is fed features or samples, not both (reset() starts the next one)')
         self._begin(decode)
@@ -745,7 +523,7 @@ class StreamingSession:
         if self._fed == 'features':
             raise ValueError('push_audio after push: an utterance is fed features or samples, not both (reset() starts the next one)')
         if (not isinstance(wave_chunk, torch.Tensor) or wave_chunk.dim() != 2 or wave_chunk.shape[0] != self.batch
-                or wave_chunk.dtype != torch.float32 or wave_chunk.device != self.device):
+                or (wave_chunk.dtype, wave_chunk.device) != (torch.float32, self.device)):
             raise ValueError(f'expected a ({self.batch}, samples) float32 chunk on {self.device}, got {tuple(getattr(wave_chunk, "shape", ()))} '
                              f'{getattr(wave_chunk, "dtype", None)} on {getattr(wave_chunk, "device", None)}')
         self._begin(decode)
@@ -787,36 +565,36 @@ class StreamingSession:
         (behind a resampler: unless its pending outputs would carry the front-end past ``win // 2`` samples, as they would at a flush)."""
         if self._flushed:
             raise ValueError('peek after flush: call reset() to start the next utterance')
-        self._check_params()
+        self._stages.check_params()
         if decode in BEAM_DECODES:
             self._beam_check(decode)
         resampled = self._resampler is not None and self._fed == 'audio'
         # behind a resampler its pending outputs come with the end: they can carry the front-end past win // 2 before any frame is in
         endable = resampled and self._frontend.samples_in + self._resampler.pending > self._frontend.win // 2
         if self.frames_in == 0 and not endable:  # (with a front-end: at most win // 2 samples so far, too few to end an utterance)
-            logits = self._logits(0)
+            logits = self._stages.logits(0)
             if decode in BEAM_DECODES:
                 return logits, empty_beam_result(self.batch, self.beam_width, self.device, decode == 'beam-timed')
             return (logits, [torch.zeros(0, dtype=torch.int32) for _ in range(self.batch)]) if decode else logits
-        pk = self._peek_record()
+        pk, stages = self._peek_record(), self._stages
         outs = []
-        places = (self._place_other, lambda k, current: self._peek_thirds[k])
+        places = (stages.place_other, stages.place_third)
         if resampled:                            # flush's steps: the frames the resampler's last outputs complete, then the end frames
             fs, extra = self._frontend, self._resampler.peek()
             m = fs.peek(out=(self._staging, 0), extra=extra).shape[2]
             first = frames_final(fs.samples_in + extra.shape[1], fs.hop, fs.win) - fs.frames_out
             cuts = [(off, n) for off, n in ((0, first), (first, m - first)) if n]          # (each at most end_frames <= max_chunk)
-            outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(cuts)]
+            outs = [stages.step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(cuts)]
         elif self._fed == 'audio':               # the front-end's end frames as uncommitted pushes, then the final step
             m = self._frontend.peek(out=(self._staging, 0)).shape[2]
-            outs = [self._step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(self._cuts(m))]
-        outs.append(self._step(pk, None, 0, 0, True, self._place_peek))
-        logits = self._join(outs)
+            outs = [stages.step(pk, self._staging, off, n, False, places[i]) for i, (off, n) in enumerate(self._cuts(m))]
+        outs.append(stages.step(pk, None, 0, 0, True, stages.place_peek))
+        logits = stages.join(outs)
         if decode in BEAM_DECODES:
             dec = self._decoder(decode)
             dec.reserve_peek(self._peek_frames, logits.shape[2])
-            return logits, dec.peek(self._log_probs(self._heard(logits)))
-        return (logits, self._greedy(pk, self._heard(logits))) if decode else logits
+            return logits, dec.peek(self._log_probs(stages.heard(logits)))
+        return (logits, self._greedy(pk, stages.heard(logits))) if decode else logits
 
     def peek_endpoint(self, decode=False):
         """``(peek(decode), EndpointResult)``: one peek of the model, then the endpointer's peek over the provisional logits on top of its
@@ -855,23 +633,16 @@ class StreamingSession:
             raise ValueError(refusal)
         peeked = self.peek(decode)
         logits = peeked if isinstance(peeked, torch.Tensor) else peeked[0]
-        return peeked, listener.peek(self._heard(logits))
+        return peeked, listener.peek(self._stages.heard(logits))
 
     def _peek_record(self):
         """The record a peek steps on, in the committed one's present state.  The first peek allocates it, with the windows only a peek
         builds: the scratch window (sized for the largest stage window) and, for a session that pushes the front-end's two end frames
         in two steps (``max_chunk`` 1), a third buffer per stage."""
         if self._peek is None:
-            if self._frontend is not None and (self.max_chunk < 2 or self._resampler is not None):
-                self._peek_thirds = [torch.empty_like(bufs[0]) for bufs in self.windows]
-                self._bufs.extend(self._peek_thirds)
-            nbytes = max(bufs[0].numel() * bufs[0].element_size() for bufs in self.windows)
-            self._peek_window = torch.empty(-(-nbytes // 4), device=self.device, dtype=torch.float32)
-            h, c = (None if t is None else torch.empty_like(t) for t in (self._carried.h, self._carried.c))
-            prev_token = torch.empty(max(self.batch, 4), device=self.device, dtype=torch.int32)
-            self._bufs.extend(t for t in (self._peek_window, h, c, prev_token) if t is not None)
+            thirds = self._frontend is not None and (self.max_chunk < 2 or self._resampler is not None)
             self._peek_frames = self._carried.planner.max_provisional_frames(self.end_frames)      # the beam peek workspace is sized once, for these
-            self._peek = _Carried(self._carried.planner.copy(), [], h, c, prev_token[:self.batch])
+            self._peek = _Carried(self._carried.planner.copy(), [], *self._stages.peek_state(self._carried, thirds))
         self._peek.refresh(self._carried)
         return self._peek
 
@@ -884,7 +655,7 @@ class StreamingSession:
 
     def _begin(self, decode):
         """Before a push or flush moves a frame: refuse stale weights, and what its beam search could not do."""
-        self._check_params()
+        self._stages.check_params()
         if decode in BEAM_DECODES:
             self._beam_check(decode)
             self._beam_mode = decode
@@ -894,6 +665,7 @@ class StreamingSession:
         if decode not in self._beams:
             self._beams[decode] = BeamSearchStream(self.batch, self.beam_width, 0, self.cutoff_top_n, self.device,
                                                    timesteps=decode == 'beam-timed', lm=self._lm)
+            self._stateful.append(self._beams[decode])
         return self._beams[decode]
 
     @staticmethod
@@ -908,273 +680,24 @@ class StreamingSession:
 
     def _result(self, outs, decode, final=False):
         """What push / push_audio / flush return for their steps' logits."""
-        logits = self._join(outs)
+        logits, heard = self._stages.join(outs), self._stages.heard
         if decode in BEAM_DECODES:
             dec = self._decoder(decode)
             self._beam_frames += logits.shape[1]
-            pushed = dec.push(self._log_probs(self._heard(logits)))
+            pushed = dec.push(self._log_probs(heard(logits)))
             result = (logits, dec.finish()) if final else (logits,) + pushed
         else:
-            result = (logits, self._greedy(self._carried, self._heard(logits))) if decode else logits
+            result = (logits, self._greedy(self._carried, heard(logits))) if decode else logits
         if self._confidence is not None:         # after the decode launches, ahead of the listeners; the only one that is told the end
-            self._confidence.push(self._heard(logits), final=final)
+            self._confidence.push(heard(logits), final=final)
         for d in self._listeners:                # endpoint, keywords, segments; a step that emitted no frame launches nothing
-            d.push(self._heard(logits))
+            d.push(heard(logits))
         return result
-
-    def _join(self, outs):
-        """The logits of several steps as one tensor.  bfloat16: over a buffer padded to 8 elements (``nbasr_flat``), as a step's are."""
-        if len(outs) == 1:
-            return outs[0]
-        if self.dtype != torch.bfloat16:
-            return torch.cat(outs, 1)
-        frames = sum(o.shape[1] for o in outs)
-        if frames == 0:
-            return outs[0]
-        logits = self._rounded(frames)
-        torch.cat(outs, 1, out=logits)
-        return logits
-
-    def _rounded(self, frames):
-        """(batch, frames, classes) bfloat16 logits over a buffer of whole 8-element chunks (``nbasr_flat``): what nbasr_convert works in."""
-        shape = (self.batch, frames, self.model.model[self.specs[-1].layer].out_features)
-        n = shape[0] * shape[1] * shape[2]
-        flat = torch.empty(max(hip.round_up8(n), 8), device=self.device, dtype=torch.bfloat16)
-        logits = flat[:n].view(shape)
-        logits.nbasr_flat = flat
-        return logits
-
-    def _heard(self, logits):
-        """What the decoders and listeners read: the logits themselves; of a bfloat16 session their fp32 widening (one nbasr_convert,
-        made once per result), so that every decode result is the offline function's on ``logits.float()``."""
-        if logits.dtype == torch.float32:
-            return logits
-        wide = getattr(logits, 'nbasr_wide', None)
-        if wide is None:
-            if logits.shape[1] == 0:
-                wide = torch.empty(logits.shape, device=self.device, dtype=torch.float32)
-            else:
-                flat = logits.nbasr_flat
-                wide = hip.convert(flat, torch.empty(flat.shape, device=self.device, dtype=torch.float32))[:logits.numel()].view(logits.shape)
-            logits.nbasr_wide = wide
-        return wide
-
-    # ---- one step ----------------------------------------------------------------------------------------------------------------
-    # Where a step builds stage k's new window is all that tells a committed step from the steps of a peek: ``place(k, current)``,
-    # ``current`` the buffer that holds the stage's window now.  A committed step and a peek's first push: the pair's other buffer
-    # (``_place_other``).  A peek's second push (``max_chunk`` 1 with a front-end), whose window the final step still reads: the stage's
-    # third buffer.  A peek's final step, whose windows are consumed by their own stage at once and never retained: the scratch window.
-    def _place_other(self, k, current):
-        bufs = self.windows[k]                   # (a one-buffer stage retains nothing: it rebuilds in place)
-        return bufs[0] if current is bufs[-1] else bufs[-1]
 
     def _cuts(self, n):
         """(first frame, frames) of the steps that take n frames."""
         return [(off, min(self.max_chunk, n - off)) for off in range(0, n, self.max_chunk)]
 
-    def _logits(self, frames):
-        return torch.empty(self.batch, frames, self.model.model[self.specs[-1].layer].out_features, device=self.device, dtype=self.dtype)
-
-    def _place_peek(self, k, current):
-        """A peek's final step: every window in the one scratch window, seen as the stage's storage type."""
-        return self._peek_window if current.dtype == torch.float32 else self._peek_window.view(current.dtype)
-
     def _commit(self, chunk, off, n, final=False):
-        return self._step(self._carried, chunk, off, n, final, self._place_other)
-
-    def _window(self, rec, k, plan, src, place):
-        """Build stage k's window [a, b) from the retained frames of its current one and the new frames at ``src`` = (tensor, first
-        column), in the buffer ``place`` names; returns (the window view, its frames)."""
-        sp = self.specs[k]
-        hist, dst, n_w = self._window_views(rec, k, plan, place, hip.round_up4)
-        absmax = self.absmax if (sp.kind == 'dense' and sp.blk > 0) else None
-        hip.stream_window(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst, absmax)
-        return dst, n_w
-
-    def _window16(self, rec, k, plan, src, place):
-        """``_window`` for bfloat16 rows (pitch: 8 frames; no range bound).  ``src`` is bfloat16, or the front-end's float32 frames at stage 0."""
-        hist, dst, n_w = self._window_views(rec, k, plan, place, hip.round_up8)
-        hip.stream_window_bf16(hist, plan.hist_off, plan.n_hist, src[0], src[1], plan.n_new, dst)
-        return dst, n_w
-
-    def _window_views(self, rec, k, plan, place, pitch):
-        """(the retained window or None, the new window in the buffer ``place`` names, its frames) of stage k; ``rec`` moves to the new one."""
-        sp, B = self.specs[k], self.batch
-        n_w = plan.b - plan.a
-        if n_w > self.caps[k]:
-            raise RuntimeError(f'stage {k}: window of {n_w} frames exceeds its capacity {self.caps[k]} (planner bound)')
-        if len(self.windows[k]) == 1 and plan.n_hist:
-            raise RuntimeError(f'stage {k} ({sp.kind}) has no context but retains {plan.n_hist} frames')
-        ld = pitch(n_w)
-        old, ld_old = rec.window[k]
-        new = place(k, old)
-        rec.window[k] = (new, ld)
-        dst = new[: B * sp.c_in * ld].view(B, sp.c_in, ld)
-        hist = old[: B * sp.c_in * ld_old].view(B, sp.c_in, ld_old) if plan.n_hist else None
-        return hist, dst, n_w
-
-    def _step(self, rec, chunk, off, n, final, place):
-        """One step of ``rec``'s planner on the device, ``rec`` advanced by it, every new window built where ``place`` says; returns the
-        step's logits."""
-        plans = rec.planner.step(n, final)
-        rec.frames_in += n
-        out = (chunk, off)                       # (tensor, first column) of the frames the next stage appends to its window
-        for k, (sp, plan, (body, windower)) in enumerate(zip(self.specs, plans, self._bodies)):
-            if plan is None:                     # nothing arrives, nothing is released (a later stage may still release at flush)
-                out = (None, 0)
-                continue
-            window = windower(self, rec, k, plan, out, place) if windower is not None else out
-            out = body(self, rec, k, sp, plan, window) if plan.compute else (None, 0)      # (not: only the window moves)
-        logits = out if isinstance(out, torch.Tensor) else self._logits(0)
-        rec.frames_out += logits.shape[1]
-        return logits
-
-    # the stage bodies: (record, stage index, spec, plan, (window view, its frames)) -> (tensor, first column) of the outputs kept, or the logits
-    def _dense(self, rec, k, sp, plan, window):
-        win, n_w = window
-        m, B = self.model.model, self.batch
-        conv, norm = m[sp.layer], m[sp.layer + 1]
-        t_out = out_length(n_w, sp.stride)
-        ld = hip.round_up4(t_out)
-        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-        scheme, packed = self._packed[sp.layer]
-        hip.dense_conv1d_fused_packed(win, n_w, packed, sp.c_out, conv.kernel_size, conv.conv.bias.detach(), (), out, conv.strides,
-                                      None, scheme, self.absmax if scheme == 'f16x2' else None)
-        hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, t_out, norm.eps)
-        return out, plan.c - plan.a // sp.stride
-
-    def _cell(self, rec, k, sp, plan, window):
-        from .executor import node_into
-        from .walk import fused_cell
-        win, n_w = window
-        cell, B = self.model.model[sp.layer], self.batch
-        ld = win.shape[2]
-        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-        nodes = cell.nodes
-        groups = getattr(nodes[-1].op, 'groups', 0)
-        fused, mask = fused_cell(cell, ld)
-        if fused:                                # the executor's one-launch cell (bit-identical to the three node launches)
-            specs = [(self._packed[id(nd.op)], nd.op.conv.bias.detach(), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
-            hip.grouped_cell_fused(win, specs, mask, out, n_w, groups)
-        else:
-            lin_ctx = (lambda lin: self._packed[id(lin)], lambda c_in, ld_: self.pointwise_ws)
-            outs = [win]
-            for j, node in enumerate(nodes):
-                dst = out if j == len(nodes) - 1 else self.node_scratch[j % 2][: B * sp.c_out * ld].view(B, sp.c_out, ld)
-                outs.append(node_into(node, outs, n_w, dst, None, None, lin_ctx, 0))
-        if cell.use_norm:
-            norm = cell.norm_layer
-            hip.layernorm_channels(out, norm.weight.detach(), norm.bias.detach(), out, n_w, norm.eps)
-        return out, plan.c - plan.a
-
-    def _lstm(self, rec, k, sp, plan, window):
-        win, nf = window                         # no context: the window holds exactly the new frames
-        lstm, B = self.model.model[sp.layer], self.batch
-        gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
-        hip.lstm_input_projection_packed(win, nf, self._packed['w_ih'], lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), gates,
-                                         LSTM_HIDDEN, self.pointwise_ws)
-        return self._recur(rec, gates, nf)
-
-    def _recur(self, rec, gates, nf):
-        """The recurrence over ``nf`` frames of gates from the carried (h, c), which it advances; returns (h rows, 0)."""
-        B = self.batch
-        h = self.h_out[: B * nf * LSTM_HIDDEN].view(B, nf, LSTM_HIDDEN)
-        h_state, c_state, cont = rec.h[: B * LSTM_HIDDEN], rec.c[: B * LSTM_HIDDEN], rec.lstm_started
-        hip.lstm_recurrence_frames16_state(gates, self._packed['w_hh16'], c_state, h, self.xcd_ws,
-                                           h_state if cont else None, hip.LSTM_CONTINUE if cont else 0)
-        rec.lstm_started = True
-        # h_n = the last frame's h becomes the next call's h0 (h_out seen as one row of nf * H floats per utterance)
-        hip.stream_window(None, 0, 0, h.view(B, 1, nf * LSTM_HIDDEN), (nf - 1) * LSTM_HIDDEN, LSTM_HIDDEN, h_state.view(B, 1, LSTM_HIDDEN))
-        return h, 0
-
-    def _head_of_lstm(self, rec, k, sp, plan, source):
-        head, h = self.model.model[sp.layer], source[0]              # the LSTM's (batch, frames, hidden) rows, no window
-        return hip.linear_head(h, head.weight.detach(), head.bias.detach(), self._logits(h.shape[1]))
-
-    def _head(self, rec, k, sp, plan, window):
-        win, n_w = window                        # without the LSTM: reads the encoder output's pitched rows
-        head = self.model.model[sp.layer]
-        return hip.linear_head_bct(win, n_w, head.weight.detach(), head.bias.detach(), self._logits(n_w))
-
-    # the bfloat16 session's bodies: bf16 rows, every LayerNorm where walk.WalkBf16 places it (_pack16)
-    def _pending(self, k, win, n_w):
-        """(stats, gamma, beta) of the LayerNorm stage k applies while it loads ``win``, its per-frame statistics taken here (one read
-        pass; per frame, so the chunking does not reach them), and its eps; (None, 0.0) where the window holds normalised rows."""
-        if self._ln_in[k] is None:
-            return None, 0.0
-        gamma, beta, eps = self._ln_in[k]
-        B, _, ld = win.shape
-        stats = self.stats[: B * 2 * ld].view(B, 2, ld)
-        return (stats, gamma, beta), eps
-
-    def _norm_out(self, k, out, frames):
-        """Stage k's own LayerNorm, where it is not left to the consumer's load: in place, or as the fp32 rows the head reads."""
-        if self._ln_out[k] is None:
-            return out
-        how, gamma, beta, eps = self._ln_out[k]
-        if how == 'inplace':
-            return hip.layernorm_channels(out, gamma, beta, out, frames, eps)
-        enc = self.enc32[: out.numel()].view(out.shape)
-        return hip.convert(out, enc) if gamma is None else hip.layernorm_channels(out, gamma, beta, enc, frames, eps)
-
-    def _dense16(self, rec, k, sp, plan, window):
-        win, n_w = window
-        conv, B = self.model.model[sp.layer], self.batch
-        t_out = out_length(n_w, sp.stride)
-        ld = hip.round_up8(t_out)
-        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-        ln, eps = self._pending(k, win, n_w)     # (the image pass fills the statistics itself)
-        image = hip.bf16_image(win, self.image, n_w, ln and ln[1:], ln and ln[0], eps)
-        packed, rows, ftile = self._packed[sp.layer]
-        hip.dense_conv1d_bf16_img(image, B, sp.c_in, n_w, win.shape[2], packed, sp.c_out, conv.kernel_size, self._copies._f32(conv.conv.bias), out,
-                                  conv.strides, rows, ftile)
-        return self._norm_out(k, out, t_out), plan.c - plan.a // sp.stride
-
-    def _cell16(self, rec, k, sp, plan, window):
-        from .executor import node_into
-        win, n_w = window
-        cell, B = self.model.model[sp.layer], self.batch
-        ld = win.shape[2]
-        out = self.scratch[: B * sp.c_out * ld].view(B, sp.c_out, ld)
-        ln0, eps = self._pending(k, win, n_w)
-        if ln0 is not None:
-            hip.channel_stats(win, ln0[0], n_w, eps)
-        nodes = cell.nodes
-        if self._cell_mfma:
-            specs = [(self._packed[id(nd.op)], self._copies._f32(nd.op.conv.bias), nd.op.kernel_size, nd.op.dilation) for nd in nodes]
-            hip.grouped_cell_mfma(win, specs, self._skip_mask, out, n_w, nodes[-1].op.groups, ln0)
-        else:                                    # one variant for every window: GC_FPL8 is the whole forward's choice for long rows
-            outs = [win]
-            for j, node in enumerate(nodes):
-                dst = out if j == len(nodes) - 1 else self.node_scratch[j % 2][: B * sp.c_out * ld].view(B, sp.c_out, ld)
-                outs.append(node_into(node, outs, n_w, dst, ln0, None, None, hip.GC_WPERM, self._copies))
-        return self._norm_out(k, out, n_w), plan.c - plan.a
-
-    def _lstm16(self, rec, k, sp, plan, window):
-        win, nf = window                         # un-normalised bf16 rows: the projection applies the last cell's LayerNorm on load
-        lstm, B, f32 = self.model.model[sp.layer], self.batch, self._copies._f32
-        ln, eps = self._pending(k, win, nf)
-        if ln is not None:
-            hip.channel_stats(win, ln[0], nf, eps)
-        gates = self.gates[: nf * B * 4 * LSTM_HIDDEN]
-        hip.lstm_input_projection_bf16(win, nf, self._packed['w_ih'], f32(lstm.bias_ih_l0), f32(lstm.bias_hh_l0), gates, LSTM_HIDDEN,
-                                       self.pointwise_ws, ln)
-        return self._recur(rec, gates, nf)
-
-    def _round_logits(self, frames, head_into):
-        """The head's fp32 logits (``head_into(out)`` writes them) rounded once to bfloat16, in whole 8-element chunks as ``WalkBf16.head``
-        does: the last chunk's padding is converted too and never returned."""
-        logits = self._rounded(frames)
-        n8 = logits.nbasr_flat.numel()
-        head_into(self.logits32[: logits.numel()].view(logits.shape))
-        hip.convert(self.logits32[:n8], logits.nbasr_flat)
-        return logits
-
-    def _head_of_lstm16(self, rec, k, sp, plan, source):
-        head, h, f32 = self.model.model[sp.layer], source[0], self._copies._f32
-        return self._round_logits(h.shape[1], lambda out: hip.linear_head(h, f32(head.weight), f32(head.bias), out))
-
-    def _head16(self, rec, k, sp, plan, window):
-        win, n_w = window                        # fp32 rows: the last LayerNorm's, or the widened encoder output
-        head, f32 = self.model.model[sp.layer], self._copies._f32
-        return self._round_logits(n_w, lambda out: hip.linear_head_bct(win, n_w, f32(head.weight), f32(head.bias), out))
+        """A committed step: the session's own record, every stage's window built in its pair's other buffer."""
+        return self._stages.step(self._carried, chunk, off, n, final, self._stages.place_other)

@@ -184,10 +184,10 @@ def test_against_the_whole_forward():
         differing = int((bits(got) != bits(want)).sum())
         print(f'{tag}: {differing} of {got.numel()} logits differ from model16(x), largest difference {float((got.float() - want.float()).abs().max()):.3e}')
         cell, last = m.model[2], m.model[2].nodes[-1].op
-        by_product = (not session(tag)._cell_mfma and cell.use_norm and cheap_consumer(cell) and isinstance(last, PadConvRelu) and last.groups > 1)
+        by_product = (not session(tag)._stages.cell_mfma and cell.use_norm and cheap_consumer(cell) and isinstance(last, PadConvRelu) and last.groups > 1)
         assert got.shape == want.shape and got.dtype == want.dtype
         assert by_product or torch.equal(got, want), tag
-    assert session('D_lively_b2_t200')._cell_mfma                   # (the conv-only cases do run the matrix-core cell)
+    assert session('D_lively_b2_t200')._stages.cell_mfma                   # (the conv-only cases do run the matrix-core cell)
 
 
 # ---- peek ----------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 """The launch sequence of a streaming session, pinned: every enqueueing C-ABI call of pushes, peeks and the flush of one utterance, in
-order, with its arguments, compared with a recording made before ``StreamingSession`` got its carried-state record
-(tests/golden/stream_launch_sequences.json).  Bit-identical logits do not show a window built in another buffer, a state copy that
-changed hands or a launch that moved; this does.  The listing and its summary are tests/test_launch_sequence_gpu.py's.
+order, with its arguments, compared with a recording made before ``StreamingSession`` got its carried-state record -- the bfloat16
+scenarios: before it got its stage engines -- (tests/golden/stream_launch_sequences.json, stream_launch_sequences_bf16.json).
+Bit-identical logits do not show a window built in another buffer, a state copy that changed hands or a launch that moved; this
+does.  The listing and its summary are tests/test_launch_sequence_gpu.py's.
 
 A scenario builds its session on a model with keyed parameters, runs its script once as a warm-up (every lazily made buffer, decoder
 and peek workspace exists after it), calls ``reset()`` and runs the same script again on the tape.
@@ -35,19 +36,22 @@ from test_launch_sequence_gpu import summarise          # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
+BF16 = torch.bfloat16
 FIXTURE = REPO / 'tests' / 'golden' / 'stream_launch_sequences.json'
+FIXTURE_BF16 = FIXTURE.with_name('stream_launch_sequences_bf16.json')      # the bfloat16 scenarios: a file of their own, the first stays as it was
 WIDTH = 4                       # the decoders' initial pool (1 + 4 * 160 nodes) holds every step: a step needs usage + 4 n + 1 of them
 
 _models = {}
 
 
-def model_for(arch, use_rnn):
-    """One model per (architecture, LSTM or not), with keyed parameters."""
-    key = (json.dumps(arch), use_rnn)
+def model_for(arch, use_rnn, dtype=torch.float32):
+    """One model per (architecture, LSTM or not, storage type), with keyed parameters (float32 values, then the cast: ``Module.to``
+    converts in place, so a bfloat16 model is one of its own)."""
+    key = (json.dumps(arch), use_rnn, dtype)
     if key not in _models:
         m = nb.get_model(arch, use_rnn=use_rnn, dropout_rate=0.0)
         m.load_state_dict(cases.keyed_params({k: tuple(v.shape) for k, v in m.state_dict().items()}, f'stream-launch/{key[0]}/{use_rnn}'))
-        _models[key] = m.to(DEV).eval()
+        _models[key] = m.to(DEV).to(dtype).eval()
     return _models[key]
 
 
@@ -125,8 +129,37 @@ def fused_cells():
     return sess, lambda: pushes(sess, x, (300,), False)
 
 
+def session16(arch, use_rnn, batch, max_chunk, **kw):
+    return streaming.StreamingSession(model_for(arch, use_rnn, BF16), batch, max_chunk, dtype=BF16, **kw)
+
+
+def bf16_greedy():
+    """The bfloat16 session's node-by-node cells with a ``linear`` node (its input LayerNorm applied in place by the stage before), the
+    on-load LayerNorm into the LSTM's projection, the recurrence, the head behind it, the peek's record and the widening for the decoder."""
+    sess = session16(cases.ARCH_M, True, 2, 64)
+    x = features(2, 280, 1).to(BF16)
+    return sess, lambda: pushes(sess, x, (100, 150, 0, 30), True)
+
+
+def bf16_mfma_cells_no_rnn():
+    """... its matrix-core cells with their on-load statistics, the last LayerNorm written as the float32 rows the head without the LSTM
+    reads, and two steps' logits joined over the padded bfloat16 buffer."""
+    sess = session16(cases.ARCH_A, False, 2, 160)
+    x = features(2, 300, 4).to(BF16)
+    return sess, lambda: pushes(sess, x, (300,), False)
+
+
+def bf16_audio_chunks_of_one():
+    """... the front-end's float32 frames rounded while the first window is built, the peek's third buffers and its scratch window
+    seen as bfloat16."""
+    sess = session16(cases.ARCH_M, True, 1, 1, frontend=frontend.LogMelFrontend(device=DEV))
+    wave = waves(1, 6400, 95)
+    return sess, lambda: pushes(sess, wave, (1600,) * 4, False, audio=True)
+
+
 SCENARIOS = {'greedy': greedy, 'beam_timed_lm_then_beam': beam_lm, 'audio': audio, 'audio_max_chunk_1': audio_chunks_of_one,
-             'node_by_node_cells': node_by_node, 'fused_cells': fused_cells}
+             'node_by_node_cells': node_by_node, 'fused_cells': fused_cells, 'bf16_greedy': bf16_greedy,
+             'bf16_mfma_cells_no_rnn': bf16_mfma_cells_no_rnn, 'bf16_audio_max_chunk_1': bf16_audio_chunks_of_one}
 
 
 def walk(sess):
@@ -206,7 +239,7 @@ def record(name):
 
 @pytest.fixture(scope='module')
 def pinned():
-    return json.loads(FIXTURE.read_text())
+    return {**json.loads(FIXTURE.read_text()), **json.loads(FIXTURE_BF16.read_text())}
 
 
 @pytest.mark.parametrize('name', list(SCENARIOS))
@@ -230,5 +263,6 @@ if __name__ == '__main__':
         raise SystemExit(__doc__)
     from nb_asr_amd import build
     build.build_library()
-    FIXTURE.write_text('{\n' + ',\n'.join(f'{json.dumps(name)}: {json.dumps(summarise(record(name)))}' for name in SCENARIOS) + '\n}\n')
-    print(f'wrote {len(SCENARIOS)} scenarios to {FIXTURE}')
+    for path, names in ((FIXTURE, [n for n in SCENARIOS if not n.startswith('bf16_')]), (FIXTURE_BF16, [n for n in SCENARIOS if n.startswith('bf16_')])):
+        path.write_text('{\n' + ',\n'.join(f'{json.dumps(name)}: {json.dumps(summarise(record(name)))}' for name in names) + '\n}\n')
+        print(f'wrote {len(names)} scenarios to {path}')

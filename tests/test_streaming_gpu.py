@@ -253,3 +253,25 @@ def test_interleaved_whole_forwards_change_nothing():
             assert torch.equal(m(y), alone), i
         outs.append(sess.flush())
     assert torch.equal(torch.cat(outs, 1), ref)
+
+
+def test_a_dropped_session_frees_its_memory_at_once():
+    """No reference cycle through a session: the last reference gone, its buffers go back to the allocator without the cycle collector
+    (which is off here) -- for the float32 and the bfloat16 session, after a push and a peek have made every lazily built part."""
+    import gc
+    import weakref
+    gc.disable()
+    try:
+        for dtype in (torch.float32, torch.bfloat16):
+            m = build(cases.ARCH_A, True, 'lively').to(dtype)
+            sess = streaming.StreamingSession(m, 1, max_chunk=8, dtype=dtype)
+            with torch.no_grad():
+                sess.push(keyed_input(1, 8, seed=7).to(DEV).to(dtype))
+                sess.peek()
+            torch.cuda.synchronize()
+            ref, owned, before = weakref.ref(sess), sess.buffer_bytes, torch.cuda.memory_allocated()
+            del sess
+            assert ref() is None, dtype
+            assert before - torch.cuda.memory_allocated() >= owned > 0, dtype
+    finally:
+        gc.enable()
