@@ -955,6 +955,28 @@ size_t nbasr_optim_workspace_bytes(int n_tensors, int n_chunks);
 int nbasr_optim_adam_step(const void* table, int n_tensors, int n_chunks, void* workspace, float* total_norm, double beta1, double beta2,
                           double eps, double max_norm, double weight_norm_coef, nbasr_stream_t stream);
 
+/* ---- dropout (reference ops.py:22,29,40,48: nn.Dropout behind every op; model.py:99: in front of the LSTM; model.py:22: the node's sum) ----
+ * Counter-based: the mask of an element is a pure function of (seed, call, row, frame).  Nothing is stored; backward is the same call
+ * on the incoming gradient with the same (p, seed, call, row0); the mask does not depend on the launch shape, on ld, or on how a batch
+ * is sliced into calls.  float32; x (rows, frames) with row pitch ld, a row = one (batch, channel) pair.
+ *   generator   Philox4x32-10 (multipliers D2511F53, CD9E8D57; Weyl constants 9E3779B9, BB67AE85 added to the key between rounds).
+ *   word        element (r, t) belongs to group g = (row0 + r) * ceil(frames / 4) + (t >> 2), a 64-bit number (modulo 2^64), and takes
+ *               word t & 3 of philox(counter = (g_lo, g_hi, call_lo, call_hi), key = (seed_lo, seed_hi)).  seed and call are 64-bit
+ *               patterns (negative values are legal); row0 >= 0 is the index of the first row within a larger tensor: a slice of a
+ *               batch gets the masks it would have in the whole.  Groups never straddle rows.
+ *   keep rule   thr = floor(p 2^32 + 0.5) in double, 0 <= p <= 1; kept iff word >= thr as unsigned 64-bit values (p = 0 keeps all,
+ *               p = 1 drops all); scale = (float)(1 / (1 - p)), 0 for p = 1; y = x * (kept ? scale : 0) in float32.  The multiply is
+ *               ATen's: a DROPPED Inf or NaN gives NaN, not 0.
+ *   node sum    skip0..2 (each may be NULL, none after a NULL one; same shape and pitch as x): y is the node's sum with the dropped
+ *               tensor as its first term, bit for bit what nbasr_skip_sum gives for (drop(x), skip0, skip1, skip2) three terms per
+ *               launch: (((+0 + drop(x)) + skip0) + skip1) + skip2, every product and sum rounded on its own.
+ * y may be x (in place).  Columns [frames, ld) of y are NOT written (an exception to the convention above: they keep what they held,
+ * zeros in an activation buffer).  Refused: NULL x or y (NBASR_ENULL); ld < frames, ld % 4 != 0, a pointer off 16 bytes (NBASR_EALIGN);
+ * p outside [0, 1] or NaN, a negative size, row0 < 0, a skip after a NULL skip (NBASR_EINVAL).  rows == 0 or frames == 0: nothing is
+ * launched, 0 is returned.  One launch, 8 bytes moved per element and 4 more per skip. */
+int nbasr_dropout(const void* x, const void* skip0, const void* skip1, const void* skip2, void* y, int rows, int frames, int ld, double p,
+                  long long seed, long long call, long long row0, nbasr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from . import ctc
 from . import frontend
 from . import streaming
 from . import optim
+from . import dropout
 from .streaming import StreamingSession
 from .search_space import (all_ops, get_search_space, get_all_architectures, get_random_architectures,
                            get_model_hash, arch_vec_to_names)

@@ -12,12 +12,13 @@ so that the reference's ``loss.backward()`` (trainer.py:220-223) reaches every p
 
 Correctness first: one launch group per op, nothing fused or deferred, tensor re-layouts as torch copies; gradients are checked against
 the reference modules' own autograd (tests/golden/grad_fixtures.npz, tests/test_backward_gpu.py) and, for the whole model, against fp64
-autograd through the oracle (tests/test_model_gpu.py).  Training-mode dropout (p > 0) is ATen's dropout on each op's output, as the
-reference places it (ops.py:22,29).  The fused inference executor (executor.py) stays the fast path for eval() / torch.no_grad().
+autograd through the oracle (tests/test_model_gpu.py).  Training-mode dropout (p > 0) sits on each op's output, as the reference places it
+(ops.py:22,29): ATen's by default, the counter-based HIP kernel -- fused with the node's sum -- after ``dropout.use('hip')`` (dropout.py).
+The fused inference executor (executor.py) stays the fast path for eval() / torch.no_grad().
 """
 import torch
 
-from . import backward, hip
+from . import backward, dropout, hip
 
 
 def _pitched(t):
@@ -244,8 +245,14 @@ def model_forward(model, x):
     from .model import SearchCell
     from .ops import PadConvRelu, Zero, Identity
     act, normalized = x, False                                 # normalized: act is a LayerNorm's output (dropout in between allowed)
+    hip_dropout = dropout.backend() == 'hip'
     for layer in model.model:
-        if isinstance(layer, PadConvRelu):
+        if (isinstance(layer, PadConvRelu) and hip_dropout and not torch.is_grad_enabled() and layer.groups == 1 and layer.kernel_size == 8
+                and layer.dilation == 1 and act.dtype == torch.float32):
+            # replayable masks are worth the same logits: without gradients the downsample convs take the GEMM route they take with
+            # them (the module's plain route is another one), so that this forward equals the differentiable one from the same state
+            act, normalized = dense_pad_conv_relu(act, layer.conv.weight, layer.conv.bias, layer.strides, normalized), False
+        elif isinstance(layer, PadConvRelu):
             layer.input_is_normalized = normalized             # (for this call only: a standalone call of the module gets the strict rule)
             try:
                 act, normalized = layer(act), False            # routes to dense_pad_conv_relu / grouped_pad_conv_relu under autograd
@@ -260,14 +267,24 @@ def model_forward(model, x):
             outs = [act]
             for node in layer.nodes:
                 op = node.op
-                terms = [] if isinstance(op, Zero) else [op(outs[-1])]
-                terms += [src for branch, src in zip(node.branch_ops, outs) if isinstance(branch, Identity)]
+                skips = [src for branch, src in zip(node.branch_ops, outs) if isinstance(branch, Identity)]
+                if skips and hip_dropout and op.training and getattr(op, 'dropout_rate', 0) > 0:
+                    # the op's dropout and the node's sum in one launch: the same call number, the same bits as the two apart
+                    op.defer_dropout = True
+                    try:
+                        z = op(outs[-1])
+                    finally:
+                        op.defer_dropout = False
+                    outs.append(skip_sum([dropout.dropout(z, op.dropout_rate, True, skips[:3])] + skips[3:]))
+                    continue
+                terms = ([] if isinstance(op, Zero) else [op(outs[-1])]) + skips
                 outs.append(skip_sum(terms) if terms else op(outs[-1]))          # (no term at all: the `zero` op's zeros)
             act, normalized = outs[-1], False
             if layer.use_norm:
                 act, normalized = layer_norm_channels(act, layer.norm_layer.weight, layer.norm_layer.bias, layer.norm_layer.eps), True
         elif isinstance(layer, nn.Dropout):
-            act = layer(act)                                   # ATen's dropout (identity in eval mode or with p == 0)
+            # identity in eval mode or with p == 0; else ATen's dropout, or the counter-based kernel after dropout.use('hip')
+            act = dropout.dropout(act, layer.p, layer.training) if hip_dropout else layer(act)
         elif isinstance(layer, nn.LSTM):
             normalized = False
             act = lstm(act, layer.weight_ih_l0, layer.weight_hh_l0, layer.bias_ih_l0, layer.bias_hh_l0)      # (B, T, H)

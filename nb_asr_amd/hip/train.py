@@ -1,10 +1,11 @@
 """The single-launch backward building blocks; backward.py strings the last eight together (nbasr.h says what each
-computes).  The optimisation step's signatures are registered here too; its wrappers, with their tables, are optim.py."""
+computes).  The optimisation step's signatures are registered here too; its wrappers, with their tables, are optim.py.  ``dropout`` is the
+counter-based dropout launch of the training path; its seed and call counter are kept by nb_asr_amd/dropout.py."""
 import ctypes
 
 import torch
 
-from . import SIGNATURES, load_library, _call, _scratch, _stream, _dev, _opt, _c_float_p, _c_int, _c_stream
+from . import SIGNATURES, HipError, load_library, _call, _scratch, _stream, _dev, _opt, _skips3, _signed64, _c_float_p, _c_int, _c_stream
 
 SIGNATURES.update({
     'nbasr_grouped_conv1d_backward_workspace_bytes': (ctypes.c_size_t, [_c_int] * 4),
@@ -22,7 +23,23 @@ SIGNATURES.update({
     'nbasr_optim_table_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_optim_workspace_bytes': (ctypes.c_size_t, [_c_int] * 2),
     'nbasr_optim_adam_step': (_c_int, [ctypes.c_void_p, _c_int, _c_int, ctypes.c_void_p, _c_float_p] + [ctypes.c_double] * 5 + [_c_stream]),
+    'nbasr_dropout': (_c_int, [_c_float_p] * 5 + [_c_int] * 3 + [ctypes.c_double] + [ctypes.c_longlong] * 3 + [_c_stream]),
 })
+
+
+def dropout(x, y, frames, p, seed, call, skips=(), row0=0):
+    """y[..., :frames] = x * (kept ? 1 / (1 - p) : 0) (+ up to three skips, the node's sum left to right) with the counter-based mask of
+    (seed, call, row0 + row, frame): nbasr.h "dropout".  x, y and the skips: float32 tensors of one shape (..., ld), rows = the product
+    of the leading dimensions; y may be x.  The pitch columns of y are not written.  Backward is the same call on the gradient."""
+    ld = x.shape[-1]
+    if tuple(y.shape) != tuple(x.shape) or any(tuple(s.shape) != tuple(x.shape) for s in skips):
+        raise HipError(f'dropout: y and the skips must have the shape of x, {tuple(x.shape)}')
+    if len(skips) > 3:
+        raise HipError(f'dropout: at most three skips per launch (got {len(skips)})')
+    s = _skips3(skips)
+    _call('nbasr_dropout', _dev(x, 'x'), _opt(s[0], 'skip0'), _opt(s[1], 'skip1'), _opt(s[2], 'skip2'), _dev(y, 'y'), x.numel() // max(ld, 1),
+          frames, ld, float(p), _signed64(seed), _signed64(call), int(row0), _stream(x))
+    return y
 
 
 def grouped_conv1d_backward(x, weight, z, dz, frames, groups, kernel, dilation, need_dx=True, need_dw=True):

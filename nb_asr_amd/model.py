@@ -255,7 +255,7 @@ class ASRModel(nn.Module):
         if self.training and self.dropout_rate > 0 and _taps is None and not _pipelined and input.dtype == torch.float32:
             # training mode, p > 0, NO gradients (reference: get_model returns the module in training mode, model/torch/__init__.py:7-35,
             # and `model(x)` under torch.no_grad() applies its dropout masks, ops.py:22,29,40,48, model.py:99): the same op-by-op path
-            # as the differentiable forward -- every op's HIP kernel, then ATen's dropout on its output -- since the fused executor
+            # as the differentiable forward -- every op's HIP kernel, then dropout on its output (ATen's, or dropout.py's) -- since the fused executor
             # holds no masks (VERDICT r5 missing 3).  forward_async / forward_graph / forward_with_taps and bf16 still refuse below.
             from .autograd import model_forward
             with torch.no_grad():

@@ -11,15 +11,16 @@ The torch modules nested inside (``nn.Conv1d``, ``nn.Linear``) are parameter con
 their ``forward`` is never called.  Calling an op on its own takes a ``(B, C, T)`` float32 tensor
 on a HIP device; inside ``ASRModel`` the executor drives the same C entry points on pitched
 workspace buffers instead (see ``executor.py``).  Dropout is the identity in eval mode or with
-``p == 0``; in training mode with ``p > 0`` every op applies ATen's dropout to its output, as the
-reference does (ops.py:22,29,40,48) -- with or without gradients enabled.
+``p == 0``; in training mode with ``p > 0`` every op applies dropout to its output, as the
+reference does (ops.py:22,29,40,48) -- with or without gradients enabled: ATen's by default, the
+counter-based HIP kernel after ``nb_asr_amd.dropout.use('hip')``.
 """
 import functools
 
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import dropout, hip
 
 CLAMP_MAX = 20.0
 GROUPS = 100
@@ -40,9 +41,14 @@ def _pitched(x):
 
 
 def _train_dropout(module, y):
-    """The op's trailing nn.Dropout (reference ops.py:22,29 / 40,48): ATen's dropout on the op's output -- on the differentiable path
-    and, round 6, on the plain one too (a training-mode module under ``torch.no_grad()``: the reference applies its masks there)."""
+    """The op's trailing nn.Dropout (reference ops.py:22,29 / 40,48): dropout on the op's output, ATen's or (dropout.use('hip')) the HIP
+    kernel's -- on the differentiable path and, round 6, on the plain one too (a training-mode module under ``torch.no_grad()``: the
+    reference applies its masks there)."""
     if module.training and module.dropout_rate > 0:
+        if getattr(module, 'defer_dropout', False):                 # model_forward fuses it with the node's sum (dropout.use('hip'))
+            return y
+        if dropout.backend() == 'hip':
+            return dropout.dropout(y, module.dropout_rate, True)     # the counter-based kernel: no stored mask, replayable
         return torch.nn.functional.dropout(y, module.dropout_rate, True)
     return y
 
