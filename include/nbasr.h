@@ -424,7 +424,7 @@ int nbasr_ctc_beam_search(const float* log_probs, const int* lengths, void* ws, 
 int nbasr_token_error_counts(const int* hyp, const int* hyp_len, int ld_hyp, const int* ref, const int* ref_len, int ld_ref,
                              const int* table, int n_table, int blank, int* counts, int batch, nbasr_stream_t stream);
 
-/* ---- streaming beam decode (nb_asr_amd/ctc.py BeamSearchStream) -----------------------------------------------------------
+/* ---- streaming beam decode (nb_asr_amd.ctc BeamSearchStream) -----------------------------------------------------------
  * nbasr_ctc_beam_search resumed chunk by chunk: a chain of steps over the frames of a stream gives, after
  * nbasr_ctc_beam_stream_finish, bit for bit what one nbasr_ctc_beam_search over the concatenated frames gives.
  *   state: nbasr_ctc_beam_stream_state_bytes(batch, beam_width, pool_nodes), 8-byte aligned, set up by nbasr_ctc_beam_stream_init
@@ -452,7 +452,7 @@ int nbasr_ctc_beam_stream_step(const float* log_probs, const int* chunk_lengths,
 int nbasr_ctc_beam_stream_finish(const void* state, int* beams, float* scores, int* beam_lens, int ld_beams, int batch, int beam_width,
                                  int pool_nodes, nbasr_stream_t stream);
 
-/* ---- per-token time steps (ctcdecode's fourth output; nb_asr_amd/ctc.py beam_decode(return_timesteps=True), BeamSearchStream(
+/* ---- per-token time steps (ctcdecode's fourth output; nb_asr_amd.ctc beam_decode(return_timesteps=True), BeamSearchStream(
  * timesteps=True)) -- the same searches, bit for bit, that also report for every token the frame at which its class had the largest
  * log-probability among the frames that extended into its node (ctcdecode's PathTrie::get_path_trie; the rule is DESIGN.md 9 "Beam
  * decode"): a new prefix's node starts at the frame that created it; while the prefix and its parent string are both live, a frame with a
@@ -477,7 +477,7 @@ int nbasr_ctc_beam_stream_timed_step(const float* log_probs, const int* chunk_le
 int nbasr_ctc_beam_stream_timed_finish(const void* state, int* beams, float* scores, int* timesteps, int* beam_lens, int ld_beams,
                                        int batch, int beam_width, int pool_nodes, nbasr_stream_t stream);
 
-/* ---- peek: a read-only "finish after these frames" (nb_asr_amd/ctc.py BeamSearchStream.peek) ---------------------------------
+/* ---- peek: a read-only "finish after these frames" (nb_asr_amd.ctc BeamSearchStream.peek) ---------------------------------
  * nbasr_ctc_beam_stream_peek takes one chunk log_probs(batch, frames, classes) with chunk_lengths(batch) or NULL, as _step does, and
  *   writes what _finish would write if _step had first been run on that chunk: beams(batch, beam_width, ld_beams) = the live prefixes'
  *   tokens after the prefix the STATE has committed (the step would commit more of them: the same tokens, split elsewhere), best first,
@@ -498,7 +498,7 @@ int nbasr_ctc_beam_stream_timed_peek(const float* log_probs, const int* chunk_le
                                      int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes, int beam_width,
                                      int blank, int cutoff_top_n, int pool_nodes, nbasr_stream_t stream);
 
-/* ---- bigram LM fusion (ctcdecode's alpha / beta with a character-based scorer; nb_asr_amd/ctc.py beam_decode(lm=...),
+/* ---- bigram LM fusion (ctcdecode's alpha / beta with a character-based scorer; nb_asr_amd.ctc beam_decode(lm=...),
  * BeamSearchStream(lm=...)) --------------------------------------------------------------------------------------------------------
  * The searches above with one fusion table W added to the log scores: `fusion`, float32, (classes, classes), row-major, on the device.
  *   W[p][c] is added whenever a prefix whose last token is p is extended by class c.  Row `blank` is the utterance-start context (the empty
@@ -532,7 +532,7 @@ int nbasr_ctc_beam_stream_lm_peek(const float* log_probs, const int* chunk_lengt
                                   float* scores, int* timesteps, int* beam_lens, int ld_beams, int batch, int frames, int classes,
                                   int beam_width, int blank, int cutoff_top_n, int pool_nodes, int timed, nbasr_stream_t stream);
 
-/* ---- endpointing: when has an utterance ended? (nb_asr_amd/ctc.py endpoint / EndpointStream; DESIGN.md 9 "Endpoint") ---------------
+/* ---- endpointing: when has an utterance ended? (nb_asr_amd.ctc endpoint / EndpointStream; DESIGN.md 9 "Endpoint") ---------------
  * No reference counterpart (the reference decodes whole utterances); the rules are the shape of Kaldi's online endpoint rules.  The
  * definition is integer-exact after one float32 compare per frame, so whole = chunked = peeked = a row alone, bit for bit.
  *   x(batch, frames, classes) float32, contiguous: logits or log-probabilities (the rule is invariant to a shift of a frame);
@@ -565,7 +565,7 @@ int nbasr_ctc_endpoint_step(const float* x, const int* lengths, const int* state
                             long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out, int batch, int frames, int classes,
                             nbasr_stream_t stream);
 
-/* ---- segmentation: where are the stretches of speech in this stream? (nb_asr_amd/ctc.py segment / SegmentStream; DESIGN.md 9 "Segments")
+/* ---- segmentation: where are the stretches of speech in this stream? (nb_asr_amd.ctc segment / SegmentStream; DESIGN.md 9 "Segments")
  * No reference counterpart.  The speech decision of a frame is the endpointer's (steps 1 and 2 above, with the same x, lengths, speech
  * set and margin); on it runs an automaton with hysteresis that re-arms: it opens and closes segments for as long as frames arrive and
  * keeps the last `capacity` closed ones in a ring.  Integer-exact after the one float32 compare per frame, so whole = chunked = peeked =
@@ -597,7 +597,7 @@ int nbasr_ctc_segment_step(const float* x, const int* lengths, const int* state_
                            int max_frames, int capacity, long long speech_lo, long long speech_hi, float margin, unsigned char* mask_out,
                            int batch, int frames, int classes, nbasr_stream_t stream);
 
-/* ---- keywords: has this phrase just been said? (nb_asr_amd/ctc.py spot_keywords / KeywordStream; DESIGN.md 9 "Keywords") -------------
+/* ---- keywords: has this phrase just been said? (nb_asr_amd.ctc spot_keywords / KeywordStream; DESIGN.md 9 "Keywords") -------------
  * No reference counterpart.  Per (utterance, keyword) and frame: the score of the best CTC path that spells the keyword, ends at this
  * frame and starts anywhere, as a log-likelihood ratio against the unconstrained best path over the same frames.  Every step is a float32
  * compare, one subtract or one add in a fixed order, so whole = chunked = peeked = a row alone = a keyword alone, bit for bit.
@@ -642,7 +642,7 @@ int nbasr_ctc_keyword_step(const float* x, const int* lengths, const int* tokens
                            int n_keywords, int blank, const int* state_in, int* state_out, float* scores_out, int* starts_out, int batch,
                            int frames, int classes, nbasr_stream_t stream);
 
-/* ---- confidence: how sure is the recogniser of each token? (nb_asr_amd/ctc.py confidence / ConfidenceStream; DESIGN.md 9 "Confidence")
+/* ---- confidence: how sure is the recogniser of each token? (nb_asr_amd.ctc confidence / ConfidenceStream; DESIGN.md 9 "Confidence")
  * No reference counterpart.  The frame measures are Laptev and Ginsburg's: each frame's softmax becomes a number in [0, 1],
  * quantised at once to an integer, and the integers are aggregated over the frames of each token.  Everything after the quantisation is
  * integer arithmetic, so whole = chunked = peeked = a row alone, bit for bit.

@@ -1,4 +1,4 @@
-// Per-token confidence over CTC logits (nb_asr_amd/ctc.py confidence / ConfidenceStream): the definition of include/nbasr.h "confidence"
+// Per-token confidence over CTC logits (nb_asr_amd.ctc confidence / ConfidenceStream): the definition of include/nbasr.h "confidence"
 // and DESIGN.md 9 "Confidence".  A frame's softmax becomes one number in [0, 1] (the probability of its label, or the normalised Gibbs or
 // Tsallis entropy of Laptev and Ginsburg), quantised at once to q = rint(conf * 2^24); a token -- a maximal run of one non-blank label --
 // records the minimum and the 64-bit sum of its frames' q.  Everything after the quantisation is integer arithmetic, so whole = chunked

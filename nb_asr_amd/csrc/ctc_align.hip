@@ -1,4 +1,4 @@
-// CTC forced alignment (nb_asr_amd/ctc.py forced_align; include/nbasr.h nbasr_ctc_forced_align): given the transcript, the best path
+// CTC forced alignment (nb_asr_amd.ctc forced_align; include/nbasr.h nbasr_ctc_forced_align): given the transcript, the best path
 // through the blank-extended label sequence, the frames of every token and their scores.  The reference has no aligner; the definition
 // is the one of include/nbasr.h, stated again in tests/ctc_align_model.py.  Where ctc_loss.hip sums over all paths, this kernel takes the
 // maximum, keeps a 2-bit back-pointer per cell and walks them back.  One wavefront per utterance, as in ctc_loss.hip.

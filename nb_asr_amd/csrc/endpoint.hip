@@ -1,4 +1,4 @@
-// Utterance endpointing over CTC logits (nb_asr_amd/ctc.py endpoint / EndpointStream): the definition of include/nbasr.h "endpointing" and
+// Utterance endpointing over CTC logits (nb_asr_amd.ctc endpoint / EndpointStream): the definition of include/nbasr.h "endpointing" and
 // DESIGN.md 9 "Endpoint".  A frame is SPEECH iff the largest value over the speech classes exceeds the largest over the others by more than
 // `margin`; a row carries six integers (frames, speech frames, first / last speech frame, endpoint frame and rule) and the first frame at
 // which a rule (min_speech, min_trailing, min_frames) holds latches the endpoint.  Everything after the one float compare is integer

@@ -1,4 +1,4 @@
-// Keyword spotting over CTC logits (nb_asr_amd/ctc.py spot_keywords / KeywordStream): the definition of include/nbasr.h "keywords" and
+// Keyword spotting over CTC logits (nb_asr_amd.ctc spot_keywords / KeywordStream): the definition of include/nbasr.h "keywords" and
 // DESIGN.md 9 "Keywords".  A keyword of L tokens has S = 2 L - 1 states (token, blank, token, ...: no leading or trailing blank, the start
 // is free and a match ends on its last token's frame).  Per frame V'[s] = max(stay, advance, skip the blank, for s = 0 a fresh start at 0)
 // + (x[z(s)] - m), m the frame's maximum; V'[S - 1] is the log-likelihood ratio of the best path that spells the keyword and ends here

@@ -1,4 +1,4 @@
-// Speech segmentation over CTC logits (nb_asr_amd/ctc.py segment / SegmentStream): the definition of include/nbasr.h "segmentation" and
+// Speech segmentation over CTC logits (nb_asr_amd.ctc segment / SegmentStream): the definition of include/nbasr.h "segmentation" and
 // DESIGN.md 9 "Segments".  The speech decision of a frame is the endpointer's; on top of it runs an automaton with hysteresis that
 // re-arms: a run of min_speech speech frames opens a segment, a run of min_silence other frames closes it (at the run's first frame),
 // and a segment that reaches max_frames is closed by force.  A row carries five integers (frames, the two runs, the open segment's
